@@ -1,6 +1,7 @@
 """bench.py -- headline benchmark of the sparse-matmul hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|c2|c5] [--reduce sum] [--exchange allgather|halo|pipelined]
+                    [--dump-outputs DIR] [--full]
 
 One *step* = one pass of the hot path over one batch of synthetic input that is already resident
 in HBM: at N = 1 a CSR SpMM (tsamd_spmm: merge-path partition + merge + carry fix-up kernels); at
@@ -18,13 +19,24 @@ Workloads:
 
 Rank 0 prints ONE JSON line (see README/DESIGN.md for the field meanings).  Timing: W warm-up
 steps, then K steps between barrier + torch.cuda.synchronize() on both sides, max over ranks.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs
+(--dump-outputs) and the line (metric, value, unit, ms_per_step, ... and the workload's config).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32 / float64;
+a fixed, seeded sample of its rows when the whole would exceed DUMP_BYTES): `out` at N = 1,
+`out_rank<r>` per rank at N > 1.  The inputs depend on the arguments only, so two builds can be
+compared output for output.
+
+--full adds everything that explains the number (it used to be the default):
 `roofline` is measured live on the SpMM merge kernel with HIP events on the launch stream
 (tsamd_spmm_profiled); `cpu_baseline` times the reference's own CPU kernel (oracle/_ref, built
-from /root/reference) on the host cores -- rank 0, N = 1 only -- and its output is compared with
-the WHOLE GPU output (`cpu_baseline.parity`).  At N = 1 the default run also carries
+from the reference sources) on the host cores -- rank 0, N = 1 only -- and its output is compared
+with the WHOLE GPU output (`cpu_baseline.parity`).  At N = 1 such a run also carries
   `control`    the same kernel on a uniform-degree graph of the same size (load balance vs bandwidth)
   `secondary`  BASELINE.json configs C2 / C3 / C4 at their stated size, each with ms, roofline,
                cpu_baseline and whole-output parity (tests/baseline_configs.py; --no-secondary skips).
+At N > 1 it carries the exchange breakdown and the other exchanges timed beside the headline one.
+The full result goes to stderr and to profiles/bench_last_full.json (not kept in git).
 """
 import argparse
 import json
@@ -178,8 +190,8 @@ def secondary(dev, cpu=True, stress=False):
 
 # ------------------------------------------------------------------------------------------------
 # the ONE stdout line: numbers only, a few KB (the driver parses the tail of stdout; round 4's 22 KB line did not
-# fit its window).  Everything else -- notes, scopes, full parity statistics -- goes to stderr and to
-# profiles/bench_last_full.json / gpurun_out/bench_last_full.json.
+# fit its window).  Everything else -- notes, scopes, full parity statistics -- goes to stderr and, in a --full run,
+# to profiles/bench_last_full.json.
 # ------------------------------------------------------------------------------------------------
 def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
@@ -275,18 +287,47 @@ def compact_line(full):
 
 
 def emit(full):
-    """Full result -> stderr + profiles/bench_last_full.json + gpurun_out/bench_last_full.json; compact line -> stdout,
-    LAST (nothing may be printed to stdout after it)."""
+    """Full result (--full) -> stderr + profiles/bench_last_full.json; compact line -> stdout, LAST (nothing may be
+    printed to stdout after it)."""
     text = json.dumps(full)
-    for d in ('profiles', 'gpurun_out'):
-        try:
-            os.makedirs(os.path.join(ROOT, d), exist_ok=True)
-            with open(os.path.join(ROOT, d, 'bench_last_full.json'), 'w') as fh:
-                fh.write(text + '\n')
-        except OSError:
-            pass
+    try:
+        os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
+        with open(os.path.join(ROOT, 'profiles', 'bench_last_full.json'), 'w') as fh:
+            fh.write(text + '\n')
+    except OSError:
+        pass
     print('[bench] full result: ' + text, file=sys.stderr, flush=True)
     print(json.dumps(compact_line(full)), flush=True)
+
+
+def headline_line(head):
+    """The line of a plain run: the contract fields and the workload's config, nothing measured beside the steps."""
+    line = {k: head[k] for k in HEAD_KEYS if k in head}
+    line['config'] = dict(head.get('config', {}))
+    return line
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: at most this many bytes of samples in all (every rank's together)
+DUMP_SEED = 20240601   # fixes which rows a sample keeps
+
+
+def dump_outputs(out, dirname, name, share=1):
+    """What the timed path returned (`out`, [rows, ...]) -> dirname/<name>.npy, float32 (float64 for a float64
+    result).  When the whole exceeds DUMP_BYTES / share, a fixed, seeded sample of its rows (kept in row order):
+    the same rows for the same shape on every run."""
+    import numpy as np
+    o = out.detach()
+    o = o.reshape(o.size(0), -1) if o.dim() > 1 else o.reshape(-1, 1)
+    dt = torch.float64 if o.dtype == torch.float64 else torch.float32
+    esize = 8 if dt == torch.float64 else 4
+    keep = max(1, (DUMP_BYTES // share) // max(1, o.size(1) * esize))
+    if keep < o.size(0):
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        rows = torch.randperm(o.size(0), generator=g)[:keep].sort().values
+        o = o.index_select(0, rows.to(o.device))
+    arr = o.to(dt).cpu().numpy().reshape((-1, ) + tuple(out.shape[1:]) if out.dim() > 1 else (-1, ))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + '.npy'), arr)
 
 
 def relabelled_leg(rowptr, col, value, x, out, reduce, steps, dev):
@@ -470,7 +511,17 @@ def _main():
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help='weak (default): every rank owns 2**scale rows; strong: the single-GPU matrix is cut '
                          'into N row blocks of equal nnz')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step returned to DIR/<name>.npy (a fixed, seeded '
+                         'sample of its rows when it is larger than %d MB)' % (DUMP_BYTES >> 20))
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything that explains the headline (roofline with its rocprofv3 --pmc children, '
+                         'cpu_baseline and parity, repeated-operand / relabelled / control legs, the secondary configs; '
+                         'at N > 1 the exchange breakdown and variants) and write profiles/bench_last_full.json.  '
+                         'Off: the run sets up, warms up, times the steps and prints the headline line')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     args.workload = args.workload or default_workload(world)
@@ -540,14 +591,15 @@ def _main():
         with torch.no_grad():
             return run_op(sharded)  # (RCCL exchange of X rows,) then the local SpMM
 
-    # operands of ONE local SpMM launch, for the roofline / parity / cpu-baseline legs below
-    if isinstance(sharded, (RowShardedSpMM, OverlappedAllGatherSpMM)):
-        x_full, col_k = RowShardedSpMM(rowptr, col, value, x_sizes, None, op_spmm).gather(x_local), col
-    elif isinstance(sharded, HaloShardedSpMM):
-        x_full, col_k = sharded.exchange(x_local), sharded.col
-    else:  # pipelined: reproduce the full block with a one-shot halo plan (setup only)
-        ref_plan = HaloShardedSpMM(rowptr, col, value, x_sizes, None, op_spmm)
-        x_full, col_k = ref_plan.exchange(x_local), ref_plan.col
+    # operands of ONE local SpMM launch, for the roofline / parity / cpu-baseline legs of --full below
+    if args.full:
+        if isinstance(sharded, (RowShardedSpMM, OverlappedAllGatherSpMM)):
+            x_full, col_k = RowShardedSpMM(rowptr, col, value, x_sizes, None, op_spmm).gather(x_local), col
+        elif isinstance(sharded, HaloShardedSpMM):
+            x_full, col_k = sharded.exchange(x_local), sharded.col
+        else:  # pipelined: reproduce the full block with a one-shot halo plan (setup only)
+            ref_plan = HaloShardedSpMM(rowptr, col, value, x_sizes, None, op_spmm)
+            x_full, col_k = ref_plan.exchange(x_local), ref_plan.col
 
     # The headline steps run with the operand cache OFF (the ops' default: they keep no state between calls): every
     # step does all of its work (probe, relabelled copy of X, partition, merge, fix-up).  What a caller sees who
@@ -569,6 +621,8 @@ def _main():
     elapsed = time.perf_counter() - t0
     if args.pmc_child:  # under rocprofv3 --pmc: the headline launches are all that is wanted
         return
+    if args.dump_outputs:  # what the last timed step returned (this rank's row block at N > 1)
+        dump_outputs(out, args.dump_outputs, 'out' if world == 1 else 'out_rank%d' % rank, share=world)
 
     # the headline number is settled HERE (max over ranks of the timed region, edges summed over ranks), before any of
     # the explanatory legs below issues another collective
@@ -581,6 +635,25 @@ def _main():
         total_edges = float(stats[1])
     else:
         total_edges = float(E)
+    if not args.full:  # a plain run: the headline line and nothing else
+        if rank == 0:
+            data = 'synthetic' if backend == 'nccl' else \
+                'synthetic (REHEARSAL over %s, ranks share GPUs: not a measurement)' % backend
+            head = dict(metric='SpMM GEdges/s', value=round(total_edges * args.steps / elapsed / 1e9, 3), unit='GEdges/s',
+                        n_gpus=world, steps=args.steps, warmup=args.warmup,
+                        ms_per_step=round(elapsed / args.steps * 1e3, 4), higher_is_better=True,
+                        scaling=(args.scaling if world > 1 else 'weak'), vs_baseline=None, dtype='f32', data=data,
+                        config=dict(workload=wl['desc'], reduce=args.reduce, rows_per_gpu=m_local, cols=n_global,
+                                    edges_per_gpu=E, features=F,
+                                    parallelism='row-sharded x%d%s' % (world, (', exchange %s' % args.exchange)
+                                                                       if world > 1 else '')))
+            if fallback_reason is not None:
+                head['config']['exchange_fallback'] = 'requested %s; %s' % (requested, fallback_reason)
+            print(json.dumps(headline_line(head)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # N > 1: everything after this point (exchange breakdown, the other exchanges, roofline launches) only EXPLAINS the
     # number.  If one of those legs stalls on a collective -- they have never run on real xGMI hardware -- a watchdog
     # prints the headline line without them after --extras-timeout seconds and ends every rank, so that an unattended

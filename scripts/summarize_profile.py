@@ -49,7 +49,7 @@ merge = [k for k in pmc if 'spmm_merge_kernel' in k]
 traffic = None
 lines = ['# %s profile summary (%s workload)' % (tag, workload), '',
          'Source: `scripts/profile_round.sh %s` on one MI355X (gpurun); raw CSVs were under `gpurun_out/%s/`.' % (tag, tag), '',
-         '## rocprofv3 --kernel-trace --stats  (`python bench.py`, the default command: headline + control + relabelled leg + C2/C3/C4)', '',
+         '## rocprofv3 --kernel-trace --stats  (`python bench.py --full`: headline + control + relabelled leg + C2/C3/C4)', '',
          '| kernel | calls | avg us | total us | % of GPU time |', '|---|---|---|---|---|']
 for k, r in ts.items():
     lines.append('| `%s` | %s | %.2f | %.1f | %s |' % (k, r['Calls'], float(r['AverageNs']) / 1e3, float(r['TotalDurationNs']) / 1e3, r['Percentage']))
@@ -58,7 +58,7 @@ lines += ['', '(the remaining GPU time of that run is ATen input generation: R-M
 ph = os.path.join(src, 'trace_headline', 'bench_kernel_stats.csv')
 head_avg = None
 if os.path.exists(ph):
-    lines += ['## rocprofv3 --kernel-trace --stats  (`python bench.py --headline-only`: only north-star launches)', '',
+    lines += ['## rocprofv3 --kernel-trace --stats  (`python bench.py --full --headline-only`: only north-star launches)', '',
               '| kernel | calls | avg us | total us |', '|---|---|---|---|']
     for r in csv.DictReader(open(ph)):
         if 'tsamd' in r['Name']:

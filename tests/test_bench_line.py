@@ -72,3 +72,34 @@ def test_bare_multi_gpu_line():
                 extras='withheld: ' + 'y' * 1000)
     line = bench.compact_line(bare)
     assert line['n_gpus'] == 8 and len(json.dumps(line)) < 1000
+
+
+def test_plain_run_line_is_the_headline_only():
+    """A plain run (no --full) prints the contract fields and the workload's config, nothing measured beside the steps."""
+    full = _full_result()
+    line = bench.headline_line(full)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+        assert line[k] == full[k], k
+    assert set(line) <= set(bench.HEAD_KEYS) | {'config'}
+    assert line['config'] == full['config']
+    assert json.loads(json.dumps(line)) == line
+
+
+def test_dump_outputs_fixed_sample_within_budget(tmp_path):
+    """--dump-outputs: float32 rows of the output, a seeded sample of fixed rows when the whole is too large."""
+    import numpy as np
+    import torch
+    small = torch.randn(100, 8)
+    bench.dump_outputs(small, str(tmp_path), 'small')
+    a = np.load(tmp_path / 'small.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy())
+    rows = bench.DUMP_BYTES // (64 * 4)
+    big = torch.arange((rows * 2) * 64, dtype=torch.float32).view(rows * 2, 64)
+    bench.dump_outputs(big, str(tmp_path), 'a')
+    bench.dump_outputs(big, str(tmp_path), 'b')
+    a, b = np.load(tmp_path / 'a.npy'), np.load(tmp_path / 'b.npy')
+    assert a.shape == (rows, 64) and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+    first = (a[:, 0] / 64).astype(np.int64)  # the rows kept, in row order, each whole
+    assert np.all(np.diff(first) > 0) and np.array_equal(a, big.numpy()[first])
+    bench.dump_outputs(big.double(), str(tmp_path), 'd', share=2)
+    assert np.load(tmp_path / 'd.npy').dtype == np.float64 and (tmp_path / 'd.npy').stat().st_size <= bench.DUMP_BYTES // 2 + 4096

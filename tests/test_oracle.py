@@ -13,6 +13,21 @@ from pytorch_sparse_amd import synth
 from tests.util import ALL_DTYPES, CODE, fromnp, tonp
 
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
+# outputs of the compiled reference (oracle/_ref), recorded with their inputs by tests/golden/make_ref_cases.py into
+# tests/golden/ref_<family>.npz: the tests below check them always, and the live reference too when it is built.  The
+# recorded cases are the live cases' generators at a smaller size (RECORDED_*), which keeps the files small.
+RECORDED_SPMM_SCALE, RECORDED_VALUE_BW_SCALE, RECORDED_SAMPLER_SMALL = 6, 5, True
+_ref_cases = {}
+
+
+def ref_cases(family):
+    if family not in _ref_cases:
+        _ref_cases[family] = np.load(os.path.join(GOLDEN, 'ref_%s.npz' % family))
+    return _ref_cases[family]
+
+
+def dtype_name(dtype):
+    return str(dtype).split('.')[-1]
 
 
 def test_readme_spmm_vector():
@@ -70,13 +85,10 @@ def test_ind2ptr_ptr2ind_vectors():
     assert oc.ptr2ind([0, 0, 0], 0).tolist() == []
 
 
-@pytest.mark.skipif(not ref.available(), reason='oracle/_ref not built')
-@pytest.mark.parametrize('dtype', ALL_DTYPES)
-@pytest.mark.parametrize('reduce', ['sum', 'mean', 'min', 'max'])
-def test_c_oracle_matches_compiled_reference(dtype, reduce):
-    r = ref.ops()
-    rp, c = synth.rmat_csr(9, 8, seed=3)
-    E, n = c.numel(), 512
+def spmm_case_inputs(dtype, scale=9):
+    """Inputs of test_c_oracle_matches_compiled_reference -> (rowptr, col, value, mat)."""
+    rp, c = synth.rmat_csr(scale, 8, seed=3)
+    E, n = c.numel(), 1 << scale
     if dtype.is_floating_point:
         v = synth.values(E, dtype=dtype)
         x = synth.features(n, 7, dtype=dtype, batch=(2, ))
@@ -89,56 +101,110 @@ def test_c_oracle_matches_compiled_reference(dtype, reduce):
         # a row whose length is a multiple of 256 would be a division by zero (SIGFPE) there
         deg = rp[1:] - rp[:-1]
         assert not bool(((deg % 256 == 0) & (deg > 0)).any())
-    for value in (v, None):
-        if reduce == 'sum':
-            ro, ra = r.spmm_sum(None, rp, c, value, None, None, x), None
-        elif reduce == 'mean':
-            ro, ra = r.spmm_mean(None, rp, c, value, None, None, None, x), None
-        elif reduce == 'min':
-            ro, ra = r.spmm_min(rp, c, value, x)
-        else:
-            ro, ra = r.spmm_max(rp, c, value, x)
-        co, ca = oc.spmm(CODE[dtype], reduce, rp.numpy(), c.numpy(), tonp(value), tonp(x))
-        assert np.array_equal(tonp(ro), co)  # bit-exact, narrow types included
-        if ra is not None:
-            # where no entry beat the reducer's init value (all candidates equal numeric_limits::max /
-            # lowest: e.g. an all-zero uint8 row under max) the reference leaves a stale index behind --
-            # unspecified; the oracle (and the HIP path) report E there
-            deg = (rp[1:] - rp[:-1]).numpy()
-            unspecified = (ca == E) & (deg[None, :, None] > 0)
-            assert np.array_equal(np.where(unspecified, E, ra.numpy()), ca)
+    return rp, c, v, x
 
 
-@pytest.mark.skipif(not ref.available(), reason='oracle/_ref not built')
-def test_c_oracle_convert_matches_compiled_reference():
+def ref_spmm(r, reduce, rp, c, value, x):
+    """The compiled reference's spmm_<reduce> -> (out, arg or None) as numpy (bf16 as its bits)."""
+    if reduce == 'sum':
+        return tonp(r.spmm_sum(None, rp, c, value, None, None, x)), None
+    if reduce == 'mean':
+        return tonp(r.spmm_mean(None, rp, c, value, None, None, None, x)), None
+    ro, ra = (r.spmm_min if reduce == 'min' else r.spmm_max)(rp, c, value, x)
+    return tonp(ro), ra.numpy()
+
+
+def check_spmm_vs_reference(dtype, reduce, rp, c, value, x, ro, ra):
+    """C oracle on numpy inputs vs the reference's (out, arg)."""
+    E = c.size
+    co, ca = oc.spmm(CODE[dtype], reduce, rp, c, value, x)
+    assert np.array_equal(ro, co)  # bit-exact, narrow types included
+    if ra is not None:
+        # where no entry beat the reducer's init value (all candidates equal numeric_limits::max /
+        # lowest: e.g. an all-zero uint8 row under max) the reference leaves a stale index behind --
+        # unspecified; the oracle (and the HIP path) report E there
+        deg = rp[1:] - rp[:-1]
+        unspecified = (ca == E) & (deg[None, :, None] > 0)
+        assert np.array_equal(np.where(unspecified, E, ra), ca)
+
+
+@pytest.mark.parametrize('dtype', ALL_DTYPES)
+@pytest.mark.parametrize('reduce', ['sum', 'mean', 'min', 'max'])
+def test_c_oracle_matches_compiled_reference(dtype, reduce):
+    z = ref_cases('spmm')
+    key = 'spmm_%s_%s' % (dtype_name(dtype), reduce)
+    rp, c = z['spmm_rowptr'], z['spmm_col']
+    v, x = z['spmm_%s_value' % dtype_name(dtype)], z['spmm_%s_mat' % dtype_name(dtype)]
+    for value, tag in ((v, 'val'), (None, 'noval')):
+        ra = z['%s_%s_arg' % (key, tag)] if reduce in ('min', 'max') else None
+        check_spmm_vs_reference(dtype, reduce, rp, c, value, x, z['%s_%s_out' % (key, tag)], ra)
+    if not ref.available():
+        return
     r = ref.ops()
+    rp, c, v, x = spmm_case_inputs(dtype)
+    for value in (v, None):
+        ro, ra = ref_spmm(r, reduce, rp, c, value, x)
+        check_spmm_vs_reference(dtype, reduce, rp.numpy(), c.numpy(), tonp(value), tonp(x), ro, ra)
+
+
+def convert_case_inputs():
     g = torch.Generator().manual_seed(1)
     ind, _ = torch.sort(torch.randint(0, 300, (2000, ), generator=g))
+    return ind
+
+
+def test_c_oracle_convert_matches_compiled_reference():
+    z = ref_cases('convert')
+    assert np.array_equal(z['convert_ptr'], oc.ind2ptr(z['convert_ind'], 300))
+    assert np.array_equal(z['convert_ind_back'], oc.ptr2ind(z['convert_ptr'], 2000))
+    if not ref.available():
+        return
+    r = ref.ops()
+    ind = convert_case_inputs()
     ptr = r.ind2ptr(ind, 300)
     assert np.array_equal(ptr.numpy(), oc.ind2ptr(ind.numpy(), 300))
     assert np.array_equal(r.ptr2ind(ptr, 2000).numpy(), oc.ptr2ind(ptr.numpy(), 2000))
 
 
-@pytest.mark.skipif(not ref.available(), reason='oracle/_ref not built')
+def value_bw_case_inputs(dtype, scale=8):
+    """-> (row, rowptr, col, value, mat, grad_out) of test_c_oracle_value_bw_matches_compiled_reference."""
+    rp, c = synth.rmat_csr(scale, 6, seed=4)
+    E, n = c.numel(), 1 << scale
+    row = torch.from_numpy(oc.ptr2ind(rp.numpy(), E))
+    v = synth.values(E, dtype=dtype)
+    x = synth.features(n, 6, dtype=dtype, batch=(2, ))
+    gout = synth.features(n, 6, seed=3, dtype=dtype, batch=(2, ))
+    return row, rp, c, v, x, gout
+
+
+def ref_value_bw(r, reduce, row, rp, c, v, x, gout):
+    # the reference reaches spmm_value_bw only through autograd (csrc/spmm.cpp:96-98)
+    v = v.clone().requires_grad_()
+    if reduce == 'sum':
+        out = r.spmm_sum(row, rp, c, v, None, None, x)
+    else:
+        out = r.spmm_mean(row, rp, c, v, None, None, None, x)
+    out.backward(gout)
+    return tonp(v.grad)
+
+
 @pytest.mark.parametrize('reduce', ['sum', 'mean'])
 def test_c_oracle_value_bw_matches_compiled_reference(reduce):
-    # the reference reaches spmm_value_bw only through autograd (csrc/spmm.cpp:96-98)
-    r = ref.ops()
-    rp, c = synth.rmat_csr(8, 6, seed=4)
-    E, n = c.numel(), 256
-    row = torch.from_numpy(oc.ptr2ind(rp.numpy(), E))
+    z = ref_cases('value_bw')
     for dtype in (torch.float32, torch.float64):
-        v = synth.values(E, dtype=dtype).requires_grad_()
-        x = synth.features(n, 6, dtype=dtype, batch=(2, ))
-        gout = synth.features(n, 6, seed=3, dtype=dtype, batch=(2, ))
-        if reduce == 'sum':
-            out = r.spmm_sum(row, rp, c, v, None, None, x)
-        else:
-            out = r.spmm_mean(row, rp, c, v, None, None, None, x)
-        out.backward(gout)
+        key = 'value_bw_%s' % dtype_name(dtype)
+        got = oc.spmm_value_bw(CODE[dtype], reduce, z['value_bw_row'], z['value_bw_rowptr'], z['value_bw_col'],
+                               z[key + '_mat'], z[key + '_grad_out'])
+        assert np.array_equal(z['%s_%s_grad_value' % (key, reduce)], got)
+    if not ref.available():
+        return
+    r = ref.ops()
+    for dtype in (torch.float32, torch.float64):
+        row, rp, c, v, x, gout = value_bw_case_inputs(dtype)
+        want = ref_value_bw(r, reduce, row, rp, c, v, x, gout)
         got = oc.spmm_value_bw(CODE[dtype], reduce, row.numpy(), rp.numpy(), c.numpy(), tonp(x),
                                tonp(gout))
-        assert np.array_equal(tonp(v.grad), got)
+        assert np.array_equal(want, got)
 
 
 def test_golden_fixtures():
@@ -236,45 +302,83 @@ def test_np_oracle_matches_reference_sampler_fixtures():
     assert n_checked == 24
 
 
-@pytest.mark.skipif(not ref.available(), reason='oracle/_ref not built')
-@pytest.mark.parametrize('seed', [0, 1, 2])
-def test_np_oracle_matches_compiled_reference_samplers(seed):
-    """The same restatements against the reference's CPU kernels run live (oracle/_ref), on random
-    graphs with isolated nodes excluded from walks (the reference reads out of the row there)."""
-    from oracle import np_oracle as npo
-    r = ref.ops()
+def sampler_case_inputs(seed, small=False):
+    """Random graph (isolated nodes excluded from walks: the reference reads out of the row there) and the
+    arguments of test_np_oracle_matches_compiled_reference_samplers -> dict of numpy arrays (`small`: a graph of
+    60-80 nodes, 40 walks, 100 relabelled columns)."""
     rng = np.random.default_rng(seed)
-    n = 300 + 50 * seed
-    key = np.unique(np.concatenate([rng.integers(0, n * n, 4000), np.arange(n) * n + (np.arange(n) + 1) % n]))
+    n = (60 + 10 * seed) if small else (300 + 50 * seed)
+    key = np.unique(np.concatenate([rng.integers(0, n * n, 600 if small else 4000),
+                                    np.arange(n) * n + (np.arange(n) + 1) % n]))
     row, col = key // n, key % n
     rowptr = np.zeros(n + 1, np.int64)
     np.cumsum(np.bincount(row, minlength=n), out=rowptr[1:])
-    t = torch.from_numpy
     idx = rng.permutation(n)[:rng.integers(1, n)]
+    start = rng.integers(0, n, 40 if small else 77)
+    cols = col[rng.integers(0, col.size, 100 if small else 500)]
+    return dict(rowptr=rowptr, row=row, col=col, idx=idx, start=start, cols=cols)
 
-    torch.manual_seed(seed)
-    start = rng.integers(0, n, 77)
-    out = r.random_walk(t(rowptr), t(col), t(start), 12)
-    torch.manual_seed(seed)
-    rand = torch.rand((77, 12)).numpy()
-    np.testing.assert_array_equal(npo.random_walk(rowptr, col, start, rand), out.numpy())
 
-    want = r.sample_adj(t(rowptr), t(col), t(idx), -1, False)
-    for g, w in zip(npo.sample_adj_all(rowptr, col, idx), want):
-        np.testing.assert_array_equal(g, w.numpy())
-    want = r.saint_subgraph(t(idx), t(rowptr), t(row), t(col))
-    for g, w in zip(npo.saint_subgraph(idx, rowptr, col), want):
-        np.testing.assert_array_equal(g, w.numpy())
-    cols = col[rng.integers(0, col.size, 500)]
-    want = r.relabel(t(cols), t(idx))
-    for g, w in zip(npo.relabel(cols, idx), want):
-        np.testing.assert_array_equal(g, w.numpy())
+def ref_samplers(r, seed, a):
+    """The compiled reference's samplers on sampler_case_inputs(seed) -> dict of numpy outputs (random_walk together
+    with the floats it drew)."""
+    t = torch.from_numpy
+    res = {}
+    torch.manual_seed(seed)
+    res['rw_out'] = r.random_walk(t(a['rowptr']), t(a['col']), t(a['start']), 12).numpy()
+    torch.manual_seed(seed)
+    res['rw_rand'] = torch.rand((len(a['start']), 12)).numpy()
+    for i, w in enumerate(r.sample_adj(t(a['rowptr']), t(a['col']), t(a['idx']), -1, False)):
+        res['sample_adj_%d' % i] = w.numpy()
+    for i, w in enumerate(r.saint_subgraph(t(a['idx']), t(a['rowptr']), t(a['row']), t(a['col']))):
+        res['saint_%d' % i] = w.numpy()
+    for i, w in enumerate(r.relabel(t(a['cols']), t(a['idx']))):
+        res['relabel_%d' % i] = w.numpy()
     for bip in (False, True):
-        w_rp, w_c, _, w_idx = r.relabel_one_hop(t(rowptr), t(col), None, t(idx), bip)
+        w_rp, w_c, _, w_idx = r.relabel_one_hop(t(a['rowptr']), t(a['col']), None, t(a['idx']), bip)
+        res['relabel_one_hop_%d_rowptr' % bip] = w_rp.numpy()
+        res['relabel_one_hop_%d_col' % bip] = w_c.numpy()
+        res['relabel_one_hop_%d_idx' % bip] = w_idx.numpy()
+    return res
+
+
+def check_samplers_vs_reference(a, want):
+    from oracle import np_oracle as npo
+    rowptr, col, idx = a['rowptr'], a['col'], a['idx']
+    np.testing.assert_array_equal(npo.random_walk(rowptr, col, a['start'], want['rw_rand']), want['rw_out'])
+    got = npo.sample_adj_all(rowptr, col, idx)
+    assert all('sample_adj_%d' % i in want for i in range(len(got)))
+    for i, g in enumerate(got):
+        np.testing.assert_array_equal(g, want['sample_adj_%d' % i])
+    got = npo.saint_subgraph(idx, rowptr, col)
+    assert all('saint_%d' % i in want for i in range(len(got)))
+    for i, g in enumerate(got):
+        np.testing.assert_array_equal(g, want['saint_%d' % i])
+    got = npo.relabel(a['cols'], idx)
+    assert all('relabel_%d' % i in want for i in range(len(got)))
+    for i, g in enumerate(got):
+        np.testing.assert_array_equal(g, want['relabel_%d' % i])
+    for bip in (False, True):
         g_rp, g_c, _, g_idx = npo.relabel_one_hop(rowptr, col, idx, bip)
-        np.testing.assert_array_equal(g_rp, w_rp.numpy())
-        np.testing.assert_array_equal(g_c, w_c.numpy())
-        np.testing.assert_array_equal(g_idx, w_idx.numpy())
+        np.testing.assert_array_equal(g_rp, want['relabel_one_hop_%d_rowptr' % bip])
+        np.testing.assert_array_equal(g_c, want['relabel_one_hop_%d_col' % bip])
+        np.testing.assert_array_equal(g_idx, want['relabel_one_hop_%d_idx' % bip])
+
+
+@pytest.mark.parametrize('seed', [0, 1, 2])
+def test_np_oracle_matches_compiled_reference_samplers(seed):
+    """The same restatements against the reference's CPU kernels: their outputs recorded on random graphs
+    (tests/golden/ref_samplers.npz), and run live (oracle/_ref) when built."""
+    z = ref_cases('samplers')
+    pre = 'samplers_%d_' % seed
+    stored = {k[len(pre):]: z[k] for k in z.files if k.startswith(pre)}
+    a = {k[3:]: v for k, v in stored.items() if k.startswith('in_')}
+    assert set(a) == {'rowptr', 'row', 'col', 'idx', 'start', 'cols'}
+    check_samplers_vs_reference(a, {k: v for k, v in stored.items() if not k.startswith('in_')})
+    if not ref.available():
+        return
+    a = sampler_case_inputs(seed)
+    check_samplers_vs_reference(a, ref_samplers(ref.ops(), seed, a))
 
 
 def test_np_neighbor_sample_matches_fixtures_and_compiled_reference():
