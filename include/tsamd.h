@@ -59,10 +59,8 @@ typedef enum { TSAMD_SUM = 0, TSAMD_MEAN = 1, TSAMD_MIN = 2, TSAMD_MAX = 3 } tsa
 /* Library / runtime identification.  Replaces torch_sparse::cuda_version
  * (csrc/version.cpp:26-41): returns HIP_VERSION the library was built with. */
 int64_t tsamd_hip_version(void);
-/* Bit 0: the library was built with -DTSAMD_EXPERIMENTS=1 (scripts/variants.py): alternative / rejected kernel
- * variants are compiled in and TSAMD_* environment switches select them.  The shipped build returns 0: it reads no
- * environment variable on any call path and contains none of those variants.  (No reference counterpart:
- * csrc/version.cpp:26-41 only reports the toolkit version.) */
+/* Build flags of the library; always 0 (no flag is defined).  Kept for ABI stability.  (No reference
+ * counterpart: csrc/version.cpp:26-41 only reports the toolkit version.) */
 int tsamd_build_flags(void);
 /* Last hipError_t observed by this library on the calling thread. */
 int tsamd_last_hip_error(void);
@@ -262,8 +260,8 @@ int tsamd_spmm_value_bw(int dtype, int reduce, const int64_t *row,
  * grad_mat is accumulated with hardware atomics (it is a scatter into the transposed
  * pattern, which this op does not receive): fp32 / fp64 global_atomic_add; f16 / bf16
  * packed global_atomic_pk_add on the final buffer, i.e. one rounding per addition like the
- * reference's own narrow-type scatter_add_, in a non-deterministic order.  Odd K (or
- * TSAMD_MINMAX_BW_SHADOW=1) accumulates narrow types in an fp32 workspace instead and
+ * reference's own narrow-type scatter_add_, in a non-deterministic order.  Odd K
+ * accumulates narrow types in an fp32 workspace instead and
  * rounds once; tsamd_spmm_minmax_bw_workspace_bytes() says how much that takes (0
  * otherwise).
  * ------------------------------------------------------------------------ */

@@ -664,10 +664,6 @@ int sort_coalesce_impl(const int64_t *row, const int64_t *col, int64_t E, int64_
   } else {
     SortCoalesce co{row_u, col_u, seg_ptr, counts + 2, status};
     co.pre_zero_bytes = pre_zero;
-#if defined(TSAMD_EXP_COAL_SEPARATE_FILLS)  // A/B builds (scripts/variants.py): a fill per piece, as before
-    co.pre_zero_bytes = 0;
-    TSAMD_HIP_TRY(hipMemsetAsync(co_ws, 0, co_bytes, stream));
-#endif
     if (reduce >= 0) co.fused_out = counts + 3;
     co.no_seg = reduce >= 0 && value == nullptr;  // tsamd_sort_coalesce_reduce without a value: index only
     if (reduce >= 0 && value != nullptr && value_bytes == 4 && value_u != nullptr) {

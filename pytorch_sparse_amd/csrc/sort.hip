@@ -161,11 +161,7 @@ __global__ __launch_bounds__(kBuildThreads) void sort_build_kernel(
   // (the pass digits are histogrammed whether or not the passes will run: this kernel is bound by its 24 bytes per
   // entry, the counters cost nothing measurable, and a separate histogram kernel in front of the passes costs the
   // one-sweep chain 5 us when it does not run and a read of the words when it does)
-#if defined(TSAMD_EXP_BUILD_NO_PASS_HIST)  // timing experiment (scripts/variants.py): the one-sweep passes would be wrong
-  const int hist_passes = B.on ? 0 : L.passes;
-#else
   const int hist_passes = L.passes;
-#endif
   for (int p = 0; p < hist_passes; ++p)
     if (threadIdx.x < kRadix) cnt[p][threadIdx.x] = 0;
   if (B.on)
@@ -563,11 +559,7 @@ __global__ __launch_bounds__(kSortThreads) void onesweep_pass_kernel(
   }
   // ... then look back: the entries with my digit in the tiles before this one
   unsigned long long before = 0;
-#if defined(TSAMD_SORT_EXP_NOLOOKBACK)
-  if (false) {
-#else
   if (tile > 0) {
-#endif
     int64_t t = tile - 1;
     unsigned int spins = 0;
     bool done = false;
@@ -847,11 +839,7 @@ __global__ __launch_bounds__(kBkScatterThreads) void bucket_scatter_kernel(
         bid2[i] = bid;
       }
       if (LEVEL == 1 || bid != 0xffffffffu) {
-#if defined(TSAMD_EXP_SCATTER_NO_RANK)  // timing experiment
-        rank[i] = cnt[bk_slot(bid)];
-#else
         rank[i] = atomicAdd(&cnt[bk_slot(bid)], 1u);
-#endif
       }
     }
   }
@@ -889,11 +877,7 @@ __global__ __launch_bounds__(kBkScatterThreads) void bucket_scatter_kernel(
   for (int k = 0; k < kPer; ++k) {
     const unsigned int b = (unsigned int)(k * kBkScatterThreads + tid);
     const unsigned int cb = (int)b < nloc ? cnt[bk_slot(b)] : 0u;
-#if defined(TSAMD_EXP_SCATTER_NO_CURSOR)  // timing experiment (scripts/variants.py): wrong result
-    gbase[k] = cursor[gid0 + b];
-#else
     gbase[k] = cb ? atomicAdd(&cursor[gid0 + b], cb) : 0u;
-#endif
   }
   auto store_rec = [&](unsigned int o, unsigned long long wd, unsigned int v) {
     if constexpr (VAL) {
@@ -956,11 +940,7 @@ __global__ __launch_bounds__(kBkScatterThreads) void bucket_scatter_kernel(
       b = ((unsigned int)dlo << bits2) + (unsigned int)(wd >> B.shift);
     }
     const unsigned int o = cnt[bk_slot(b)] + (unsigned int)j;
-#if defined(TSAMD_EXP_SCATTER_LINEAR_STORE)  // timing experiment: the tile goes out as one contiguous piece
-    store_rec((unsigned int)(tile0 + j), wd ^ (unsigned long long)(o & 1u), VAL ? sval[j] : 0u);
-#else
     store_rec(o, wd, VAL ? sval[j] : 0u);
-#endif
   }
 }
 
@@ -1162,19 +1142,12 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
     }
   };
   const int p_top = SB.n - SB.n_top;  // the top digits are the last n_top passes of the list
-#if defined(TSAMD_EXP_BSORT_ONE_PASS)  // timing experiments: wrong result
-  lsd_passes(SB.n - 1, SB.n);
-#else
   lsd_passes(p_top, SB.n);
-#endif
   // FINISH.  Groups = runs of entries that agree in every bit from SB.lo up; an entry's final place is its place in
   // the run, taken while the output is written (no second trip through LDS).  First: is any group too long for that?
   // (sorted by prefix: a group longer than G exists exactly when some entry and the entry G places on agree)
   const int lo = SB.lo;
   bool exact = p_top == 0;
-#if defined(TSAMD_EXP_BSORT_NO_FINISH)
-  exact = true;
-#endif
   if (!exact) {
     int over = 0;
 #pragma unroll
@@ -1208,9 +1181,6 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
     static_assert(ITEMS * kW <= 128, "one wave scans the per-(step, wave) head counts, two per lane");
     const bool fuse = VAL && Co.reduce >= 0;
     // 1. the exact order in LDS (the finish step moves what it otherwise only re-addresses)
-#if defined(TSAMD_EXP_COAL_NO_EXACT)  // timing experiments (scripts/variants.py): wrong result
-    exact = true;
-#endif
     if (!exact) {
       unsigned long long fw[ITEMS];
       unsigned int fv[VAL ? ITEMS : 1];
@@ -1316,25 +1286,12 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
       // round trips, and eight times as many of them queue behind the stores of the other workgroups)
       // (also rejected: 64 words in the first round trip and kW x 64 in every later one of the same bucket -- the ripple
       // through the first ~512 buckets in 2 hops instead of 8 -- kernel 113.8 vs 112.3 us, coalesce 0.370 / 0.376 vs
-      // 0.369 / 0.361 ms: the chain is not what this kernel waits for either; -DTSAMD_EXP_COAL_WIDEN_LOOKBACK)
-#if defined(TSAMD_EXP_COAL_WIDE_LOOKBACK)
-      int lbw = kW;
-#else
-      int lbw = 1;
-#endif
-#if defined(TSAMD_EXP_COAL_WIDEN_LOOKBACK)
-      constexpr bool kWiden = true;
-#else
-      constexpr bool kWiden = false;
-#endif
+      // 0.369 / 0.361 ms: the chain is not what this kernel waits for either)
+      const int lbw = 1;
       __shared__ unsigned long long s_lb_sum[kW];
       __shared__ int s_lb_state[kW];  // 0: the wave's 64 buckets are all "own count"; 1: an inclusive prefix ends the sum here; 2: a bucket is not ready
       unsigned long long before = 0;
       int64_t t = bucket - 1;
-#if defined(TSAMD_EXP_COAL_NO_LOOKBACK)
-      t = -1;
-      before = start;
-#endif
       unsigned int spins = 0;
       while (t >= 0) {
         const int64_t mt = t - tid;
@@ -1371,7 +1328,6 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
         if (verdict == 0) {  // THREADS buckets of own counts: further back
           before += acc;
           t -= 64 * lbw;
-          if (kWiden) lbw = kW;
         } else {  // a bucket in the window has not published yet: read the window again
           if (++spins > kSpinLimit) {  // (see the pass kernel: the dispatch-order assumption does not hold here)
             __builtin_trap();
@@ -1399,11 +1355,7 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
     for (int k = 0; k < ITEMS; ++k) {
       const int j = k * THREADS + tid;
       if (k * THREADS >= n || j >= n) continue;
-#if defined(TSAMD_EXP_COAL_NO_HEAD_STORES)
-      if (((heads >> k) & 1u) && sword[j] == 0x123456789ull) {
-#else
       if ((heads >> k) & 1u) {
-#endif
         const unsigned long long wd = sword[j];
         const int64_t p = base + s_heads[k * kW + w] + (unsigned int)__popcll(s_hbits[k * kW + w] & lt_mask);
         const unsigned long long key = keybase | (wd >> L.idx_bits);
@@ -1483,13 +1435,9 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
       if (!ok[k]) continue;
-#if defined(TSAMD_EXP_BSORT_NO_STORE)
-      if (key[k] == 0x123456789ull) perm_out[o[k]] = (int64_t)e[k];
-#else
       if (row_out) row_out[o[k]] = (int64_t)(key[k] >> L.col_bits);
       if (col_out) col_out[o[k]] = (int64_t)(key[k] & cmask);
       if (perm_out) perm_out[o[k]] = (int64_t)e[k];
-#endif
     }
   }
 }

@@ -86,12 +86,6 @@ constexpr bool kPartial = TSAMD_SPMM_PARTIAL_BUILD != 0;
 #ifndef TSAMD_MINMAX_UNROLL
 #define TSAMD_MINMAX_UNROLL 2
 #endif
-#ifndef TSAMD_MASKED_SEGMENT_SKIP
-#define TSAMD_MASKED_SEGMENT_SKIP 1  // 0: the masked sum gathers every entry's whole row (round 3), for A/B builds
-#endif
-#ifndef TSAMD_MINMAX_SPLIT_LOOP
-#define TSAMD_MINMAX_SPLIT_LOOP 1  // 0: the round-3 loop (value-mode branch inside the step loop), kept for A/B builds
-#endif
 constexpr int kUnroll = TSAMD_UNROLL;      // gathers in flight per group
 constexpr int kMinMaxUnroll = TSAMD_MINMAX_UNROLL;  // min / max carry (value, arg) per element: fewer
 constexpr int kWavesPerBlock = TSAMD_WPB;  // 256-thread workgroups
@@ -173,7 +167,7 @@ struct Workspace {
 //    with its rows at hashed positions and the gather uses the hashed ids.  The hash is a
 //    bijection on [0, N): multiply by an odd constant and fold the high half into the low half
 //    on ceil(log2 N) bits, cycle-walking until the value is < N.  Sums are bit-identical with
-//    and without it (only addresses change).  TSAMD_SPMM_RELABEL=0|1 forces it off|on.
+//    and without it (only addresses change).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t hash_row(uint32_t c, uint32_t N, uint32_t bits, uint32_t mul,
                                              uint32_t shift) {
@@ -201,9 +195,6 @@ __device__ __forceinline__ bool use_relabel(int mode, const int *f) {
 constexpr int kProbeBlocks = 64;
 #ifndef TSAMD_PERMUTE_BLOCKS
 #define TSAMD_PERMUTE_BLOCKS 8192
-#endif
-#ifndef TSAMD_PERMUTE_NT
-#define TSAMD_PERMUTE_NT 1
 #endif
 
 // Fingerprint of a dense operand for the operand cache: 64 x 256 sixteen-byte packets spread evenly over
@@ -272,19 +263,11 @@ __global__ __launch_bounds__(256) void spmm_permute_rows_kernel(const T *__restr
     for (uint32_t sl = sl0; sl < slots; sl += lanes) {
       // the source is streamed once: a non-temporal load keeps it from evicting lines of the copy that the merge
       // kernel is about to gather (same-box A/B, north star: copy + probe + partition 0.44 -> 0.40-0.42 ms;
-      // a non-temporal store on top changed nothing; TSAMD_PERMUTE_NT=0 restores plain loads)
-#if TSAMD_PERMUTE_NT
+      // a non-temporal store on top changed nothing)
       typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
       static_assert(sizeof(P) == 16, "16-byte packets");
       const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + sl));
-#if TSAMD_PERMUTE_NT >= 2
-      __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(dst + sl));
-#else
       *reinterpret_cast<u32x4 *>(dst + sl) = v;
-#endif
-#else
-      dst[sl] = src[sl];
-#endif
     }
   }
 }
@@ -399,7 +382,6 @@ __device__ __forceinline__ void accumulate_window(
   constexpr int kU = RED == RED_ADD ? kUnroll : kMinMaxUnroll;
   const int n = hi - lo;
   const int nsteps = (n + (1 << lgG) - 1) >> lgG;
-#if TSAMD_MINMAX_SPLIT_LOOP
   if constexpr (RED != RED_ADD) {
     // min / max: one step loop PER value mode (the wave-uniform `has_value` test sits outside the loop).  The
     // 2-byte instantiations are bound by VALU issue (SQ counters, round 3: ~80 % of the slots at config 3); with the
@@ -447,7 +429,6 @@ __device__ __forceinline__ void accumulate_window(
     else run(std::false_type{});
     return;
   }
-#endif
   for (int s = 0; s < nsteps; s += kU) {
     P x[kU];
     A w[kU];
@@ -458,23 +439,16 @@ __device__ __forceinline__ void accumulate_window(
     for (int u = 0; u < kU; ++u) {
       idx[u] = lo + ((s + u) << lgG) + g;
       const int src = idx[u] < hi ? idx[u] : hi - 1;
-      if constexpr (RED != RED_ADD) idx[u] = src;  // see below: min / max need no mask
       const uint32_t c = lane_read(c_l, src);
       w[u] = lane_read(w_l, src);
       if constexpr (MASKED) {
-#if TSAMD_MASKED_SEGMENT_SKIP
         cm[u] = c;
         em[u] = lane_read(e_l, src);
         on[u] = (lane_read(z_l, src) >> mask_seg) & 1u;
-#else
-        x[u] = *reinterpret_cast<const P *>(matk + (uint64_t)c * K);
-        mb[u] = maskk[(uint64_t)lane_read(e_l, src) * mask_words];
-#endif
       } else {
         x[u] = *reinterpret_cast<const P *>(matk + (uint64_t)c * K);
       }
     }
-#if TSAMD_MASKED_SEGMENT_SKIP
     if constexpr (MASKED) {
       // winners are sparse in the entries of long rows (an entry of a row of degree d wins a feature with
       // probability ~1/d): the record says which of the row's 32-feature segments have one at all, and only
@@ -494,7 +468,6 @@ __device__ __forceinline__ void accumulate_window(
         }
       }
     }
-#endif
     if constexpr (RED == RED_ADD && MASKED) {
       // the masked sum is bound by instruction issue as much as by its gathers (twice the instructions of the
       // plain sum per row): the packet's predicate bits become all-ones / all-zero words (v_bfe_i32) that are
@@ -502,10 +475,8 @@ __device__ __forceinline__ void accumulate_window(
       auto add_masked = [&](auto with_value) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-#if TSAMD_MASKED_SEGMENT_SKIP
           // no lane of the wave gathered anything for this slot (hub-row entries mostly win nothing): nothing to add
           if (__ballot(on[u] != 0u) == 0ull) continue;  // wave-uniform
-#endif
           const uint32_t bits = idx[u] < hi ? (mb[u] >> mask_shift) : 0u;
 #pragma unroll
           for (int j = 0; j < VEC; ++j) {
@@ -535,46 +506,14 @@ __device__ __forceinline__ void accumulate_window(
       else add_masked(std::false_type{});
       continue;
     }
-    if constexpr (RED != RED_ADD) {
-      // Slots past `hi` re-read the row's last entry: min / max are idempotent, the duplicate carries the same
-      // (value, edge id) as the original, so nothing has to be masked (strict compares: an equal candidate with
-      // a larger or equal id never replaces).  Without values the candidate is the stored element itself: no
-      // product, no rounding -- as a wave-uniform branch, not a select: the 2-byte instantiations are bound by
-      // VALU issue (84 % of the pipe at config 3, SQ counters), and `has_value ? round(w * x) : x` per element
-      // was a third of their instructions.
-      auto fold = [&](auto with_value) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) {
-            const A xv = Traits<T>::to_acc(x[u].v[j]);
-            A p = xv;
-            if constexpr (decltype(with_value)::value) p = Traits<T>::round_acc(w[u] * xv);
-            const bool better = RED == RED_MIN ? (p < val[j]) : (p > val[j]);
-            val[j] = better ? p : val[j];
-#if !defined(TSAMD_EXP_NO_ARG_TRACK)
-            arg[j] = better ? wrel + (uint32_t)idx[u] : arg[j];
-#endif
-          }
-        }
-      };
-      if (has_value) fold(std::true_type{});  // wave-uniform
-      else fold(std::false_type{});
-      continue;
-    }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       const bool ok = idx[u] < hi;
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const A xv = Traits<T>::to_acc(x[u].v[j]);
-        if constexpr (RED == RED_ADD && MASKED) {
-          const A p = Traits<T>::round_acc(w[u] * xv);
-          val[j] += (ok && ((mb[u] >> (mask_shift + (uint32_t)j)) & 1u)) ? p : A(0);
-        } else {
-          const A p = w[u] * xv;
-          val[j] += ok ? p : A(0);
-        }
+        const A p = w[u] * xv;
+        val[j] += ok ? p : A(0);
       }
     }
   }
@@ -704,7 +643,6 @@ __device__ __forceinline__ void write_row(T *__restrict__ out_base, int64_t *__r
       asm volatile("" : "+v"(val[j]));  // keep the mean / non-mean paths from splitting the 16-byte store
       o.v[j] = Traits<T>::from_acc(val[j]);
     }
-#if !defined(TSAMD_NO_NT_STORE)
     // output rows are written once and never re-read by this kernel: a non-temporal store keeps
     // them from evicting gathered rows of `mat` from L2 (+1.5-2 % measured)
     if constexpr (sizeof(Pack<T, VEC>) == 16) {
@@ -713,9 +651,6 @@ __device__ __forceinline__ void write_row(T *__restrict__ out_base, int64_t *__r
     } else {
       *reinterpret_cast<Pack<T, VEC> *>(outk) = o;
     }
-#else
-    *reinterpret_cast<Pack<T, VEC> *>(outk) = o;
-#endif
   } else {
     Pack<int64_t, VEC> a;
 #pragma unroll
@@ -732,10 +667,7 @@ __device__ __forceinline__ void write_row(T *__restrict__ out_base, int64_t *__r
     }
     // written once, never re-read here: keep them out of L2 (1.3 GB of arg ids at config-3 size
     // would otherwise evict the gathered rows of `mat`)
-#if !defined(TSAMD_EXP_NO_OUT_STORE)
     nt_store(outk, o);
-#endif
-#if !defined(TSAMD_EXP_NO_ARG_STORE)
     if constexpr (!STORE_ARG) {  // the caller keeps the winners in another form (Workspace::rec_out)
     } else if constexpr (a32) {
       Pack<int32_t, VEC> an;
@@ -745,9 +677,6 @@ __device__ __forceinline__ void write_row(T *__restrict__ out_base, int64_t *__r
     } else {
       nt_store(argk, a);
     }
-#else
-    asm volatile("" ::"v"(a.v[0]), "v"(a.v[VEC - 1]));
-#endif
   }
 }
 
@@ -1584,10 +1513,6 @@ void plan_partition(int64_t M, int64_t E, int64_t row_bytes, int64_t *P, int64_t
   const int64_t total = M + E > 0 ? M + E : 1;
   int64_t cap = row_bytes <= 512 ? 256 : (row_bytes < 1024 ? 512 : 1024);
   if (row_bytes <= 128) cap = kShortRowItems;  // side-by-side short rows: long partitions amortise the batches
-  if (const char *env = exp_env("TSAMD_SPMM_ITEMS")) {  // experiments
-    const long v = atol(env);
-    if (v >= 64 && v <= 4096) cap = v;
-  }
   if (cap > TSAMD_ITEMS_MAX) cap = TSAMD_ITEMS_MAX;
   int64_t it = ceil_div(total, (int64_t)TSAMD_TARGET_WAVES);
   if (it < TSAMD_ITEMS_MIN) it = TSAMD_ITEMS_MIN;
@@ -1604,16 +1529,12 @@ void plan_partition(int64_t M, int64_t E, int64_t row_bytes, int64_t *P, int64_t
 // Only rows whose byte size is a power of two (>= 128 B) camp on memory channels: with hub ids
 // that are multiples of big powers of two, `id * pitch` keeps its low address bits zero only if the
 // pitch is a power of two itself.  Same-box A/B on the north-star graph (scripts/bench_fsweep.py,
-// TSAMD_SPMM_RELABEL=0/1): F = 32 / 64 / 128 / 256 fp32 gain 8 / 10 / 26 / 30 % from the copy,
+// relabel forced off / on): F = 32 / 64 / 128 / 256 fp32 gain 8 / 10 / 26 / 30 % from the copy,
 // F = 24 / 40 / 48 / 80 / 96 / 112 / 160 / 192 LOSE 13-25 % (they spread by themselves and only pay
-// for the copy and the hashing), 64-byte rows lose 2-10 %.  TSAMD_SPMM_RELABEL=1 still forces it.
-bool relabel_forced() {
-  const char *env = exp_env("TSAMD_SPMM_RELABEL");
-  return env != nullptr && env[0] == '1';
-}
+// for the copy and the hashing), 64-byte rows lose 2-10 %.
 
 // Round 3 same-box A/B over reduction x element type x row size on the scale-20 / 21 R-MAT graphs
-// (scripts/ab_relabel.py, profiles/r03_ab_relabel.jsonl): the copy LOSES 3-11 % for min / max on f16 / bf16
+// (profiles/r03_ab_relabel.jsonl): the copy LOSES 3-11 % for min / max on f16 / bf16
 // at every row size (those kernels are bound by instruction issue, not by the camped channels, and pay
 // the copy and the per-entry hashing on top) and 15 % for fp32 min / max on 128-byte rows; 128-byte rows
 // of sums are a wash (-5 ... +5 %).  It stays for sums on power-of-two rows >= 256 bytes (3-23 % gain)
@@ -1624,7 +1545,7 @@ bool relabel_possible(int dtype, int reduce, int64_t N, int64_t K, int64_t E) {
                        row_bytes % 16 == 0;
   const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
   const bool camps = row_bytes >= 256 && (row_bytes & (row_bytes - 1)) == 0 && !(minmax && dtype_size(dtype) < 4);
-  return size_ok && (camps || relabel_forced());
+  return size_ok && camps;
 }
 
 size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K,
@@ -1651,10 +1572,6 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   w.tail_arg = reinterpret_cast<uint32_t *>(minmax ? take(sizeof(uint32_t) * plane) : nullptr);
   w.relabel_mode = 0;
   w.relabel_flag = reinterpret_cast<int *>(take(256));
-  if (const char *env = exp_env("TSAMD_SPMM_XPERM_PAD")) {  // experiments: shift the copy of X
-    const long v = atol(env);
-    if (v > 0 && v <= (64l << 20)) (void)take((size_t)v);
-  }
   w.xperm = (!relabelled && relabel_possible(dtype, reduce, N, K, E)) ? take(dtype_size(dtype) * (size_t)B * N * K) : nullptr;
   // (carved behind the copy of X: the position of that copy relative to the start of the workspace decides which
   // of its hot rows share a memory channel -- 3-5 % of the north-star kernel either way, measured by padding --
@@ -1706,11 +1623,7 @@ int launch_spmm(const int64_t *rowptr, const int64_t *col, const T *value, const
 
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[0], stream));
   {
-    int mode = 0;
-    if (ws.xperm != nullptr && VEC > 1 && !ws.out_relabel) {
-      const char *env = exp_env("TSAMD_SPMM_RELABEL");
-      mode = env ? (env[0] == '1' ? 1 : (env[0] == '0' ? 0 : 2)) : 2;
-    }
+    int mode = ws.xperm != nullptr && VEC > 1 && !ws.out_relabel ? 2 : 0;
     // masked sums (the pull of the min / max backward): `col` points at winner records, not at column ids, so there
     // is nothing to probe; same-box A/B at configs[2]: 1.76 ms with the copy, 1.93 without (the rows gathered are
     // grad_out rows indexed by the R-MAT ROW ids of the forward, which camp like its column ids)

@@ -12,10 +12,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef TSAMD_MASKED_SEGMENT_SKIP
-#define TSAMD_MASKED_SEGMENT_SKIP 1  // 0: the masked SDDMM / masked sum gather every entry's whole rows (round 3)
-#endif
-
 namespace tsamd {
 namespace {
 
@@ -38,10 +34,7 @@ constexpr int kUnroll = 2;
 // that did not win must not contribute at all: 0 * Inf would be a NaN) and gfx950's v_dot2c_f32_{bf16,f16} takes the
 // pair -- conversion, two multiplies and two adds in one instruction.  24 VALU instructions per packet instead of
 // ~45 (two conversions + select + FMA per element): the masked SDDMM ran at 0.94 of the VALU slots
-// (profiles/r04_sq_counters.md).  -DTSAMD_MASKED_DOT2=0 keeps the per-element form.
-#ifndef TSAMD_MASKED_DOT2
-#define TSAMD_MASKED_DOT2 1
-#endif
+// (profiles/r04_sq_counters.md).
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ float masked_dot8(const u32x4_t &x, const u32x4_t &y, uint32_t bits, float acc) {
@@ -129,7 +122,6 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_value_bw_kernel(
         const T *mrow = mat + ((uint64_t)b * N + c) * K;
         const T *grow = grad + ((uint64_t)b * M + r) * K;
         for (uint32_t sl = kl; sl < slots; sl += lpr) {
-#if TSAMD_MASKED_SEGMENT_SKIP
           if constexpr (MASKED) {
             // The record word first: an entry of a row of degree d wins a feature with probability ~1/d, and the
             // entries of a hub row are consecutive in this kernel's (CSR) order -- most slots of most steps hold no
@@ -151,13 +143,13 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_value_bw_kernel(
               u32x4 xb, yb;
               __builtin_memcpy(&xb, &x, 16);
               __builtin_memcpy(&yb, &y, 16);
+              // keep the two 16-byte loads whole (without the barrier they sink into the per-element selects as
+              // 2-byte loads: 1.8 ms instead of 0.7 ms)
               asm volatile("" : "+v"(xb), "+v"(yb));
-#if TSAMD_MASKED_DOT2
               if constexpr (sizeof(T) == 2 && VEC == 8 && std::is_same<A, float>::value) {
                 acc[u] = masked_dot8<T>(xb, yb, bits, acc[u]);
                 continue;
               }
-#endif
               __builtin_memcpy(&x, &xb, 16);
               __builtin_memcpy(&y, &yb, 16);
             }
@@ -166,33 +158,11 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_value_bw_kernel(
               acc[u] += ((bits >> j) & 1u) ? Traits<T>::to_acc(x.v[j]) * Traits<T>::to_acc(y.v[j]) : A(0);
             continue;
           }
-#endif
           P x = *reinterpret_cast<const P *>(mrow + (uint64_t)sl * VEC);
           P y = *reinterpret_cast<const P *>(grow + (uint64_t)sl * VEC);
-          if constexpr (MASKED) {
-            // keep the two 16-byte loads whole: without the barrier the compiler sinks them into the
-            // per-element selects below as 2-byte loads (measured 1.8 ms instead of 0.7 ms)
-            {
-              typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-              static_assert(sizeof(P) == 16, "masked SDDMM works on 16-byte packets");
-              u32x4 xb, yb;
-              __builtin_memcpy(&xb, &x, 16);
-              __builtin_memcpy(&yb, &y, 16);
-              asm volatile("" : "+v"(xb), "+v"(yb));
-              __builtin_memcpy(&x, &xb, 16);
-              __builtin_memcpy(&y, &yb, 16);
-            }
-            // VEC divides 32: the packet's bits sit in one word of the record
-            const uint32_t f0 = sl * VEC;
-            const uint32_t bits = rec[((uint64_t)b * (uint64_t)E + (uint64_t)(base + src)) * rec_stride + (f0 >> 5)] >> (f0 & 31u);
 #pragma unroll
-            for (int j = 0; j < VEC; ++j)
-              acc[u] += ((bits >> j) & 1u) ? Traits<T>::to_acc(x.v[j]) * Traits<T>::to_acc(y.v[j]) : A(0);
-          } else {
-#pragma unroll
-            for (int j = 0; j < VEC; ++j)
-              acc[u] += Traits<T>::to_acc(x.v[j]) * Traits<T>::to_acc(y.v[j]);
-          }
+          for (int j = 0; j < VEC; ++j)
+            acc[u] += Traits<T>::to_acc(x.v[j]) * Traits<T>::to_acc(y.v[j]);
         }
       }
     }
@@ -361,8 +331,8 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_value_bw_masked_ke
 //     narrowing pass): the lane adds its value in its half of the aligned 4-byte word and +0 in
 //     the other half; when both halves of a word go to the same entry the even lane adds both.
 //     This is the reference's own arithmetic class (its scatter_add_ accumulates in the narrow
-//     type, one rounding per add) in a non-deterministic order.  TSAMD_MINMAX_BW_SHADOW=1 (and
-//     buffers that are not 4-byte aligned) use the fp32 shadow, rounded once;
+//     type, one rounding per add) in a non-deterministic order.  Buffers that are not 4-byte
+//     aligned or have an odd element count use the fp32 shadow, rounded once;
 //   * kBwRows rows x 2 feature tiles are in flight per wave so that the dependent chain
 //     arg -> col[arg] -> atomic is overlapped; every row has exactly K elements, so the work is
 //     balanced whatever the degrees are.
@@ -576,9 +546,6 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_minmax_bw_kernel(
 // global atomics.  A winner is only trusted to lie inside the chunk (LDS bounds); a foreign arg_out
 // gives a wrong mask, never a wild store.
 // ---------------------------------------------------------------------------
-#ifndef TSAMD_WINREC_LINE_STORES
-#define TSAMD_WINREC_LINE_STORES 1
-#endif
 #ifndef TSAMD_WINREC_ROWS
 #define TSAMD_WINREC_ROWS 2
 #endif
@@ -598,7 +565,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void minmax_winrec_kernel(
   const int64_t e0 = ((int64_t)blockIdx.x * kWavesPerBlock + wib) * kWave;
   if (e0 >= E) return;
   const int n = (int)(E - e0 < kWave ? E - e0 : kWave);
-  const bool whole32 = TSAMD_WINREC_LINE_STORES && W == 4u && S == 8u && n == kWave;  // wave-uniform
+  const bool whole32 = W == 4u && S == 8u && n == kWave;  // wave-uniform
   const uint32_t ntiles = (K + 63u) >> 6;
   const bool mine = lane < n;
   const uint32_t m_l = mine ? (uint32_t)row[e0 + lane] : 0xFFFFFFFFu;
@@ -747,9 +714,7 @@ int launch_value_bw_masked(const int64_t *row, const int64_t *rowptr, const int6
   const uint32_t lpr = slots >= 64 ? 64u : (1u << ilog2_ceil(slots));
   const int lgG = 6 - ilog2_ceil(lpr);
   const unsigned int blocks = (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock);
-  const char *env_pipe = exp_env("TSAMD_MASKED_SDDMM_PIPE");  // experiments: 0 = the round-4 kernel
-  const bool pipelined = !(env_pipe != nullptr && env_pipe[0] == '0');
-  if (pipelined && slots <= 64u && K % VEC == 0 && (uint64_t)kWave * rec_stride < (1ull << 32)) {
+  if (slots <= 64u && K % VEC == 0 && (uint64_t)kWave * rec_stride < (1ull << 32)) {
     hipLaunchKernelGGL((spmm_value_bw_masked_kernel<T>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream, row,
                        rowptr, col, mat, grad, out, B, M, N, (uint32_t)K, E, lgG, rec, rec_stride);
   } else {
@@ -838,21 +803,14 @@ extern "C" int tsamd_spmm_value_bw(int dtype, int reduce, const int64_t *row,
   });
 }
 
-// f16 / bf16 grad_mat: packed atomics on the final buffer unless TSAMD_MINMAX_BW_SHADOW=1 asks for
-// the fp32 shadow (round once; costs a memset, fp32 atomics on twice as many 64-byte segments and a
-// narrowing pass over [B,N,K]).
-static bool minmax_bw_shadow(int dtype) {
-  if (dtype != TSAMD_F16 && dtype != TSAMD_BF16) return false;
-  const char *env = exp_env("TSAMD_MINMAX_BW_SHADOW");
-  return env != nullptr && env[0] == '1';
-}
-
+// f16 / bf16 grad_mat: packed atomics on the final buffer where they can work; the fp32 shadow otherwise
+// (round once; costs a memset, fp32 atomics on twice as many 64-byte segments and a narrowing pass over [B,N,K]).
 extern "C" size_t tsamd_spmm_minmax_bw_workspace_bytes(int dtype, int64_t B, int64_t N, int64_t K,
                                                        int64_t E) {
   (void)E;
   const bool narrow = dtype == TSAMD_F16 || dtype == TSAMD_BF16;
   // packed atomics need whole 4-byte words inside the buffer: an odd element count takes the shadow
-  if (minmax_bw_shadow(dtype) || (narrow && ((B * N * K) % 2) != 0))
+  if (narrow && ((B * N * K) % 2) != 0)
     return align_up(sizeof(float) * (size_t)(B * N * K), 256);
   return 0;
 }
@@ -889,9 +847,8 @@ extern "C" int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int6
   const size_t es = dtype_size(dtype);
   const size_t nmat = (size_t)(B * N * K);
   const bool narrow = dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-  bool shadow = narrow && grad_mat && minmax_bw_shadow(dtype);
   // packed atomics work on aligned 4-byte words inside the buffer
-  if (narrow && grad_mat && !shadow && (((uintptr_t)grad_mat % 4) != 0 || (nmat % 2) != 0)) shadow = true;
+  const bool shadow = narrow && grad_mat && (((uintptr_t)grad_mat % 4) != 0 || (nmat % 2) != 0);
   float *shadow_mat = nullptr;
   if (shadow) {
     const size_t need = align_up(sizeof(float) * nmat, 256);
@@ -928,34 +885,13 @@ static size_t winrec_bytes(int64_t B, int64_t K, int64_t E) {
   return align_up(sizeof(uint32_t) * (size_t)(B * E) * win_record_stride(K), 256);
 }
 
-// grad_mat route of the pull: winner bit masks + the masked merge-path SpMM (default), or -- TSAMD_MINMAX_BW_LISTS=1,
-// K <= 1024 -- compacted winner lists (csrc/spmm_bw_list.hip).  Same-box A/B on the 2^20 R-MAT graph
-// (profiles/r04_minmax_bw_routes.md): the lists move a third of the bytes but issue ~26 instructions per entry and
-// one LDS add per (row, feature) and end up instruction-bound: 2.08 vs 1.78 ms at configs[2] (bf16, F = 128), ahead
-// only for bf16 F = 64 (1.58 vs 1.75) and fp32 F = 256 (4.30 vs 4.43).  Kept as an option, bit-identical results
-// for value-less narrow types, tests/test_spmm_gpu.py runs both.
-static bool use_lists(int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E) {
-#if defined(TSAMD_EXPERIMENTS)
-  const char *env = exp_env("TSAMD_MINMAX_BW_LISTS");
-  if (env == nullptr || env[0] != '1') return false;
-  return minmax_bw_lists_supported(dtype, B, M, N, K, E);
-#else
-  (void)dtype; (void)B; (void)M; (void)N; (void)K; (void)E;
-  return false;  // (csrc/spmm_bw_list.hip is only compiled into experiment builds)
-#endif
-}
-
+// grad_mat route of the pull: winner bit masks + the masked merge-path SpMM.  Compacted winner lists per entry were
+// measured slower (instruction-bound: 2.08 vs 1.78 ms at configs[2], profiles/r04_minmax_bw_routes.md).
 extern "C" size_t tsamd_spmm_minmax_bw_csc_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N,
                                                            int64_t K, int64_t E) {
   if (dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
   // the masked sum runs on the transposed matrix: N rows, M columns
-  const size_t masked = winrec_bytes(B, K, E) + spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
-#if defined(TSAMD_EXPERIMENTS)
-  const size_t lists = minmax_bw_lists_supported(dtype, B, M, N, K, E) ? minmax_bw_lists_workspace_bytes(dtype, B, M, N, K, E) : 0;
-#else
-  const size_t lists = 0;
-#endif
-  return masked > lists ? masked : lists;
+  return winrec_bytes(B, K, E) + spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
 }
 
 // arg32: arg_any holds int32 ids (tsamd_spmm_minmax_arg32); only the record route reads them in that width
@@ -983,21 +919,6 @@ static int minmax_bw_csc_impl(int dtype, const int64_t *rowptr, const int64_t *c
   if (total > 0 && (!rowptr || !col || !mat || !grad_out || !arg_out)) return TSAMD_ERR_INVALID;
   if (grad_mat && E > 0 && (!colptr || !csr2csc || !row)) return TSAMD_ERR_INVALID;
   const size_t es = dtype_size(dtype);
-#if defined(TSAMD_EXPERIMENTS)
-  if (grad_mat && total > 0 && E > 0 && B * N * K > 0 && use_lists(dtype, B, M, N, K, E)) {
-    if (arg32) return TSAMD_ERR_UNSUPPORTED;  // the (opt-in) list route reads int64 ids: the caller widens them
-    if (!workspace || workspace_bytes < minmax_bw_lists_workspace_bytes(dtype, B, M, N, K, E) ||
-        (uintptr_t)workspace % 256 != 0)
-      return TSAMD_ERR_WORKSPACE;
-    if (grad_value) {  // the row-parallel kernel (per-row LDS slots, plain stores)
-      int st = tsamd_spmm_minmax_bw(dtype, rowptr, col, value, mat, grad_out, arg_out, grad_value, nullptr, B, M, N,
-                                    K, E, nullptr, 0, stream_);
-      if (st != TSAMD_OK) return st;
-    }
-    return minmax_bw_lists(dtype, row, col, value, grad_out, arg_out, colptr, csr2csc, grad_mat, B, M, N, K, E,
-                           workspace, stream);
-  }
-#endif
   // grad_value as a masked SDDMM over the records needs 16-byte packets; else the row-parallel LDS kernel
   const bool sddmm_ok = grad_value && row && (K * (int64_t)es) % 16 == 0 && ((uintptr_t)mat % 16) == 0 &&
                         ((uintptr_t)grad_out % 16) == 0;

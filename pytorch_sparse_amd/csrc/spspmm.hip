@@ -293,10 +293,6 @@ __device__ inline void wave_radix_sort_lds(uint32_t *&ka, A *&va, uint32_t *&kb,
 // ---------------------------------------------------------------------------
 constexpr int kExpandBatch = 4;
 
-#ifndef TSAMD_SPSPMM_OWNER_SCAN
-#define TSAMD_SPSPMM_OWNER_SCAN 1  // 0: the one-wave kernels locate a product's A entry by the 6-step search (round 1-3), for A/B builds
-#endif
-
 template <typename A>
 struct ExpandScratch {
   int off[65];
@@ -356,33 +352,22 @@ __device__ __forceinline__ EachProduct<Emit> each_product(Emit emit) {
   return EachProduct<Emit>{emit};
 }
 
-// PRE: the caller already holds the per-lane (start of the B row, its length, value of the A entry) of a row of at
-// most 64 entries -- the persistent kernels below fetch them a row ahead (RowPipe).
-template <typename T, bool WITH_VAL, bool PRE = false, typename Emit>
+template <typename T, bool WITH_VAL, typename Emit>
 __device__ __forceinline__ int expand_row_wave(const int64_t *__restrict__ colA, const T *__restrict__ valA,
                                                const int64_t *__restrict__ rowptrB,
                                                const uint32_t *__restrict__ colB, const T *__restrict__ valB,
                                                int64_t as, int64_t ae,
-                                               ExpandScratch<typename Traits<T>::acc_t> &sc, Emit emit,
-                                               int64_t pre_bs = 0, int pre_d = 0,
-                                               typename Traits<T>::acc_t pre_av = typename Traits<T>::acc_t(1)) {
+                                               ExpandScratch<typename Traits<T>::acc_t> &sc, Emit emit) {
   using A = typename Traits<T>::acc_t;
   const int lane = (int)threadIdx.x;
   uint32_t *own_w = reinterpret_cast<uint32_t *>(sc.own);
   int filled = 0;
-  // PRE: exactly one chunk (the caller sends rows of more than 64 entries through the loading form): no load of
-  // this function then sits in a loop around the gathers, where the compiler's wait-count bookkeeping would make
-  // the gathers wait for the caller's prefetches first
-  for (int64_t e0 = as; e0 < (PRE ? (as < ae ? as + 1 : as) : ae); e0 += 64) {
+  for (int64_t e0 = as; e0 < ae; e0 += 64) {
     const int64_t e = e0 + lane;
     int64_t bs = 0;
     int d = 0;
     A av = A(1);
-    if constexpr (PRE) {
-      bs = pre_bs;
-      d = pre_d;
-      av = pre_av;
-    } else if (e < ae) {
+    if (e < ae) {
       const int64_t c = colA[e];
       bs = rowptrB[c];
       d = (int)(rowptrB[c + 1] - bs);
@@ -461,10 +446,8 @@ __device__ __forceinline__ int expand_row(const int64_t *__restrict__ colA, cons
                                           int64_t as, int64_t ae,
                                           ExpandScratch<typename Traits<T>::acc_t> &sc, Emit emit) {
   using A = typename Traits<T>::acc_t;
-#if TSAMD_SPSPMM_OWNER_SCAN
   if constexpr (BLOCK == 64 && !LONG_B)
     return expand_row_wave<T, WITH_VAL>(colA, valA, rowptrB, colB, valB, as, ae, sc, each_product(emit));
-#endif
   const int tid = (int)threadIdx.x;
   const int lane = tid & 63;
   int filled = 0;
@@ -497,9 +480,6 @@ __device__ __forceinline__ int expand_row(const int64_t *__restrict__ colA, cons
     // row, its value): a hit costs no LDS access at all -- the hist / bin kernels of the large rows are bound by the
     // CU's LDS pipe (occupancy 4 -> 8 moved them by 5-18 %, more loads in flight by nothing), and the round-4 form
     // read five LDS words per product even on a hit.
-#ifndef TSAMD_SPSPMM_REG_ENTRY
-#define TSAMD_SPSPMM_REG_ENTRY 1
-#endif
     int c_off = 0, c_end = 0;  // [c_off, c_end): products of the cached entry (empty: nothing cached for this chunk)
     int64_t c_bs = 0;
     A c_av = A(1);
@@ -511,11 +491,7 @@ __device__ __forceinline__ int expand_row(const int64_t *__restrict__ colA, cons
         const int qq = q0 + u * BLOCK;
         const int q = qq < total ? qq : total - 1;
         if constexpr (LONG_B) {
-#if TSAMD_SPSPMM_REG_ENTRY
           if (!(c_off <= q && q < c_end)) {
-#else
-          {  // (A/B builds: search and read LDS for every product)
-#endif
             int lo = 0, hi = 64;  // last entry whose offset is <= q (zero-length entries are skipped)
 #pragma unroll
             for (int step = 0; step < 6; ++step) {
@@ -628,177 +604,12 @@ __global__ __launch_bounds__(BLOCK) void spspmm_symbolic_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Persistent one-wave kernels over the small rows, software-pipelined across rows.
-//
-// A row costs a chain of dependent round trips before its first product can be gathered: prod / rowptrA (uniform)
-// -> colA -> rowptrB -> colB.  With one row per workgroup (rounds 1-3) every wave sat through that chain alone:
-// after the owner scan took the instruction count down, the SQ counters showed the symbolic kernel 61 % of its
-// time parked on a wait with 46 % of the VALU slots used (profiles/r04_sq_counters.md) -- at 8 waves per SIMD the
-// device holds ~8 k rows in flight, and 500 k rows x 4 round trips / 8 k is most of the kernel's time.
-// Here a wave takes rows blockIdx.x, + gridDim.x, ... and keeps THREE future rows in flight: at the top of every
-// iteration it issues rowptrB of the next row (whose colA arrived during the previous iteration), colA (+ valA)
-// of the one after (whose rowptrA arrived ...) and prod / rowptrA (/ rowptrC) of the third -- one stage per row,
-// all in the same round trip as the current row's own gathers.
-// ---------------------------------------------------------------------------
-// MEASURED NEGATIVE (round 4, same box, profiles/r04_ab_spspmm_row_pipe.log): config 4 1.48 -> 1.80-1.82 ms (symbolic
-// 448 -> 532 us, numeric 844 -> 1085 us under the counter pass).  The per-row time of a wave did not move (7.3 -> 7.6 us):
-// what the SQ counters report as "waiting" is the row's LDS traffic and the LDS / VALU pipes shared with the other 7
-// waves of the SIMD (VALU 3.4 us + LDS ~2-3 us of a 7.3 us round at 8 waves per SIMD), not the four global round
-// trips -- those are already covered by the other waves.  On top, a persistent launch of 28 one-wave workgroups per CU
-// does not fit the numeric kernel's 5.9 KB of LDS 28 times (27 do): the 28th waits for a whole wave-lifetime.  Kept
-// behind the macro (default OFF) as the record of the experiment.
-#ifndef TSAMD_SPSPMM_ROW_PIPE
-#define TSAMD_SPSPMM_ROW_PIPE 0
-#endif
-#ifndef TSAMD_SPSPMM_PIPE_WAVES
-#define TSAMD_SPSPMM_PIPE_WAVES 28  // workgroups (= waves) per CU of the persistent launch (LDS: ~5.5-6 KB each of 160 KB)
-#endif
-
-#if TSAMD_SPSPMM_ROW_PIPE
-template <typename T, bool WITH_VAL>
-struct RowPipe {
-  using A = typename Traits<T>::acc_t;
-  // uniform per row: row id, entries [as, ae), products (RAW: whether the row is a small one is only looked at an
-  // iteration after the load was issued -- nothing in issue() may consume what it just asked for), output position
-  struct Head {
-    int64_t row, as, ae, out, pp;
-    __device__ __forceinline__ int p() const { return (pp > 0 && pp <= kSmallCap) ? (int)pp : 0; }
-  };
-  const int64_t *rowptrA, *colA, *rowptrB, *prod, *rowptrC;
-  const T *valA;
-  int64_t M, stride;
-  int lane;
-  Head h0, h1, h2;          // current row, next, the one after
-  uint32_t c1 = 0, c2 = 0;  // first 64 column ids of the rows h1 / h2 (per lane)
-  A av0 = A(1), av1 = A(1), av2 = A(1);
-  int64_t bs0 = 0;
-  int d0 = 0;
-
-  __device__ __forceinline__ Head fetch_head(int64_t r) const {  // stage 1: uniform loads
-    Head h{r, 0, 0, 0, 0};
-    if (r < M) {
-      h.pp = prod[r];
-      h.as = rowptrA[r];
-      h.ae = rowptrA[r + 1];
-      if (rowptrC != nullptr) h.out = rowptrC[r];
-    }
-    return h;
-  }
-  __device__ __forceinline__ void fetch_cols(const Head &h, uint32_t &c, A &av) const {  // stage 2
-    c = 0;
-    av = A(1);
-    const int64_t e = h.as + lane;
-    // (only dwords that stay live until rotate() are asked for: a dead half of a 64-bit load is a register the
-    // allocator hands out again at once, and writing it waits for the load -- the prefetch would stall at issue)
-    if (h.p() != 0 && e < h.ae) {
-      c = *reinterpret_cast<const uint32_t *>(colA + e);  // low half: column ids are < 2^32
-      if (WITH_VAL && valA != nullptr) av = Traits<T>::to_acc(valA[e]);
-    }
-  }
-  __device__ __forceinline__ void fetch_brow(const Head &h, uint32_t c, int64_t &bs, uint32_t &be_lo) const {  // stage 3
-    bs = 0;
-    be_lo = 0;
-    if (h.p() != 0 && h.as + lane < h.ae) {
-      bs = rowptrB[c];
-      be_lo = *reinterpret_cast<const uint32_t *>(rowptrB + (int64_t)c + 1);  // a B row has < 2^31 entries
-    }
-  }
-  __device__ __forceinline__ void start(int64_t first) {
-    h0 = fetch_head(first);
-    h1 = fetch_head(first + stride);
-    h2 = fetch_head(first + 2 * stride);
-    uint32_t c0;
-    fetch_cols(h0, c0, av0);
-    fetch_cols(h1, c1, av1);
-    uint32_t be0;
-    fetch_brow(h0, c0, bs0, be0);
-    d0 = (int)(be0 - (uint32_t)bs0);
-  }
-  // top of an iteration: one stage for each of the three rows behind the current one (loads only)
-  struct Next {
-    Head h3;
-    int64_t bs1;
-    uint32_t be1;
-  };
-  __device__ __forceinline__ Next issue() {
-    Next n;
-    fetch_brow(h1, c1, n.bs1, n.be1);
-    fetch_cols(h2, c2, av2);
-    n.h3 = fetch_head(h2.row + stride);
-    return n;
-  }
-  __device__ __forceinline__ void rotate(const Next &n) {
-    h0 = h1;
-    bs0 = n.bs1;
-    d0 = (int)(n.be1 - (uint32_t)n.bs1);
-    av0 = av1;
-    h1 = h2;
-    c1 = c2;
-    av1 = av2;
-    h2 = n.h3;
-  }
-};
-
-__global__ __launch_bounds__(64) void spspmm_symbolic_small_kernel(
-    const int64_t *__restrict__ rowptrA, const int64_t *__restrict__ colA,
-    const int64_t *__restrict__ rowptrB, const uint32_t *__restrict__ colB,
-    const int64_t *__restrict__ prod, int64_t M, int64_t *__restrict__ nnzC) {
-  constexpr int LOG_T = 10, kT = 1 << LOG_T;
-  __shared__ alignas(16) uint32_t tab[kT];
-  __shared__ ExpandScratch<float> sc;
-  const int lane = (int)threadIdx.x;
-  RowPipe<float, false> pipe{rowptrA, colA, rowptrB, prod, nullptr, nullptr, M, (int64_t)gridDim.x, lane};
-  pipe.start((int64_t)blockIdx.x);
-  while (pipe.h0.row < M) {
-    const auto nxt = pipe.issue();
-    if (pipe.h0.p() != 0) {  // wave-uniform
-      typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-      for (int t = 0; t < kT / 256; ++t)
-        *reinterpret_cast<u32x4 *>(tab + 4 * (lane + 64 * t)) = u32x4{kEmptyKey, kEmptyKey, kEmptyKey, kEmptyKey};
-      __syncthreads();
-      int fresh = 0;
-      auto insert = [&](int, uint32_t c, float) {
-        uint32_t h = hash_slot<LOG_T>(c, false);
-        for (;;) {
-          const uint32_t old = atomicCAS(&tab[h], kEmptyKey, c);
-          if (old == kEmptyKey) {
-            ++fresh;
-            break;
-          }
-          if (old == c) break;
-          h = (h + 1) & (kT - 1);
-        }
-      };
-      if (pipe.h0.ae - pipe.h0.as <= 64)  // wave-uniform; the prefetched chunk is the whole row
-        expand_row_wave<float, false, true>(colA, nullptr, rowptrB, colB, nullptr, pipe.h0.as, pipe.h0.ae, sc,
-                                            each_product(insert), pipe.bs0, pipe.d0, 1.0f);
-      else
-        expand_row_wave<float, false, false>(colA, nullptr, rowptrB, colB, nullptr, pipe.h0.as, pipe.h0.ae, sc,
-                                             each_product(insert));
-      fresh = (int)wave_scan_add_dpp((uint32_t)fresh);
-      if (lane == 63) nnzC[pipe.h0.row] = fresh;
-      __syncthreads();
-    }
-    pipe.rotate(nxt);
-  }
-}
-
-#endif  // TSAMD_SPSPMM_ROW_PIPE
-
-// ---------------------------------------------------------------------------
 // wave-level bitonic sort of 64 * I unique 32-bit keys held in registers, element
 // e = lane * I + j.  "Flip + butterfly" form: every compare-exchange leaves the minimum at the
 // lower position, so no direction bits are needed; strides below I stay inside a lane
 // (v_min / v_max on registers), the others exchange with lane ^ mask through DPP (masks 1, 2, 3,
-// 7, 15), ds_swizzle (4, 8, 16, 31) or ds_bpermute (32, 63) -- none of which allocates LDS.
+// 7, 8, 15), ds_swizzle (4, 16, 31) or ds_bpermute (32, 63) -- none of which allocates LDS.
 // ---------------------------------------------------------------------------
-#ifndef TSAMD_SPSPMM_DPP_XOR8
-#define TSAMD_SPSPMM_DPP_XOR8 1
-#endif
-#ifndef TSAMD_SPSPMM_DPP_XOR4
-#define TSAMD_SPSPMM_DPP_XOR4 0
-#endif
 template <int MASK>
 __device__ __forceinline__ uint32_t xor_lane(uint32_t v, int lane) {
   if constexpr (MASK == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
@@ -806,19 +617,9 @@ __device__ __forceinline__ uint32_t xor_lane(uint32_t v, int lane) {
   else if constexpr (MASK == 3) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x1B, 0xF, 0xF, true);
   else if constexpr (MASK == 7) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);
   else if constexpr (MASK == 15) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);
-#if TSAMD_SPSPMM_DPP_XOR8
   // lane ^ 8 inside a row of 16 lanes is a rotation by 8: row_ror:8 -- a VALU move instead of an LDS-pipe ds_swizzle
   // (12 of the 32 LDS-pipe exchanges of a 256-key sort; the pipe is shared by every wave of the CU)
   else if constexpr (MASK == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);
-#endif
-#if TSAMD_SPSPMM_DPP_XOR4
-  // lane ^ 4: banks 0 / 2 of a row read four lanes up (row_shl:4), banks 1 / 3 four lanes down (row_shr:4): two DPP
-  // moves under bank masks instead of one ds_swizzle
-  else if constexpr (MASK == 4) {
-    const int up = __builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xF, 0x5, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(up, (int)v, 0x114, 0xF, 0xA, false);
-  }
-#endif
   else if constexpr (MASK < 32) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (MASK << 10) | 0x1F);
   else return (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ MASK) << 2, (int)v);
 }
@@ -996,7 +797,6 @@ __global__ __launch_bounds__(64) void spspmm_numeric_small_kernel(
   const bool with_val = valC != nullptr;
   const int items = p <= 64 ? 1 : (p <= 128 ? 2 : (p <= 256 ? 4 : 8));  // keys per lane
   for (int q = p + lane; q < 64 * items; q += 64) skey[q] = kEmptyKey;   // padding sorts last
-#if TSAMD_SPSPMM_OWNER_SCAN
   __syncthreads();  // (one wave: the padding above is ordered before the packet stores below)
   // the lane's four consecutive products as ONE 16-byte store of keys (and one packet of values) when their slots
   // are a whole aligned group inside the arrays; slots past the row's end get the padding key again (they are padding:
@@ -1029,18 +829,6 @@ __global__ __launch_bounds__(64) void spspmm_numeric_small_kernel(
   else
     expand_row_wave<T, false>(colA, valA, rowptrB, colB, valB, as_i, ae_i, sc,
                               [&](int q0, int n, const uint32_t (&c)[4], const A (&v)[4]) { put4(std::false_type{}, q0, n, c, v); });
-#else
-  if (with_val) {
-    expand_row<T, 64, true>(colA, valA, rowptrB, colB, valB, rowptrA[i], rowptrA[i + 1], sc,
-                            [&](int q, uint32_t c, A v) {
-      skey[q] = (c << kIdxBits) | (uint32_t)q;
-      sval[q] = v;
-    });
-  } else {
-    expand_row<T, 64, false>(colA, valA, rowptrB, colB, valB, rowptrA[i], rowptrA[i + 1], sc,
-                             [&](int q, uint32_t c, A) { skey[q] = (c << kIdxBits) | (uint32_t)q; });
-  }
-#endif
   __syncthreads();
   if (items == 1) sort_lds_keys<1>(skey, lane);
   else if (items == 2) sort_lds_keys<2>(skey, lane);
@@ -1051,65 +839,6 @@ __global__ __launch_bounds__(64) void spspmm_numeric_small_kernel(
       p, out_i, colC, valC, sscan, [&](int idx) { return skey[idx] >> kIdxBits; },
       [&](int idx) { return sval[skey[idx] & (uint32_t)(kSmallCap - 1)]; });
 }
-
-#if TSAMD_SPSPMM_ROW_PIPE
-// The same kernel, persistent and pipelined over the rows (RowPipe above).
-template <typename T>
-__global__ __launch_bounds__(64) void spspmm_numeric_small_pipe_kernel(
-    const int64_t *__restrict__ rowptrA, const int64_t *__restrict__ colA,
-    const T *__restrict__ valA, const int64_t *__restrict__ rowptrB,
-    const uint32_t *__restrict__ colB, const T *__restrict__ valB,
-    const int64_t *__restrict__ prod, const int64_t *__restrict__ rowptrC, int64_t M,
-    int64_t *__restrict__ colC, T *__restrict__ valC) {
-  using A = typename Traits<T>::acc_t;
-  __shared__ alignas(16) uint32_t skey[kSmallCap];
-  __shared__ A sval[kSmallCap];
-  __shared__ ExpandScratch<A> sc;
-  __shared__ int sscan[8];
-  const int lane = (int)threadIdx.x;
-  const bool with_val = valC != nullptr;
-  auto row_body = [&](auto wv, RowPipe<T, decltype(wv)::value> &pipe) __attribute__((always_inline)) {
-    constexpr bool kWV = decltype(wv)::value;
-    pipe.start((int64_t)blockIdx.x);
-    while (pipe.h0.row < M) {
-      const auto nxt = pipe.issue();
-      const int p = pipe.h0.p();
-      if (p != 0) {  // wave-uniform
-        const int items = p <= 64 ? 1 : (p <= 128 ? 2 : (p <= 256 ? 4 : 8));  // keys per lane
-        for (int q = p + lane; q < 64 * items; q += 64) skey[q] = kEmptyKey;   // padding sorts last
-        auto put = [&](int q, uint32_t c, A v) {
-          skey[q] = (c << kIdxBits) | (uint32_t)q;
-          if constexpr (kWV) sval[q] = v;
-        };
-        if (pipe.h0.ae - pipe.h0.as <= 64)  // wave-uniform; the prefetched chunk is the whole row
-          expand_row_wave<T, kWV, true>(colA, valA, rowptrB, colB, valB, pipe.h0.as, pipe.h0.ae, sc, each_product(put),
-                                        pipe.bs0, pipe.d0, pipe.av0);
-        else
-          expand_row_wave<T, kWV, false>(colA, valA, rowptrB, colB, valB, pipe.h0.as, pipe.h0.ae, sc, each_product(put));
-        __syncthreads();
-        if (items == 1) sort_lds_keys<1>(skey, lane);
-        else if (items == 2) sort_lds_keys<2>(skey, lane);
-        else if (items == 4) sort_lds_keys<4>(skey, lane);
-        else sort_lds_keys<8>(skey, lane);
-        __syncthreads();
-        compress_and_store<T, 64>(
-            p, pipe.h0.out, colC, valC, sscan, [&](int idx) { return skey[idx] >> kIdxBits; },
-            [&](int idx) { return sval[skey[idx] & (uint32_t)(kSmallCap - 1)]; });
-        __syncthreads();
-      }
-      pipe.rotate(nxt);
-    }
-  };
-  if (with_val) {
-    RowPipe<T, true> pipe{rowptrA, colA, rowptrB, prod, rowptrC, valA, M, (int64_t)gridDim.x, lane};
-    row_body(std::true_type{}, pipe);
-  } else {
-    RowPipe<T, false> pipe{rowptrA, colA, rowptrB, prod, rowptrC, nullptr, M, (int64_t)gridDim.x, lane};
-    row_body(std::false_type{}, pipe);
-  }
-}
-
-#endif  // TSAMD_SPSPMM_ROW_PIPE
 
 // ---------------------------------------------------------------------------
 // numeric, (column, value) pairs sorted in LDS: medium rows (256 threads, bitonic) and small
@@ -1953,12 +1682,6 @@ __global__ __launch_bounds__(64) void spspmm_smallbin_accum_kernel(
   }
 }
 
-#ifndef TSAMD_SPSPMM_SUBBINS
-#define TSAMD_SPSPMM_SUBBINS 1  // 0: shared cursors (round-4 behaviour: bin order and big-bin sums run-dependent), for A/B builds
-#endif
-#ifndef TSAMD_SPSPMM_WAVE_ACCUM
-#define TSAMD_SPSPMM_WAVE_ACCUM 1  // 0: the 256-thread accumulation (sums in arrival order), for A/B builds
-#endif
 struct LargeWs {
   int64_t *hist;      // [n_large * nr * sub + 1] products per (bin, wave segment), scanned in place -> segment offsets
   int64_t *bin_off;   // [n_large * nr + 1] offset of every bin = of its first segment
@@ -1988,11 +1711,7 @@ size_t carve_large(void *base, int64_t n_large, int64_t P_large, int64_t N, size
   l.nr = (int)((N + ((int64_t)1 << l.lg_range) - 1) >> l.lg_range);
   if (l.nr < 1) l.nr = 1;
   l.ntask = n_large * (int64_t)l.nr;
-  static const bool subbins = [] {  // TSAMD_SPSPMM_SUBBINS=0 in the environment: the round-4 shared cursors (A/B runs)
-    const char *e = exp_env("TSAMD_SPSPMM_SUBBINS");
-    return e ? e[0] != '0' : (TSAMD_SPSPMM_SUBBINS != 0);
-  }();
-  l.sub = (subbins && l.nr <= kMaxRanges / (kLargeThreads / 64)) ? kLargeThreads / 64 : 1;
+  l.sub = l.nr <= kMaxRanges / (kLargeThreads / 64) ? kLargeThreads / 64 : 1;
   l.hist = (int64_t *)take(8 * (size_t)(l.ntask * l.sub + 1));
   l.bin_off = (int64_t *)take(8 * (size_t)(l.ntask + 1));
   l.bin_cnt = (int64_t *)take(8 * (size_t)(l.ntask + 1));
@@ -2010,27 +1729,6 @@ size_t carve_large(void *base, int64_t n_large, int64_t P_large, int64_t N, size
   if (w) *w = l;
   return off;
 }
-
-#if TSAMD_SPSPMM_ROW_PIPE
-unsigned int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-  }
-  return (unsigned int)cus;
-}
-
-// one-wave workgroups of the pipelined small-row kernels: as many as the device holds at once, never more than rows
-unsigned int pipe_blocks(int64_t M) {
-  const int64_t cap = (int64_t)device_cus() * TSAMD_SPSPMM_PIPE_WAVES;
-  return (unsigned int)(M < cap ? (M > 0 ? M : 1) : cap);
-}
-#endif
 
 unsigned int persistent_blocks();
 // one-wave workgroups of the reproducible accumulation: as many as the LDS of the device holds at once
@@ -2054,14 +1752,9 @@ unsigned int persistent_blocks() {
   return (unsigned int)cus * TSAMD_SPSPMM_ACCUM_WGS;
 }
 
-// dynamic LDS of the hist / bin kernels: their nr * sub counters (TSAMD_SPSPMM_STATIC_COUNTERS=1 in the environment asks
-// for the round-4 footprint of kMaxRanges counters: same-box A/B runs of the occupancy effect)
+// dynamic LDS of the hist / bin kernels: their nr * sub counters
 static size_t large_counter_bytes(int nr, int sub) {
-  static const bool fat = [] {
-    const char *e = exp_env("TSAMD_SPSPMM_STATIC_COUNTERS");
-    return e != nullptr && e[0] == '1';
-  }();
-  const size_t n = fat ? (size_t)kMaxRanges : (size_t)nr * (size_t)sub;
+  const size_t n = (size_t)nr * (size_t)sub;
   // (the bin kernel keeps an int64 offset beside every cursor when there are at most kOffLdsMax of them; the hist kernel
   // uses the first part only)
   const size_t off_bytes = n <= (size_t)kOffLdsMax ? n * sizeof(int64_t) : 0;
@@ -2148,7 +1841,7 @@ int numeric_large(const int64_t *rowptrA, const int64_t *colA, const void *valA,
                      (const uint32_t *)w.bcol, (const T *)bv, (const int64_t *)w.bin_cnt, rowptrC, colC,
                      reinterpret_cast<T *>(valC));
   TSAMD_LAUNCH_CHECK();
-  if (w.sub > 1 && TSAMD_SPSPMM_WAVE_ACCUM)  // bins in a reproducible order: sum them in that order, one wave per bin
+  if (w.sub > 1)  // bins in a reproducible order: sum them in that order, one wave per bin
     hipLaunchKernelGGL((spspmm_large_accum_wave_kernel<T>), dim3(persistent_wave_blocks<T>()), dim3(64), 0, stream,
                        rows, w.nr, (const int64_t *)(w.lists + w.ntask), (const int64_t *)(w.counts + 1),
                        (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, (const T *)bv, (const int64_t *)w.bin_cnt,
@@ -2175,13 +1868,10 @@ int numeric_rows(const int64_t *rowptrA, const int64_t *colA, const void *valA, 
   T *vc = reinterpret_cast<T *>(valC);
   {  // small rows: all M rows in natural order, the kernel skips the others
     if (bits + kIdxBits <= 32) {
-#if TSAMD_SPSPMM_ROW_PIPE
-      hipLaunchKernelGGL((spspmm_numeric_small_pipe_kernel<T>), dim3(pipe_blocks(M)), dim3(64), 0, stream,
-                         rowptrA, colA, va, rowptrB, colB, vb, prod, rowptrC, M, colC, vc);
-#else
+      // (one workgroup per row: a persistent launch pipelined across rows measured slower,
+      // profiles/r04_ab_spspmm_row_pipe.log)
       hipLaunchKernelGGL((spspmm_numeric_small_kernel<T>), dim3((unsigned int)M), dim3(64), 0, stream,
                          rowptrA, colA, va, rowptrB, colB, vb, prod, rowptrC, colC, vc);
-#endif
     } else
       hipLaunchKernelGGL((spspmm_numeric_pairs_kernel<T, 64, kSmallCap>), dim3((unsigned int)M), dim3(64),
                          0, stream, rowptrA, colA, va, rowptrB, colB, vb, prod, bins, rowptrC, colC, vc,
@@ -2259,17 +1949,12 @@ extern "C" int tsamd_spspmm_symbolic(int dtype, const int64_t *rowptrA, const in
     return TSAMD_ERR_WORKSPACE;
   TSAMD_HIP_TRY(hipMemsetAsync(nnzC, 0, sizeof(int64_t) * (size_t)M, stream));
   const bool narrow_cols = N <= ((int64_t)1 << 24);  // hash_slot: 24-bit multiply
-#if TSAMD_SPSPMM_ROW_PIPE
-  hipLaunchKernelGGL(spspmm_symbolic_small_kernel, dim3(pipe_blocks(M)), dim3(64), 0, stream, rowptrA, colA,
-                     rowptrB, colB, prod, M, nnzC);
-#else
   if (narrow_cols)
     hipLaunchKernelGGL((spspmm_symbolic_kernel<64, 10, true>), dim3((unsigned int)M), dim3(64), 0, stream, rowptrA,
                        colA, rowptrB, colB, prod, bins, nnzC);
   else
     hipLaunchKernelGGL((spspmm_symbolic_kernel<64, 10, false>), dim3((unsigned int)M), dim3(64), 0, stream, rowptrA,
                        colA, rowptrB, colB, prod, bins, nnzC);
-#endif
   TSAMD_LAUNCH_CHECK();
   if (n_medium > 0) {
     if (narrow_cols)

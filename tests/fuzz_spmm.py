@@ -6,7 +6,7 @@ because it drives the oracle.  Usage (on a GPU box):
 
 Draws: M up to 2e5 rows, degree laws (uniform / Zipf / a few hubs / block-empty), N up to 1e6
 columns incl. hub-heavy column laws that trigger the relabel probe, K in 1..300, all six dtypes, four
-reductions, batches, TSAMD_SPMM_RELABEL in {auto, 0, 1}.  Prints one line per failure and a summary;
+reductions, batches.  Prints one line per failure and a summary;
 exit code 1 when anything failed."""
 import argparse
 import os
@@ -80,8 +80,6 @@ def main():
         batch = () if rng.random() < 0.8 else (int(rng.integers(1, 3)), )
         has_value = bool(rng.random() < 0.6)
         reduce = ['sum', 'mean', 'min', 'max'][rng.integers(4)]
-        relabel = ['auto', '0', '1'][rng.integers(3)]
-        os.environ['TSAMD_SPMM_RELABEL'] = relabel
         g = torch.Generator().manual_seed(case)
         if dtype.is_floating_point:
             v = (torch.rand(E, generator=g) - 0.3).to(dtype) if has_value else None
@@ -90,8 +88,8 @@ def main():
             v = torch.randint(-4, 5, (E, ), dtype=dtype, generator=g) if has_value else None
             x = torch.randint(-9, 9, (*batch, N, K), dtype=dtype, generator=g)
         rpt, ct = torch.from_numpy(rp), torch.from_numpy(c)
-        tag = 'case %d: M=%d N=%d E=%d K=%d %s %s batch=%s value=%s relabel=%s' % (
-            case, M, N, E, K, dtype, reduce, batch, has_value, relabel)
+        tag = 'case %d: M=%d N=%d E=%d K=%d %s %s batch=%s value=%s' % (
+            case, M, N, E, K, dtype, reduce, batch, has_value)
         try:
             out, arg = nat.spmm(rpt.to(dev), ct.to(dev), None if v is None else v.to(dev), x.to(dev), reduce)
             torch.cuda.synchronize()

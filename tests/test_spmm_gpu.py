@@ -10,7 +10,7 @@ import torch
 from oracle import c_oracle as oc
 from pytorch_sparse_amd import _native as nat
 from pytorch_sparse_amd import synth
-from tests.util import (ALL_DTYPES, CODE, FLOAT_DTYPES, SUM_ATOL, SUM_TOL, bits_equal, check_spmm, experiments_build, fromnp,
+from tests.util import (ALL_DTYPES, CODE, FLOAT_DTYPES, SUM_ATOL, SUM_TOL, bits_equal, check_spmm, fromnp,
                         oracle_spmm, tonp)
 
 pytestmark = pytest.mark.gpu
@@ -226,20 +226,12 @@ def _csc_arrays(rp, c, n_cols):
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float64])
-def test_minmax_bw_winner_lists_hub_columns(dev, dtype):
-    if not experiments_build():
-        pytest.skip('the winner-list route is only compiled into experiment builds (scripts/variants.py)')
-    _minmax_bw_winner_lists_hub_columns(dev, dtype)
-
-
-def _minmax_bw_winner_lists_hub_columns(dev, dtype):
-    """The winner-list route of tsamd_spmm_minmax_bw_csc (csrc/spmm_bw_list.hip, TSAMD_MINMAX_BW_LISTS=1, K <= 1024) on a
-    power-law graph whose hub columns span many 256-position waves of the pull kernel (head / tail carries + fix-up)
-    and whose long rows span many 64-entry chunks of the list kernel (offsets of cut rows): against the default route
-    (win masks + masked merge-path SpMM; same arithmetic, other summation order) and against
-    exact integer arithmetic (small integer operands: every sum is exact in fp32, so BOTH routes must agree bit for
-    bit); K up to the tile limit, a batch, value-less, columns without entries."""
-    import os
+def test_minmax_bw_pull_hub_columns(dev, dtype):
+    """grad_mat of tsamd_spmm_minmax_bw_csc (win masks + masked merge-path SpMM) on a power-law graph whose hub columns
+    span many 256-position waves of the pull kernel (head / tail carries + fix-up): against the scatter route
+    (tsamd_spmm_minmax_bw; same arithmetic, other summation order) and against exact integer arithmetic (small integer
+    operands: every sum is exact in fp32, so both routes must agree bit for bit); K up to 1024, a batch, value-less,
+    columns without entries."""
     rp, c = synth.rmat_csr(12, 24, seed=11)
     n, E = 1 << 12, c.numel()
     deg_col = torch.bincount(c, minlength=n)
@@ -254,18 +246,11 @@ def _minmax_bw_winner_lists_hub_columns(dev, dtype):
         out, arg = run_gpu(dev, rp, c, v, x, 'max')
         args = (rp.to(dev), c.to(dev), None if v is None else v.to(dev), x.to(dev), gout.to(dev), arg,
                 colptr.to(dev), perm.to(dev), row.to(dev))
-        _, gm_masks = nat.spmm_minmax_bw_csc(*args, want_value=False, want_mat=True)
-        os.environ['TSAMD_MINMAX_BW_LISTS'] = '1'
-        try:
-            _, gm = nat.spmm_minmax_bw_csc(*args, want_value=False, want_mat=True)
-        finally:
-            del os.environ['TSAMD_MINMAX_BW_LISTS']
+        _, gm = nat.spmm_minmax_bw_csc(*args, want_value=False, want_mat=True)
         _, gm_scatter = nat.spmm_minmax_bw(rp.to(dev), c.to(dev), None if v is None else v.to(dev), x.to(dev), gout.to(dev),
                                            arg, want_value=False, want_mat=True)
-        if dtype == torch.bfloat16:  # sums beyond 256 round: the two pulls (fp32 sums, one rounding) still agree exactly
-            assert bits_equal(gm, gm_masks), (K, batch)
-        else:
-            assert bits_equal(gm, gm_masks) and bits_equal(gm, gm_scatter), (K, batch)
+        if dtype != torch.bfloat16:  # (bf16 sums beyond 256 round: the scatter rounds at every addition)
+            assert bits_equal(gm, gm_scatter), (K, batch)
         # exact reference on the host: scatter of the integer products
         a = arg.cpu()
         valid = a != E
@@ -284,22 +269,9 @@ def _minmax_bw_winner_lists_hub_columns(dev, dtype):
             assert torch.equal(gm.cpu(), want.to(dtype)), (K, batch)  # exact sum, rounded once
 
 
-@pytest.fixture(params=['masks', 'lists'])
-def pull_route(request):
-    """Both grad_mat routes of tsamd_spmm_minmax_bw_csc: the default (win masks + masked merge-path SpMM) and the
-    winner lists (TSAMD_MINMAX_BW_LISTS=1)."""
-    import os
-    if request.param == 'lists':
-        if not experiments_build():
-            pytest.skip('the winner-list route is only compiled into experiment builds (scripts/variants.py)')
-        os.environ['TSAMD_MINMAX_BW_LISTS'] = '1'
-    yield request.param
-    os.environ.pop('TSAMD_MINMAX_BW_LISTS', None)
-
-
 @pytest.mark.parametrize('reduce', ['min', 'max'])
 @pytest.mark.parametrize('dtype', FLOAT_DTYPES)
-def test_minmax_bw_csc_pull(dev, dtype, reduce, pull_route):
+def test_minmax_bw_csc_pull(dev, dtype, reduce):
     """tsamd_spmm_minmax_bw_csc (winner masks + masked merge-path SpMM over the CSC view) against the fp64
     formulas of csrc/spmm.cpp:204-242: fp32 (fp64) accumulation, one rounding -- so well inside the bound of the
     scatter kernel -- deterministic, identical grad_value; rows above and below 64 entries, K that is not a
@@ -399,45 +371,35 @@ def test_minmax_arg32_forward_and_pull(dev, dtype):
 
 @pytest.mark.parametrize('dtype', FLOAT_DTYPES)
 def test_masked_sddmm_pipelined_against_round4_kernel(dev, dtype):
-    if not experiments_build():
-        pytest.skip('TSAMD_MASKED_SDDMM_PIPE is only read by experiment builds (scripts/variants.py)')
-    _masked_sddmm_pipelined_against_round4_kernel(dev, dtype)
-
-
-def _masked_sddmm_pipelined_against_round4_kernel(dev, dtype):
-    """grad_value of the pull backward: the pipelined masked SDDMM (record words of 8 steps in one round trip, the
-    gathers of two steps in flight, v_dot2c for 2-byte types) against the round-4 kernel (TSAMD_MASKED_SDDMM_PIPE=0)
-    for every lane-group width (1 ... 64 packets per row, also counts that are not powers of two), batches, a chunk
-    that ends inside a wave (E % 64 != 0), and against the fp64 formula."""
-    import os
+    """grad_value of the pull backward against the fp64 formula: the pipelined masked SDDMM (record words of 8 steps in
+    one round trip, the gathers of two steps in flight, v_dot2c for 2-byte types) for every lane-group width (1 ... 64
+    packets per row, also counts that are not powers of two), batches, a chunk that ends inside a wave (E % 64 != 0);
+    65 packets per row take the round-4 kernel (spmm_value_bw_kernel with records).  grad_mat must not depend on the
+    grad_value route: it is checked against the pull without grad_value."""
     rp, c = synth.rmat_csr(10, 12, seed=4)
     n, E = 1 << 10, c.numel()
     assert E % 64 != 0
     colptr, perm, row = _csc_arrays(rp, c, n)
     vec = 16 // torch.empty(0, dtype=dtype).element_size()
     u = {torch.float32: 2.0 ** -24, torch.float64: 2.0 ** -53, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]
-    for slots, batch in ((1, ()), (2, (2, )), (3, ()), (4, ()), (8, ()), (16, ()), (24, ()), (32, (2, )), (64, ())):
+    for slots, batch in ((1, ()), (2, (2, )), (3, ()), (4, ()), (8, ()), (16, ()), (24, ()), (32, (2, )), (64, ()),
+                         (65, ())):
         K = slots * vec
         v, x = make_inputs(rp, c, n, K, dtype, True, batch)
         gout = synth.features(n, K, seed=9, dtype=dtype, batch=batch)
         out, arg = run_gpu(dev, rp, c, v, x, 'max')
         args = (rp.to(dev), c.to(dev), v.to(dev), x.to(dev), gout.to(dev), arg, colptr.to(dev), perm.to(dev), row.to(dev))
         gv, gm = nat.spmm_minmax_bw_csc(*args, want_value=True, want_mat=True)
-        os.environ['TSAMD_MASKED_SDDMM_PIPE'] = '0'
-        try:
-            gv_old, gm_old = nat.spmm_minmax_bw_csc(*args, want_value=True, want_mat=True)
-        finally:
-            os.environ.pop('TSAMD_MASKED_SDDMM_PIPE', None)
-        assert bits_equal(gm, gm_old)
+        _, gm_only = nat.spmm_minmax_bw_csc(*args, want_value=False, want_mat=True)
+        assert bits_equal(gm, gm_only)
         egv, _ = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().numpy(), x.double().numpy(), gout.double().numpy(),
                                    arg.cpu().numpy(), want_value=True)
         l1, _ = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().numpy(), x.double().abs().numpy(),
                                   gout.double().abs().numpy(), arg.cpu().numpy(), want_value=True)
         acc_u = 2.0 ** -53 if dtype == torch.float64 else 2.0 ** -24
         bound = (K * len(batch or (1, )) * 2 + 2) * acc_u * l1 + u * np.abs(egv) * 1.01 + 1e-30
-        for got in (gv, gv_old):
-            err = np.abs(got.cpu().double().numpy() - egv)
-            assert (err <= bound).all(), (slots, batch, float((err / bound).max()))
+        err = np.abs(gv.cpu().double().numpy() - egv)
+        assert (err <= bound).all(), (slots, batch, float((err / bound).max()))
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16, torch.float32])
@@ -600,32 +562,22 @@ def test_full_size_properties(dev, config):
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float64])
-def test_relabel_path_is_bit_identical(dev, dtype, monkeypatch):
-    """The channel-camping avoidance (hashed-row copy of mat) only changes addresses:
-    forced on and forced off must give bit-identical results, batched input included, and the
-    N that is not a power of two exercises the cycle-walking hash."""
-    n, m, K = 9001, 5000, 8
+def test_relabel_path_is_bit_identical(dev, dtype):
+    """The channel-camping avoidance (hashed-row copy of mat) only changes addresses: on low-bit-skewed
+    column ids (what the probe looks for) with 256-byte rows the shipped decision takes the copy for sums (and for
+    fp32 / fp64 max), and the result must match the oracle, batched input included; the N that is not a power of two
+    exercises the cycle-walking hash."""
+    n, m = 9001, 5000
+    K = 256 // torch.empty(0, dtype=dtype).element_size()  # a power-of-two row pitch of 256 bytes
     g = torch.Generator().manual_seed(11)
     E = 1300000
     row, col = torch.randint(0, m, (E, ), generator=g), torch.randint(0, n, (E, ), generator=g)
     col[::3] &= ~7  # low-bit skew, as the probe looks for
     rp, c = synth.to_csr(row, col, m, n)
     v, x = make_inputs(rp, c, n, K, dtype, True, batch=(2, ))
-    res = {}
-    if not experiments_build():
-        pytest.skip('TSAMD_SPMM_RELABEL is only read by experiment builds; tests/test_relabelled_gpu.py covers the copy')
-    for mode in ('0', '1', 'auto'):
-        monkeypatch.setenv('TSAMD_SPMM_RELABEL', mode)
-        for reduce in ('sum', 'max'):
-            out, arg = run_gpu(dev, rp, c, v, x, reduce)
-            res[(mode, reduce)] = (out.cpu(), None if arg is None else arg.cpu())
     for reduce in ('sum', 'max'):
-        for mode in ('1', 'auto'):
-            assert bits_equal(res[('0', reduce)][0], res[(mode, reduce)][0]), (mode, reduce)
-        if reduce == 'max':
-            assert torch.equal(res[('0', reduce)][1], res[('1', reduce)][1])
-    check_spmm(res[('1', 'max')][0], res[('1', 'max')][1], rp, c, v, x, 'max')
-    check_spmm(res[('1', 'sum')][0], None, rp, c, v, x, 'sum')
+        out, arg = run_gpu(dev, rp, c, v, x, reduce)
+        check_spmm(out, arg, rp, c, v, x, reduce)
 
 
 def test_spmm_fuzz_small_shapes(dev):
