@@ -685,6 +685,26 @@ int tsamd_set_diag_apply(const int64_t *pos, const int64_t *row, const int64_t *
  * tsamd_subset_assoc  assoc[M] = position of every node in idx, -1 elsewhere (the association
  *                     array of subgraph_cpu, csrc/cpu/saint_cpu.cpp:17-18); *err = #bad ids.
  *                     SAINT sub-graphs are then select + filter(TSAMD_KEEP_COL_MAPPED).
+ *
+ * ego_k_hop_sample_adj (csrc/cpu/ego_sample_cpu.cpp, CPU-only in the reference): one sub-graph per seed g = idx[g]
+ * (duplicates included, each independent).  Every function below ADDS the number of ids outside [0, M) it meets to
+ * *err (device, the caller zeroes it once per call) and uses node 0 in their place, so nothing reads out of bounds.
+ *   tsamd_ego_seeds     seg_out[g] = g, node_out[g] = idx[g]: the pairs (seed, node) the node sets start from.
+ *   tsamd_ego_plan      one hop: out_ptr[F + 1] = exclusive scan of the draws per frontier entry -- the whole row when
+ *                       deg <= num_neighbors (both replace modes), else num_neighbors; nothing when num_neighbors < 0;
+ *                       *total (device) = number of draws.
+ *   tsamd_ego_draw      the T draws of that hop (one lane per draw): nbr[t] = the drawn column, seg_out[t] = fseg of its
+ *                       frontier entry.  Without replacement a uniform subset (Floyd up to deg 64, the keyed bijection
+ *                       above), with it uniform picks -- tsamd_sample_draw's draws, keyed by (seed, frontier position,
+ *                       j).  The next frontier is (nbr, seg_out), duplicates included.
+ *   node sets           tsamd_sort_coalesce_reduce, index only, of the pairs (seg, node) of the seeds and all draws with
+ *                       sizes (n, M): col_u = n_id (ascending inside a seed), row_u = its seed, ind2ptr(row_u, n) = ptr.
+ *   tsamd_ego_roots     root_n_id[g] = position of idx[g] in n_id[ptr[g] : ptr[g + 1]], plus ptr[g].
+ *   tsamd_ego_induced_count / _write   the induced sub-graphs.  vptr[D + 1] / V = tsamd_select_plan(rowptr, M, n_id,
+ *                       D): virtual entry x (of V) is stored entry e of row n_id[i] in (i, e) order.  _count: *count
+ *                       (device) = number of entries whose column lies in the node set of the row's seed n_seg[i];
+ *                       _write (same inputs, the workspace of _count): for those, in virtual-entry order, row_out = i,
+ *                       col_out = position of the column in n_id, e_id_out = e.  ind2ptr(row_out, D) = the rowptr.
  * ------------------------------------------------------------------------ */
 int tsamd_random_walk(const int64_t *rowptr, const int64_t *col, const int64_t *start,
                       const float *rand, int64_t n, int64_t walk_length, int64_t *out,
@@ -725,6 +745,23 @@ int tsamd_temporal_emit(const int64_t *nbr, const int64_t *e, const int64_t *seg
                         int64_t *node_out, int64_t *root_out, int64_t *time_out, void *stream);
 int tsamd_subset_assoc(const int64_t *idx, int64_t n, int64_t M, int64_t *assoc, int64_t *err,
                        void *stream);
+int tsamd_ego_seeds(const int64_t *idx, int64_t n, int64_t M, int64_t *seg_out, int64_t *node_out, int64_t *err,
+                    void *stream);
+size_t tsamd_ego_plan_workspace_bytes(int64_t F);
+int tsamd_ego_plan(const int64_t *rowptr, int64_t M, const int64_t *frontier, int64_t F, int64_t num_neighbors,
+                   int64_t *out_ptr, int64_t *total, int64_t *err, void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_ego_draw(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *frontier, const int64_t *fseg,
+                   int64_t F, int64_t num_neighbors, int replace, uint64_t seed, const int64_t *out_ptr, int64_t T,
+                   int64_t *nbr, int64_t *seg_out, int64_t *err, void *stream);
+int tsamd_ego_roots(const int64_t *idx, int64_t n, const int64_t *ptr, const int64_t *n_id, int64_t *root_n_id,
+                    void *stream);
+size_t tsamd_ego_induced_workspace_bytes(int64_t V);
+int tsamd_ego_induced_count(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *n_id,
+                            const int64_t *n_seg, int64_t D, const int64_t *ptr, const int64_t *vptr, int64_t V,
+                            int64_t *count, int64_t *err, void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_ego_induced_write(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *n_id,
+                            const int64_t *n_seg, int64_t D, const int64_t *ptr, const int64_t *vptr, int64_t V,
+                            const void *workspace, int64_t *row_out, int64_t *col_out, int64_t *e_id_out, void *stream);
 
 #ifdef __cplusplus
 }

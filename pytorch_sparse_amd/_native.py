@@ -41,6 +41,8 @@ SYMBOLS = [
     'tsamd_relabel_workspace_bytes', 'tsamd_relabel_plan', 'tsamd_relabel_apply', 'tsamd_relabel_seed',
     'tsamd_relabel_extend', 'tsamd_temporal_mark', 'tsamd_temporal_redraw_workspace_bytes', 'tsamd_temporal_redraw',
     'tsamd_temporal_relabel_workspace_bytes', 'tsamd_temporal_relabel', 'tsamd_temporal_emit', 'tsamd_subset_assoc',
+    'tsamd_ego_seeds', 'tsamd_ego_plan_workspace_bytes', 'tsamd_ego_plan', 'tsamd_ego_draw', 'tsamd_ego_roots',
+    'tsamd_ego_induced_workspace_bytes', 'tsamd_ego_induced_count', 'tsamd_ego_induced_write',
 ]
 
 DTYPES = {

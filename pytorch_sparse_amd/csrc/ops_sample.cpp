@@ -803,6 +803,123 @@ std::tuple<TensorDict, TensorDict, TensorDict, TensorDict> hetero_temporal_neigh
   return pack_hetero(node_types, colptr_dict, tnode, rows, cols, edges, hs.any);
 }
 
+// torch_sparse::ego_k_hop_sample_adj(Tensor rowptr, Tensor col, Tensor idx, int depth, int num_neighbors, bool replace)
+//   -> (Tensor rowptr, Tensor col, Tensor n_id, Tensor e_id, Tensor ptr, Tensor root_n_id)
+// (reference schema, csrc/ego_sample.cpp; CPU-only there, csrc/cpu/ego_sample_cpu.cpp).  Every seed g grows its own
+// depth-hop node set S_g (every draw of a hop is expanded in the next one, duplicates included); n_id lists each S_g in
+// ascending id order, and the sub-graph induced by S_g follows in (row ascending, stored order) -- the reference's
+// outputs bit for bit once the sets are fixed.  Host read-backs: one per hop (the number of draws) + the number of
+// distinct (seed, node) pairs + the number of candidate entries V + the number of kept entries; none per seed or row.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ego_k_hop_sample_adj(Tensor rowptr, Tensor col, Tensor idx,
+                                                                                int64_t depth, int64_t num_neighbors,
+                                                                                bool replace) {
+  check_index(rowptr, "rowptr");
+  check_index(col, "col");
+  check_index(idx, "idx");
+  TORCH_CHECK(rowptr.numel() >= 1, "ego_k_hop_sample_adj: empty rowptr");
+  c10::hip::HIPGuard guard(rowptr.get_device());
+  rowptr = rowptr.contiguous();
+  col = col.contiguous();
+  idx = idx.contiguous();
+  const int64_t M = rowptr.numel() - 1, n = idx.numel();
+  auto iopt = rowptr.options().requires_grad(false);
+  if (n == 0) {  // (the reference's loops have nothing to do and torch::cat gets an empty list)
+    auto none = [&]() { return torch::empty({0}, iopt); };
+    return std::make_tuple(torch::zeros({1}, iopt), none(), none(), none(), torch::zeros({1}, iopt), none());
+  }
+  TORCH_CHECK_INDEX(M > 0, "index out of range: the graph has no nodes");
+  void *stream = current_stream(rowptr);
+  // device words: [0, 4) the coalesce's counts, [4] #ids outside [0, M) (all steps add to it), [5] draws of the hop,
+  // [6, 8) select_plan's info (V, #bad ids) -- [7] then receives the number of kept entries
+  Tensor words = torch::zeros({8}, iopt);
+  int64_t *w = words.data_ptr<int64_t>();
+  auto check_ids = [&](int64_t bad) {
+    TORCH_CHECK_INDEX(bad == 0, "index out of range: ", bad, " node ids are outside [0, ", M, ")");
+  };
+
+  Tensor seg0 = torch::empty({n}, iopt), node0 = torch::empty({n}, iopt);
+  check_status(tsamd_ego_seeds(idx.data_ptr<int64_t>(), n, M, seg0.data_ptr<int64_t>(), node0.data_ptr<int64_t>(), w + 4,
+                               stream),
+               "tsamd_ego_seeds");
+  std::vector<Tensor> segs{seg0}, nodes{node0};
+  Tensor frontier = node0, fseg = seg0;
+  const uint64_t seed0 = host_seed();
+  for (int64_t hop = 0; hop < depth && num_neighbors > 0; ++hop) {  // k <= 0 draws nothing (ego_sample_cpu.cpp:49-73)
+    const int64_t F = frontier.numel();
+    if (F == 0) break;
+    Tensor out_ptr = torch::empty({F + 1}, iopt);
+    Tensor ws = workspace(tsamd_ego_plan_workspace_bytes(F), rowptr);
+    check_status(tsamd_ego_plan(rowptr.data_ptr<int64_t>(), M, frontier.data_ptr<int64_t>(), F, num_neighbors,
+                                out_ptr.data_ptr<int64_t>(), w + 5, w + 4, ws.data_ptr(), (size_t)ws.numel(), stream),
+                 "tsamd_ego_plan");
+    const Tensor h = words.narrow(0, 4, 2).cpu();  // read-back: the hop's number of draws
+    check_ids(h.data_ptr<int64_t>()[0]);
+    const int64_t T = h.data_ptr<int64_t>()[1];
+    Tensor nbr = torch::empty({T}, iopt), sg = torch::empty({T}, iopt);
+    check_status(tsamd_ego_draw(rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), M, frontier.data_ptr<int64_t>(),
+                                fseg.data_ptr<int64_t>(), F, num_neighbors, replace ? 1 : 0,
+                                seed0 + 0x9E3779B97F4A7C15ull * (uint64_t)(hop + 1), out_ptr.data_ptr<int64_t>(), T,
+                                nbr.data_ptr<int64_t>(), sg.data_ptr<int64_t>(), w + 4, stream),
+                 "tsamd_ego_draw");
+    segs.push_back(sg);
+    nodes.push_back(nbr);
+    frontier = nbr;
+    fseg = sg;
+  }
+
+  // the node sets: distinct (seed, node) pairs in row-major order
+  Tensor seg = segs.size() == 1 ? segs[0] : torch::cat(segs), node = nodes.size() == 1 ? nodes[0] : torch::cat(nodes);
+  const int64_t L = seg.numel();
+  Tensor row_t = torch::empty({L}, iopt), col_t = torch::empty({L}, iopt);
+  Tensor row_u = torch::empty({L}, iopt), col_u = torch::empty({L}, iopt), seg_ptr = torch::empty({L + 1}, iopt);
+  {
+    Tensor ws = workspace(tsamd_sort_coalesce_workspace_bytes(L), rowptr);
+    check_status(tsamd_sort_coalesce_reduce(seg.data_ptr<int64_t>(), node.data_ptr<int64_t>(), L, n, M,
+                                            row_t.data_ptr<int64_t>(), col_t.data_ptr<int64_t>(),
+                                            row_u.data_ptr<int64_t>(), col_u.data_ptr<int64_t>(),
+                                            seg_ptr.data_ptr<int64_t>(), w, TSAMD_F32, TSAMD_SUM, nullptr, nullptr,
+                                            nullptr, ws.data_ptr(), (size_t)ws.numel(), stream),
+                 "tsamd_sort_coalesce_reduce");
+  }
+  const Tensor hd = words.narrow(0, 2, 3).cpu();  // read-back: the number of distinct pairs
+  check_ids(hd.data_ptr<int64_t>()[2]);
+  const int64_t D = hd.data_ptr<int64_t>()[0];
+  Tensor n_id = D == L ? col_u : col_u.narrow(0, 0, D).clone();
+  Tensor n_seg = row_u.narrow(0, 0, D);
+  Tensor ptr = torch::empty({n + 1}, iopt), root_n_id = torch::empty({n}, iopt);
+  check_status(tsamd_ind2ptr(n_seg.data_ptr<int64_t>(), n, D, ptr.data_ptr<int64_t>(), stream), "tsamd_ind2ptr");
+  check_status(tsamd_ego_roots(idx.data_ptr<int64_t>(), n, ptr.data_ptr<int64_t>(), n_id.data_ptr<int64_t>(),
+                               root_n_id.data_ptr<int64_t>(), stream),
+               "tsamd_ego_roots");
+
+  // the induced sub-graphs: every stored entry of every row of n_id is a candidate
+  Tensor vptr = torch::empty({D + 1}, iopt);
+  {
+    Tensor ws = workspace(tsamd_select_workspace_bytes(D), rowptr);
+    check_status(tsamd_select_plan(rowptr.data_ptr<int64_t>(), M, n_id.data_ptr<int64_t>(), D,
+                                   vptr.data_ptr<int64_t>(), w + 6, ws.data_ptr(), (size_t)ws.numel(), stream),
+                 "tsamd_select_plan");
+  }
+  const int64_t V = words.narrow(0, 6, 1).cpu().data_ptr<int64_t>()[0];  // read-back: the number of candidates
+  Tensor ws = workspace(tsamd_ego_induced_workspace_bytes(V), rowptr);
+  check_status(tsamd_ego_induced_count(rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), M, n_id.data_ptr<int64_t>(),
+                                       n_seg.data_ptr<int64_t>(), D, ptr.data_ptr<int64_t>(), vptr.data_ptr<int64_t>(), V,
+                                       w + 7, w + 4, ws.data_ptr(), (size_t)ws.numel(), stream),
+               "tsamd_ego_induced_count");
+  const Tensor hk = words.narrow(0, 4, 4).cpu();  // read-back: the number of kept entries
+  check_ids(hk.data_ptr<int64_t>()[0]);
+  const int64_t K = hk.data_ptr<int64_t>()[3];
+  Tensor row_o = torch::empty({K}, iopt), col_o = torch::empty({K}, iopt), e_id = torch::empty({K}, iopt);
+  if (K > 0)  // (empty outputs have no storage to pass on)
+    check_status(tsamd_ego_induced_write(rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), M,
+                                         n_id.data_ptr<int64_t>(), n_seg.data_ptr<int64_t>(), D, ptr.data_ptr<int64_t>(),
+                                         vptr.data_ptr<int64_t>(), V, ws.data_ptr(), row_o.data_ptr<int64_t>(),
+                                         col_o.data_ptr<int64_t>(), e_id.data_ptr<int64_t>(), stream),
+                 "tsamd_ego_induced_write");
+  Tensor out_rowptr = torch::empty({D + 1}, iopt);
+  check_status(tsamd_ind2ptr(row_o.data_ptr<int64_t>(), D, K, out_rowptr.data_ptr<int64_t>(), stream), "tsamd_ind2ptr");
+  return std::make_tuple(out_rowptr, col_o, n_id, e_id, ptr, root_n_id);
+}
 
 }  // namespace
 }  // namespace tsamd_ops
@@ -818,4 +935,5 @@ static auto registry_sample = torch::RegisterOperators()
                            .op("torch_sparse::saint_subgraph", &saint_subgraph)
                            .op("torch_sparse::neighbor_sample", &neighbor_sample)
                            .op("torch_sparse::hetero_neighbor_sample", &hetero_neighbor_sample)
-                           .op("torch_sparse::hetero_temporal_neighbor_sample", &hetero_temporal_neighbor_sample);
+                           .op("torch_sparse::hetero_temporal_neighbor_sample", &hetero_temporal_neighbor_sample)
+                           .op("torch_sparse::ego_k_hop_sample_adj", &ego_k_hop_sample_adj);

@@ -23,6 +23,7 @@
 //     capacity buffer and its length is a DEVICE counter -- a relation's relabel costs neither the
 //     M x 8-byte fill nor the re-seeding of everything sampled so far, and no host read-back.
 #include "common.h"
+#include "expand.h"
 #include "scan.h"
 
 namespace tsamd {
@@ -399,6 +400,220 @@ __global__ void assoc_kernel(const int64_t *__restrict__ idx, int64_t n, int64_t
   atomicMax(reinterpret_cast<long long *>(&assoc[v]), (long long)i);  // duplicates: last position wins
 }
 
+// ---- ego sub-graphs (ego_k_hop_sample_adj, csrc/cpu/ego_sample_cpu.cpp) -------------------------------------------
+// Every seed g grows its own node set S_g; the pairs (g, node) of the seeds and of all draws are made distinct by the
+// index-only sort-coalesce (csrc/sort.hip), which leaves n_id sorted by (g, node) = the reference's std::set order.
+// Ids outside [0, M) are counted in *err and replaced by 0, so that nothing downstream reads out of bounds.
+
+__device__ inline int64_t ego_checked(int64_t w, int64_t M, unsigned long long *err) {
+  if (w >= 0 && w < M) return w;
+  atomicAdd(err, 1ull);
+  return 0;
+}
+
+// the pairs (g, idx[g]) the node sets start from
+__global__ void ego_seeds_kernel(const int64_t *__restrict__ idx, int64_t n, int64_t M, int64_t *__restrict__ seg_out,
+                                 int64_t *__restrict__ node_out, unsigned long long *err) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  seg_out[g] = g;
+  node_out[g] = ego_checked(idx[g], M, err);
+}
+
+// cnt[i] = draws of frontier entry i: the whole row when deg <= k, else k (both replace modes); nothing when k < 0
+__global__ void ego_count_kernel(const int64_t *__restrict__ rowptr, int64_t M, const int64_t *__restrict__ frontier,
+                                 int64_t F, int64_t k, int64_t *__restrict__ cnt, unsigned long long *err) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= F) return;
+  const int64_t v = frontier[i];
+  if (v < 0 || v >= M) {
+    atomicAdd(err, 1ull);
+    cnt[i] = 0;
+    return;
+  }
+  const int64_t deg = rowptr[v + 1] - rowptr[v];
+  cnt[i] = k < 0 ? 0 : (deg <= k ? deg : k);
+}
+
+// one lane per DRAW t (not per (row, j): k may be far larger than any degree): its frontier entry by a binary search in
+// out_ptr; the draw itself is sample_draw_kernel's, keyed by (seed, frontier position, j)
+__global__ void ego_draw_kernel(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M,
+                                const int64_t *__restrict__ frontier, const int64_t *__restrict__ fseg, int64_t F,
+                                int64_t k, int replace, uint64_t seed, const int64_t *__restrict__ out_ptr, int64_t T,
+                                int64_t *__restrict__ nbr, int64_t *__restrict__ seg_out, unsigned long long *err) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const int64_t i = segment_of(out_ptr, F, t);
+  const int64_t o = out_ptr[i], j = t - o;
+  const int64_t v = frontier[i], g = fseg[i];
+  const int64_t s = rowptr[v], deg = rowptr[v + 1] - s;
+  int64_t p;
+  if (deg <= k) {
+    p = j;  // the whole row, in stored order (also with replacement, ego_sample_cpu.cpp:49-55)
+  } else if (replace) {
+    const U4 r = philox(seed, (uint64_t)i, (uint32_t)j, 0xD4A3u ^ (uint32_t)((uint64_t)j >> 32));
+    p = (int64_t)__umul64hi(u64(r.x, r.y), (uint64_t)deg);
+  } else if (deg <= 64) {
+    // Floyd's algorithm over a 64-bit mask, done by the lane of draw 0 (k < deg <= 64 steps)
+    if (j != 0) return;
+    uint64_t used = 0;
+    int64_t c = 0;
+    for (int64_t q = deg - k; q < deg; ++q) {
+      const U4 r = philox(seed, (uint64_t)i, (uint32_t)q, 0xF10Du);
+      const uint64_t pick0 = __umul64hi(u64(r.x, r.y), (uint64_t)(q + 1));
+      const uint64_t pick = ((used >> pick0) & 1ull) ? (uint64_t)q : pick0;
+      used |= 1ull << pick;
+      nbr[o + c] = ego_checked(col[s + (int64_t)pick], M, err);
+      seg_out[o + c] = g;
+      ++c;
+    }
+    return;
+  } else {
+    p = (int64_t)permute_index((uint64_t)j, (uint64_t)deg, seed, (uint64_t)i);
+  }
+  nbr[t] = ego_checked(col[s + p], M, err);
+  seg_out[t] = g;
+}
+
+// first position in n_id[a, b) (ascending) that is not below w
+__device__ inline int64_t lower_bound_ids(const int64_t *__restrict__ n_id, int64_t a, int64_t b, int64_t w) {
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (n_id[mid] < w) a = mid + 1;
+    else b = mid;
+  }
+  return a;
+}
+
+__global__ void ego_roots_kernel(const int64_t *__restrict__ idx, int64_t n, const int64_t *__restrict__ ptr,
+                                 const int64_t *__restrict__ n_id, int64_t *__restrict__ root) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  root[g] = lower_bound_ids(n_id, ptr[g], ptr[g + 1], idx[g]);
+}
+
+// The induced sub-graphs, parallel over the V VIRTUAL entries = every stored entry of every row of n_id, in
+// (g, v ascending, e ascending) order -- the reference's output order (ego_sample_cpu.cpp:92-104).  A workgroup owns a
+// tile of kExpandTile consecutive virtual entries: the rows that intersect it (their vptr offsets and row starts) are
+// staged in LDS as in select_fill_kernel, so a hub row that appears in many node sets is spread over many workgroups.
+// Each entry reads w = col[e] and binary-searches w in the sorted node set of its own seed.
+constexpr int kEgoSlices = kExpandTile / 256;
+
+struct EgoTile {
+  int64_t lo, n;  // the rows [lo, lo + n) intersect the tile
+  bool staged;
+};
+
+__device__ inline EgoTile ego_stage(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ n_id,
+                                    const int64_t *__restrict__ vptr, int64_t D, int64_t e0, int64_t e1, int64_t *so,
+                                    int64_t *ss, int64_t *span) {
+  int64_t lo, hi;
+  tile_span(vptr, D, e0, e1, span, &lo, &hi);
+  EgoTile t;
+  t.lo = lo;
+  t.n = hi - lo + 1;
+  t.staged = t.n <= kExpandTile;
+  if (t.staged) {
+    for (int i = threadIdx.x; i < (int)t.n; i += blockDim.x) {
+      so[i] = vptr[lo + i];
+      ss[i] = rowptr[n_id[lo + i]];
+    }
+  }
+  __syncthreads();
+  return t;
+}
+
+// virtual entry e -> (output row r = its position in n_id, output column c = global position of its column in n_id,
+// src = its position in col); true when the column belongs to the seed's node set
+__device__ inline bool ego_member(const EgoTile &t, const int64_t *so, const int64_t *ss,
+                                  const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M,
+                                  const int64_t *__restrict__ n_id, const int64_t *__restrict__ n_seg,
+                                  const int64_t *__restrict__ ptr, const int64_t *__restrict__ vptr, int64_t D,
+                                  int64_t e, int64_t *r, int64_t *c, int64_t *src, unsigned long long *err) {
+  int64_t i;
+  if (t.staged) {
+    const int q = segment_of_lds(so, (int)t.n, e);
+    i = t.lo + q;
+    *src = ss[q] + (e - so[q]);
+  } else {  // long runs of rows without entries: search the global offsets in place
+    i = t.lo + segment_of(vptr + t.lo, t.n, e);
+    *src = rowptr[n_id[i]] + (e - vptr[i]);
+  }
+  *r = i;
+  const int64_t w = col[*src];
+  if (w < 0 || w >= M) {
+    if (err) atomicAdd(err, 1ull);
+    return false;
+  }
+  const int64_t g = n_seg[i], b = ptr[g + 1];
+  const int64_t a = lower_bound_ids(n_id, ptr[g], b, w);
+  *c = a;
+  return a < b && n_id[a] == w;
+}
+
+__global__ __launch_bounds__(256) void ego_induced_count_kernel(
+    const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M, const int64_t *__restrict__ n_id,
+    const int64_t *__restrict__ n_seg, int64_t D, const int64_t *__restrict__ ptr, const int64_t *__restrict__ vptr,
+    int64_t V, int64_t *__restrict__ tile_cnt, unsigned long long *err) {
+  __shared__ int64_t so[kExpandTile];
+  __shared__ int64_t ss[kExpandTile];
+  __shared__ int64_t span[2];
+  __shared__ int wsum[4];
+  const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
+  const int64_t e1 = e0 + kExpandTile < V ? e0 + kExpandTile : V;
+  const EgoTile t = ego_stage(rowptr, n_id, vptr, D, e0, e1, so, ss, span);
+  int cnt = 0;
+  for (int j = 0; j < kEgoSlices; ++j) {
+    const int64_t e = e0 + (int64_t)j * 256 + threadIdx.x;
+    int64_t r, c, src;
+    const bool keep = e < e1 && ego_member(t, so, ss, rowptr, col, M, n_id, n_seg, ptr, vptr, D, e, &r, &c, &src, err);
+    cnt += __popcll(__ballot(keep));  // wave-uniform
+  }
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (int64_t)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// the same membership test again; the kept entries of a tile go to tile_off[tile] + their rank inside the tile, in
+// virtual-entry order (a stable compaction)
+__global__ __launch_bounds__(256) void ego_induced_write_kernel(
+    const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M, const int64_t *__restrict__ n_id,
+    const int64_t *__restrict__ n_seg, int64_t D, const int64_t *__restrict__ ptr, const int64_t *__restrict__ vptr,
+    int64_t V, const int64_t *__restrict__ tile_off, int64_t *__restrict__ row_out, int64_t *__restrict__ col_out,
+    int64_t *__restrict__ e_id_out) {
+  __shared__ int64_t so[kExpandTile];
+  __shared__ int64_t ss[kExpandTile];
+  __shared__ int64_t span[2];
+  __shared__ int wcnt[2][4];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
+  const int64_t e1 = e0 + kExpandTile < V ? e0 + kExpandTile : V;
+  const EgoTile t = ego_stage(rowptr, n_id, vptr, D, e0, e1, so, ss, span);
+  int64_t run = tile_off[blockIdx.x];
+  for (int j = 0; j < kEgoSlices; ++j) {
+    const int64_t e = e0 + (int64_t)j * 256 + threadIdx.x;
+    int64_t r = 0, c = 0, src = 0;
+    const bool keep = e < e1 && ego_member(t, so, ss, rowptr, col, M, n_id, n_seg, ptr, vptr, D, e, &r, &c, &src, nullptr);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wcnt[j & 1][wave] = __popcll(m);
+    __syncthreads();  // (double-buffered counts: the buffer written here was last read before the previous barrier)
+    int wbase = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int cw = wcnt[j & 1][w];
+      wbase += w < wave ? cw : 0;
+      total += cw;
+    }
+    if (keep) {
+      const int64_t p = run + wbase + __popcll(m & ((1ull << lane) - 1ull));
+      row_out[p] = r;
+      col_out[p] = c;
+      e_id_out[p] = src;
+    }
+    run += total;
+  }
+}
+
 }  // namespace
 }  // namespace tsamd
 
@@ -689,5 +904,103 @@ extern "C" int tsamd_subset_assoc(const int64_t *idx, int64_t n, int64_t M, int6
                        M, assoc, reinterpret_cast<unsigned long long *>(err));
     TSAMD_LAUNCH_CHECK();
   }
+  return TSAMD_OK;
+}
+
+// ---- ego sub-graphs ------------------------------------------------------------------------------------------------
+extern "C" int tsamd_ego_seeds(const int64_t *idx, int64_t n, int64_t M, int64_t *seg_out, int64_t *node_out,
+                               int64_t *err, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (n < 0 || M < 0 || !err || (n > 0 && (!idx || !seg_out || !node_out))) return TSAMD_ERR_INVALID;
+  if (n == 0) return TSAMD_OK;
+  hipLaunchKernelGGL(ego_seeds_kernel, dim3((unsigned int)ceil_div(n, 256)), dim3(256), 0, stream, idx, n, M, seg_out,
+                     node_out, reinterpret_cast<unsigned long long *>(err));
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+extern "C" size_t tsamd_ego_plan_workspace_bytes(int64_t F) { return scan_workspace_bytes(F + 1); }
+
+extern "C" int tsamd_ego_plan(const int64_t *rowptr, int64_t M, const int64_t *frontier, int64_t F,
+                              int64_t num_neighbors, int64_t *out_ptr, int64_t *total, int64_t *err, void *workspace,
+                              size_t workspace_bytes, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || F < 0 || !rowptr || !out_ptr || !total || !err || (F > 0 && !frontier)) return TSAMD_ERR_INVALID;
+  if (!workspace || workspace_bytes < tsamd_ego_plan_workspace_bytes(F)) return TSAMD_ERR_WORKSPACE;
+  TSAMD_HIP_TRY(hipMemsetAsync(out_ptr + F, 0, sizeof(int64_t), stream));
+  if (F > 0) {
+    hipLaunchKernelGGL(ego_count_kernel, dim3((unsigned int)ceil_div(F, 256)), dim3(256), 0, stream, rowptr, M, frontier,
+                       F, num_neighbors, out_ptr, reinterpret_cast<unsigned long long *>(err));
+    TSAMD_LAUNCH_CHECK();
+  }
+  return exclusive_scan_i64(out_ptr, out_ptr, F + 1, total, workspace, stream);
+}
+
+extern "C" int tsamd_ego_draw(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *frontier,
+                              const int64_t *fseg, int64_t F, int64_t num_neighbors, int replace, uint64_t seed,
+                              const int64_t *out_ptr, int64_t T, int64_t *nbr, int64_t *seg_out, int64_t *err,
+                              void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || F < 0 || T < 0) return TSAMD_ERR_INVALID;
+  if (T == 0) return TSAMD_OK;
+  if (F == 0 || num_neighbors <= 0 || !rowptr || !col || !frontier || !fseg || !out_ptr || !nbr || !seg_out || !err)
+    return TSAMD_ERR_INVALID;
+  hipLaunchKernelGGL(ego_draw_kernel, dim3((unsigned int)ceil_div(T, 256)), dim3(256), 0, stream, rowptr, col, M,
+                     frontier, fseg, F, num_neighbors, replace, seed, out_ptr, T, nbr, seg_out,
+                     reinterpret_cast<unsigned long long *>(err));
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+extern "C" int tsamd_ego_roots(const int64_t *idx, int64_t n, const int64_t *ptr, const int64_t *n_id, int64_t *root_n_id,
+                               void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (n < 0) return TSAMD_ERR_INVALID;
+  if (n == 0) return TSAMD_OK;
+  if (!idx || !ptr || !n_id || !root_n_id) return TSAMD_ERR_INVALID;
+  hipLaunchKernelGGL(ego_roots_kernel, dim3((unsigned int)ceil_div(n, 256)), dim3(256), 0, stream, idx, n, ptr, n_id,
+                     root_n_id);
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+extern "C" size_t tsamd_ego_induced_workspace_bytes(int64_t V) {
+  const int64_t tiles = ceil_div(V > 0 ? V : 1, (int64_t)kExpandTile);
+  return align_up(sizeof(int64_t) * (size_t)(tiles + 1), 256) + scan_workspace_bytes(tiles + 1);
+}
+
+extern "C" int tsamd_ego_induced_count(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *n_id,
+                                       const int64_t *n_seg, int64_t D, const int64_t *ptr, const int64_t *vptr,
+                                       int64_t V, int64_t *count, int64_t *err, void *workspace,
+                                       size_t workspace_bytes, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || D < 0 || V < 0 || !count || !err) return TSAMD_ERR_INVALID;
+  if (V > 0 && (D == 0 || !rowptr || !col || !n_id || !n_seg || !ptr || !vptr)) return TSAMD_ERR_INVALID;
+  if (!workspace || workspace_bytes < tsamd_ego_induced_workspace_bytes(V)) return TSAMD_ERR_WORKSPACE;
+  const int64_t tiles = V > 0 ? ceil_div(V, (int64_t)kExpandTile) : 0;
+  int64_t *tile_off = reinterpret_cast<int64_t *>(workspace);
+  void *scan_ws = reinterpret_cast<char *>(workspace) + align_up(sizeof(int64_t) * (size_t)(tiles + 1), 256);
+  TSAMD_HIP_TRY(hipMemsetAsync(tile_off + tiles, 0, sizeof(int64_t), stream));
+  if (tiles > 0) {
+    hipLaunchKernelGGL(ego_induced_count_kernel, dim3((unsigned int)tiles), dim3(256), 0, stream, rowptr, col, M, n_id,
+                       n_seg, D, ptr, vptr, V, tile_off, reinterpret_cast<unsigned long long *>(err));
+    TSAMD_LAUNCH_CHECK();
+  }
+  return exclusive_scan_i64(tile_off, tile_off, tiles + 1, count, scan_ws, stream);
+}
+
+extern "C" int tsamd_ego_induced_write(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *n_id,
+                                       const int64_t *n_seg, int64_t D, const int64_t *ptr, const int64_t *vptr,
+                                       int64_t V, const void *workspace, int64_t *row_out, int64_t *col_out,
+                                       int64_t *e_id_out, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || D < 0 || V < 0 || !workspace) return TSAMD_ERR_INVALID;
+  if (V == 0) return TSAMD_OK;
+  if (D == 0 || !rowptr || !col || !n_id || !n_seg || !ptr || !vptr || !row_out || !col_out || !e_id_out)
+    return TSAMD_ERR_INVALID;
+  const int64_t tiles = ceil_div(V, (int64_t)kExpandTile);
+  hipLaunchKernelGGL(ego_induced_write_kernel, dim3((unsigned int)tiles), dim3(256), 0, stream, rowptr, col, M, n_id,
+                     n_seg, D, ptr, vptr, V, reinterpret_cast<const int64_t *>(workspace), row_out, col_out, e_id_out);
+  TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
 }
