@@ -26,8 +26,6 @@ ARCH = 'gfx950'
 HIP_SOURCES = ['api.hip', 'spmm.hip', 'spmm_min.hip', 'spmm_max.hip', 'spmm_partial.hip', 'spmm_bw.hip', 'spmm_ref_order.hip', 'spmm_coo.hip', 'convert.hip', 'scan.hip', 'sort.hip',
                'coalesce.hip', 'spspmm.hip', 'select.hip', 'sample.hip', 'segreduce.hip']
 OPS_SOURCES = ['ops_spmm.cpp', 'ops_storage.cpp', 'ops_sample.cpp']
-# translation units that #include another .hip file (rebuilt when that one changes)
-HIP_INCLUDES = {'spmm_partial.hip': ['spmm.hip'], 'spmm_min.hip': ['spmm.hip'], 'spmm_max.hip': ['spmm.hip']}
 
 
 def _hipcc():
@@ -79,7 +77,7 @@ def build_kernels(verbose=True, force=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJDIR, src + '.o')
         objs.append(o)
-        deps = [s] + headers + [os.path.join(CSRC, d) for d in HIP_INCLUDES.get(src, [])]
+        deps = [s] + headers
         if force or _newer(o, deps):
             jobs.append([hipcc] + flags + ['-c', s, '-o', o])
     if jobs:

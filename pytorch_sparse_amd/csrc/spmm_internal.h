@@ -7,8 +7,15 @@
 
 namespace tsamd {
 
+// One SpMM call and its carved workspace (csrc/spmm_kernels.h), and the launchers of the min / max instantiations
+// (csrc/spmm_min.hip, csrc/spmm_max.hip) that the entry points of csrc/spmm.hip call.
+struct SpmmCall;
+struct Workspace;
+int spmm_launch_min(int vec, const SpmmCall &c, const Workspace &ws);
+int spmm_launch_max(int vec, const SpmmCall &c, const Workspace &ws);
+
 // Winner records of the pull-formulated min/max backward (csrc/spmm_bw.hip writes them, the masked
-// merge kernel of csrc/spmm.hip and the masked SDDMM read them).  One record per (batch, CSR entry e),
+// merge kernel of csrc/spmm_kernels.h and the masked SDDMM read them).  One record per (batch, CSR entry e),
 // `win_record_stride(K)` 32-bit words, 16-byte aligned:
 //   words [0, W)   W = ceil(K / 32): bit (k % 32) of word k / 32 = (arg_out[b, row(e), k] == e)
 //   word  W        row(e)                       (the "column" of e in the transposed product)
@@ -23,7 +30,7 @@ static inline uint32_t win_record_stride(int64_t K) {
 }
 
 // out[b, m, k] = sum over the entries i of row m of the pattern `rowptr` (entry i is record perm[i], perm
-// may be NULL) whose bit k is set of round_T(value * mat[b, id, k]) -- the merge-path SpMM of csrc/spmm.hip
+// may be NULL) whose bit k is set of round_T(value * mat[b, id, k]) -- the merge-path SpMM of csrc/spmm_kernels.h
 // with a per-(entry, feature) predicate; E < 2^32.  Workspace as for tsamd_spmm (SUM).
 size_t spmm_masked_sum_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E);
 int spmm_masked_sum(int dtype, const int64_t *rowptr, bool has_value, const int64_t *perm,

@@ -1,5 +1,7 @@
-// The min instantiations of the SpMM kernels of spmm.hip (and their int32-id variants), reached from the main unit through
-// tsamd::spmm_min_bridge: a separate translation unit only so that the pieces compile in parallel (spmm.hip alone took
-// 176 s -- the longest step of build(); now 39 + 66 + 66 s side by side).  No entry point is defined here.
-#define TSAMD_SPMM_TU 2
-#include "spmm.hip"
+// The min instantiations of the SpMM kernels (and their int32-id variants); see the top of spmm_kernels.h.
+#define TSAMD_SPMM_PARTIAL_BUILD 0
+#include "spmm_kernels.h"
+
+int tsamd::spmm_launch_min(int vec, const SpmmCall &c, const Workspace &ws) {
+  return TSAMD_DISPATCH_DTYPE_ALL(c.dtype, [&]() -> int { return dispatch_spmm<scalar_t, RED_MIN>(vec, c, ws); });
+}

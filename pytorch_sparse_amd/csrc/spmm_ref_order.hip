@@ -1,6 +1,6 @@
 // SpMM in the REFERENCE'S ORDER OF OPERATIONS -- a verification mode, not a fast path.
 //
-// The product kernels (csrc/spmm.hip) cut rows between waves and add partial sums in a tree: their fp32 sums differ
+// The product kernels (csrc/spmm_kernels.h) cut rows between waves and add partial sums in a tree: their fp32 sums differ
 // from the reference CPU kernel's in the last bits (inside 1e-5 * sum|terms|, tests/ and bench.py count it), because
 // that kernel (csrc/cpu/spmm_cpu.cpp:61-87 with csrc/cpu/reducer.h:43-84) walks a row's entries one after the other,
 // multiplies, rounds, adds, rounds.  This kernel does exactly that -- one thread per (batch, row, feature), entries in
