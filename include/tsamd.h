@@ -705,6 +705,30 @@ int tsamd_set_diag_apply(const int64_t *pos, const int64_t *row, const int64_t *
  *                       (device) = number of entries whose column lies in the node set of the row's seed n_seg[i];
  *                       _write (same inputs, the workspace of _count): for those, in virtual-entry order, row_out = i,
  *                       col_out = position of the column in n_id, e_id_out = e.  ind2ptr(row_out, D) = the rowptr.
+ *
+ * hgt_sample (csrc/cpu/hgt_sample_cpu.cpp, CPU-only in the reference): HGT budget sampling.  Per node type ONE 64-bit
+ * word per id, alive for the whole call: 0 = untouched, all-ones = seen (listed), anything else = the budget in fixed
+ * point (units of 2^-32), and a list of the ids that ever received budget (the candidates).  See csrc/hgt_sample.hip.
+ *   tsamd_hgt_seen        word[ids[i]] = seen; *err (device, the caller zeroes it) += #ids outside [0, M).
+ *   tsamd_hgt_budget_add  out_ptr[F + 1] / nbr = a tsamd_sample_plan / _draw pair with num_neighbors =
+ *                         TSAMD_HGT_MAX_NEIGHBORS, replace = 0 over the new nodes of the destination type.  Every draw
+ *                         of a column with c draws adds floor(2^32 / c) to the word of its source unless that is seen
+ *                         (one integer atomic: the sums do not depend on the order of arrival); a source whose word was
+ *                         0 is appended to cand (order arbitrary).  state[0] (device) = length of cand, state[1] +=
+ *                         #ids outside [0, M) + appends beyond `capacity`.
+ *   tsamd_hgt_select      k <= #live candidates draws WITHOUT replacement, sequentially proportional to budget^2, as an
+ *                         exponential race: key = -log(u) / budget^2, u = Philox(seed, id, hop, type_tag) in (0, 1], the
+ *                         k smallest (key as float32, then id) win: out[k] in ascending key order, their words turn
+ *                         seen.  Candidates that are seen already (drawn earlier) take no part.  A pure function of
+ *                         (seed, hop, type_tag) and the words, whatever the order of cand.  *err += winners asked for
+ *                         beyond the live candidates (their out entry is -1).
+ *   tsamd_hgt_keys / tsamd_hgt_commit   the two halves of tsamd_hgt_select around its sort, for a caller that sorts the
+ *                         candidates of SEVERAL types at once: _keys writes key[C] = (type_tag << 32) | float32 bits of
+ *                         the race key (all-ones for a dead entry) and id[C]; after ONE tsamd_sort_coo of the
+ *                         concatenated (key, id) arrays with M = (largest tag + 1) << 32, N = largest id space, type
+ *                         t's segment starts at the sum of the C of the types with a smaller tag; _commit takes the
+ *                         first k entries of that segment (*err += entries that are dead or not of type_tag).  type_tag < 2^16.
+ *   tsamd_hgt_check_ids   ids outside [0, M) are counted in *err and replaced by 0 (before a dense array is indexed).
  * ------------------------------------------------------------------------ */
 int tsamd_random_walk(const int64_t *rowptr, const int64_t *col, const int64_t *start,
                       const float *rand, int64_t n, int64_t walk_length, int64_t *out,
@@ -762,6 +786,19 @@ int tsamd_ego_induced_count(const int64_t *rowptr, const int64_t *col, int64_t M
 int tsamd_ego_induced_write(const int64_t *rowptr, const int64_t *col, int64_t M, const int64_t *n_id,
                             const int64_t *n_seg, int64_t D, const int64_t *ptr, const int64_t *vptr, int64_t V,
                             const void *workspace, int64_t *row_out, int64_t *col_out, int64_t *e_id_out, void *stream);
+#define TSAMD_HGT_MAX_NEIGHBORS 50
+int tsamd_hgt_seen(const int64_t *ids, int64_t n, int64_t M, uint64_t *word, int64_t *err, void *stream);
+int tsamd_hgt_budget_add(const int64_t *out_ptr, int64_t F, const int64_t *nbr, int64_t M, uint64_t *word,
+                         int64_t *cand, int64_t capacity, int64_t *state, void *stream);
+size_t tsamd_hgt_select_workspace_bytes(int64_t C);
+int tsamd_hgt_select(const int64_t *cand, int64_t C, uint64_t *word, int64_t M, int64_t k, uint64_t seed,
+                     int64_t hop, int64_t type_tag, int64_t *out, int64_t *err, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int tsamd_hgt_keys(const int64_t *cand, int64_t C, const uint64_t *word, int64_t M, uint64_t seed, int64_t hop,
+                   int64_t type_tag, int64_t *key, int64_t *id, void *stream);
+int tsamd_hgt_commit(const int64_t *key_sorted, const int64_t *id_sorted, int64_t k, uint64_t *word, int64_t M,
+                     int64_t type_tag, int64_t *out, int64_t *err, void *stream);
+int tsamd_hgt_check_ids(int64_t *ids, int64_t n, int64_t M, int64_t *err, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ and, widening along SURVEY.md section 8f (the callers either side of that path):
     narrow, select, index_select(_nnz), masked_select(_nnz), permute, cat, SparseTensor.__getitem__,
     sample, sample_adj, random_walk, saint_subgraph, reverse_cuthill_mckee, eye, spadd, converters
     torch.ops.torch_sparse.{non_diag_mask, sample_adj, neighbor_sample, random_walk, saint_subgraph,
-                            relabel, relabel_one_hop, ego_k_hop_sample_adj}
+                            relabel, relabel_one_hop, ego_k_hop_sample_adj, hgt_sample}
 
 Everything computes in hand-written HIP kernels (``lib/libtsamd.so``, C-ABI in ``include/tsamd.h``)
 reached through the torch operator library ``lib/_tsamd_ops.so``.  There is no CPU compute path:

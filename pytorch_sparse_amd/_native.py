@@ -43,6 +43,8 @@ SYMBOLS = [
     'tsamd_temporal_relabel_workspace_bytes', 'tsamd_temporal_relabel', 'tsamd_temporal_emit', 'tsamd_subset_assoc',
     'tsamd_ego_seeds', 'tsamd_ego_plan_workspace_bytes', 'tsamd_ego_plan', 'tsamd_ego_draw', 'tsamd_ego_roots',
     'tsamd_ego_induced_workspace_bytes', 'tsamd_ego_induced_count', 'tsamd_ego_induced_write',
+    'tsamd_hgt_seen', 'tsamd_hgt_budget_add', 'tsamd_hgt_select_workspace_bytes', 'tsamd_hgt_select', 'tsamd_hgt_keys',
+    'tsamd_hgt_commit', 'tsamd_hgt_check_ids',
 ]
 
 DTYPES = {

@@ -921,6 +921,277 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ego_k_hop_sample_adj(
   return std::make_tuple(out_rowptr, col_o, n_id, e_id, ptr, root_n_id);
 }
 
+// ---- HGT budget sampling (csrc/cpu/hgt_sample_cpu.cpp) ----------------------------------------------------------------
+edge_t split_relation(const rel_t &rel) {
+  std::vector<std::string> parts;
+  size_t start = 0;
+  for (;;) {
+    const size_t end = rel.find("__", start);
+    parts.push_back(rel.substr(start, end == std::string::npos ? std::string::npos : end - start));
+    if (end == std::string::npos) break;
+    start = end + 2;
+  }
+  TORCH_CHECK(parts.size() == 3, "hgt_sample: relation key '", rel, "' is not of the form src__rel__dst");
+  return std::make_tuple(parts[0], parts[1], parts[2]);
+}
+
+// what one node type carries through a call of hgt_sample (csrc/hgt_sample.hip): the dense budget / seen words, the
+// candidate list, and the node list as one tensor per block (the inputs, then what every hop drew)
+struct HgtType {
+  Tensor word, cand;
+  int64_t M = 0, tag = 0;
+  int64_t C = 0;      // length of the candidate list as of the last read-back
+  int64_t drawn = 0;  // candidates drawn so far (dead entries of the list)
+  std::vector<Tensor> blocks;
+  Tensor fresh;  // the newest block: what the next budget update expands
+  Tensor nodes;  // the final list
+};
+
+// torch_sparse::hgt_sample(Dict(str, Tensor) colptr_dict, Dict(str, Tensor) row_dict, Dict(str, Tensor) input_node_dict,
+//     Dict(str, int[]) num_samples_dict, int num_hops)
+//     -> (Dict(str, Tensor) node, Dict(str, Tensor) row, Dict(str, Tensor) col, Dict(str, Tensor) edge)
+// (reference schema, csrc/hgt_sample.cpp; CPU-only there).  The node types are the keys of num_samples_dict, the
+// relations those of colptr_dict (src__rel__dst, one CSC each).  Every type keeps a budget over its unseen nodes: a
+// newly listed node w adds 1 / min(deg, 50) to every unseen source of its column (50 uniform entries of a longer
+// column), per relation into w's type; a hop draws num_samples[t][hop] nodes of every type without replacement,
+// sequentially proportional to budget^2, and expands them.  The edges are those of the (at most 50 per column)
+// entries of the final lists' columns whose source is listed.  What the random draws do not decide is the reference's
+// result; docs/design/widening.md lists the divergences.  Host read-backs: 3 + num_hops (the set-up's id maxima, one
+// per budget update, two for the edges), whatever the number of types, relations, inputs and samples.
+std::tuple<TensorDict, TensorDict, TensorDict, TensorDict> hgt_sample(
+    const TensorDict &colptr_dict, const TensorDict &row_dict, const TensorDict &input_node_dict,
+    const c10::Dict<node_t, std::vector<int64_t>> &num_samples_dict, int64_t num_hops) {
+  std::vector<node_t> node_types;
+  for (const auto &kv : num_samples_dict) {
+    node_types.push_back(kv.key());
+    TORCH_CHECK((int64_t)kv.value().size() >= num_hops, "num_samples_dict[", kv.key(), "] has fewer than num_hops entries");
+    for (int64_t ell = 0; ell < num_hops; ++ell)
+      TORCH_CHECK(kv.value()[ell] >= 0, "num_samples_dict[", kv.key(), "] has a negative entry");
+  }
+  std::sort(node_types.begin(), node_types.end());
+  std::vector<rel_t> rels;  // ascending key order: the order of the draws' seeds
+  std::vector<edge_t> edge_types;
+  for (const auto &kv : colptr_dict) rels.push_back(kv.key());
+  std::sort(rels.begin(), rels.end());
+  for (const auto &rel : rels) {
+    const edge_t et = split_relation(rel);
+    TORCH_CHECK(num_samples_dict.contains(std::get<0>(et)), "hgt_sample: unknown node type ", std::get<0>(et), " in ", rel);
+    TORCH_CHECK(num_samples_dict.contains(std::get<2>(et)), "hgt_sample: unknown node type ", std::get<2>(et), " in ", rel);
+    TORCH_CHECK(row_dict.contains(rel), "hgt_sample: row_dict has no entry ", rel);
+    edge_types.push_back(et);
+  }
+  for (const auto &kv : input_node_dict)
+    TORCH_CHECK(num_samples_dict.contains(kv.key()), "hgt_sample: unknown node type ", kv.key(), " in input_node_dict");
+  // id space of every type: one read-back, the relations' maxima remembered per graph (hetero_setup)
+  HeteroSetup hs = hetero_setup(node_types, edge_types, colptr_dict, row_dict, input_node_dict, num_samples_dict);
+  c10::hip::HIPGuard guard(hs.any.get_device());
+  auto iopt = hs.any.options().requires_grad(false);
+  void *stream = current_stream(hs.any);
+  const int64_t kCap = TSAMD_HGT_MAX_NEIGHBORS;
+
+  // device words, two per type: (length of the candidate list, #bad ids and other errors)
+  Tensor state = torch::zeros({2 * (int64_t)node_types.size()}, iopt);
+  std::map<node_t, HgtType> types;
+  for (size_t i = 0; i < node_types.size(); ++i) {
+    HgtType &ty = types[node_types[i]];
+    ty.M = hs.num_nodes.at(node_types[i]);
+    ty.tag = (int64_t)i;
+    ty.word = torch::zeros({ty.M}, iopt);
+    ty.cand = torch::empty({ty.M}, iopt);
+    ty.fresh = input_node_dict.contains(node_types[i]) ? input_node_dict.at(node_types[i]).contiguous() : torch::empty({0}, iopt);
+    if (ty.fresh.numel() > 0) ty.blocks.push_back(ty.fresh);
+  }
+  auto words = [&](HgtType &ty) { return reinterpret_cast<uint64_t *>(ty.word.data_ptr<int64_t>()); };
+  auto st = [&](HgtType &ty) { return state.data_ptr<int64_t>() + 2 * ty.tag; };
+  auto check_state = [&](const int64_t *h) {
+    for (const auto &t : node_types) {
+      HgtType &ty = types.at(t);
+      TORCH_CHECK_INDEX(h[2 * ty.tag + 1] == 0, "index out of range: ", h[2 * ty.tag + 1], " node ids of type ", t,
+                        " are outside [0, ", ty.M, ")");
+      ty.C = h[2 * ty.tag];
+    }
+  };
+  auto check_plans = [&](const std::vector<Drawn> &plans, const int64_t *h) {
+    for (size_t i = 0; i < plans.size(); ++i)
+      TORCH_CHECK_INDEX(h[2 * i + 1] == 0, "index out of range: ", h[2 * i + 1], " node ids are outside [0, ",
+                        plans[i].colptr.numel() - 1, ")");
+  };
+  auto mark_seen = [&](HgtType &ty) {
+    check_status(tsamd_hgt_seen(ty.fresh.data_ptr<int64_t>(), ty.fresh.numel(), ty.M, words(ty), st(ty) + 1, stream),
+                 "tsamd_hgt_seen");
+  };
+  for (size_t r = 0; r < rels.size(); ++r)  // (an id space without ids and a non-empty row: every entry is negative)
+    TORCH_CHECK_INDEX(types.at(std::get<0>(edge_types[r])).M > 0 || row_dict.at(rels[r]).numel() == 0,
+                      "index out of range: row_dict[", rels[r], "] has negative entries only");
+  const uint64_t seed0 = host_seed();
+  uint64_t draw_no = 0;
+  // the budget update for the newest block of every type.  The draws are not sized by a read-back: a column gives at
+  // most 50, so F * 50 slots hold them and tsamd_hgt_budget_add walks the plan's segments itself; ONE transfer then
+  // brings the candidate counters, the error words and the plans' bad-id counts.
+  auto update_budget = [&]() {
+    std::vector<Drawn> plans;
+    for (size_t r = 0; r < rels.size(); ++r) {
+      HgtType &src = types.at(std::get<0>(edge_types[r])), &dst = types.at(std::get<2>(edge_types[r]));
+      ++draw_no;
+      const Tensor row = row_dict.at(rels[r]).contiguous();
+      if (dst.fresh.numel() == 0 || row.numel() == 0) continue;
+      Drawn d = plan_neighbors(colptr_dict.at(rels[r]).contiguous(), row, dst.fresh, kCap, false,
+                               seed0 + 0x9E3779B97F4A7C15ull * draw_no);
+      d.T = d.F * kCap;  // an upper bound: the slots behind the plan's total stay unused
+      draw_planned(d);
+      check_status(tsamd_hgt_budget_add(d.out_ptr.data_ptr<int64_t>(), d.F, d.nbr.data_ptr<int64_t>(), src.M, words(src),
+                                        src.cand.data_ptr<int64_t>(), src.cand.numel(), st(src), stream),
+                   "tsamd_hgt_budget_add");
+      plans.push_back(d);
+    }
+    if (plans.empty()) return;
+    std::vector<Tensor> parts;
+    for (auto &d : plans) parts.push_back(d.info);
+    parts.push_back(state);
+    const Tensor host = torch::cat(parts).cpu();  // host sync: the update's one read-back
+    check_plans(plans, host.data_ptr<int64_t>());
+    check_state(host.data_ptr<int64_t>() + 2 * plans.size());
+  };
+
+  for (const auto &t : node_types) mark_seen(types.at(t));  // every input is seen before any budget is added
+  if (num_hops > 0) update_budget();
+  // a hop's draws: the race keys of every type that draws (tsamd_hgt_keys), ONE sort of all of them -- the type tag
+  // rides on top of the key, and at mini-batch sizes a sort costs its launches, not what it moves --, then every type
+  // takes the first `take` entries of its segment (tsamd_hgt_commit).  The key takes 32 bits + the bits of the type tag
+  // above the id: when that and the bits of the largest id space exceed the sort's 64, every type sorts alone.
+  int64_t max_M = 1;
+  for (const auto &t : node_types) max_M = std::max(max_M, types.at(t).M);
+  const int64_t n_tags = (int64_t)node_types.size();
+  int key_bits = 32, id_bits = 0;
+  while (((int64_t)1 << (key_bits - 32)) < n_tags) ++key_bits;
+  while (id_bits < 63 && ((int64_t)1 << id_bits) < max_M) ++id_bits;
+  const bool one_sort = key_bits + id_bits <= 64;
+  const uint64_t select_seed = seed0 ^ 0x48475453414D504Cull;
+  for (int64_t ell = 0; ell < num_hops; ++ell) {
+    std::vector<HgtType *> drawing;
+    std::vector<int64_t> takes;
+    int64_t total_C = 0;
+    for (const auto &t : node_types) {
+      HgtType &ty = types.at(t);
+      const int64_t take = std::min<int64_t>(num_samples_dict.at(t)[ell], ty.C - ty.drawn);
+      ty.fresh = torch::empty({take}, iopt);
+      if (take == 0) continue;
+      drawing.push_back(&ty);
+      takes.push_back(take);
+      total_C += ty.C;
+    }
+    if (one_sort && drawing.size() > 1) {
+      Tensor keys = torch::empty({4, total_C}, iopt), perm = torch::empty({total_C}, iopt);  // key, id, sorted key, sorted id
+      int64_t *key = keys.data_ptr<int64_t>(), *id = key + total_C, *key_s = id + total_C, *id_s = key_s + total_C;
+      int64_t off = 0;
+      for (HgtType *ty : drawing) {  // ascending tag: the order of the segments after the sort
+        check_status(tsamd_hgt_keys(ty->cand.data_ptr<int64_t>(), ty->C, words(*ty), ty->M, select_seed, ell, ty->tag,
+                                    key + off, id + off, stream),
+                     "tsamd_hgt_keys");
+        off += ty->C;
+      }
+      Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(total_C), keys);
+      check_status(tsamd_sort_coo(key, id, total_C, n_tags << 32, max_M, key_s, id_s, perm.data_ptr<int64_t>(), ws.data_ptr(),
+                                  (size_t)ws.numel(), stream),
+                   "tsamd_sort_coo");
+      off = 0;
+      for (size_t i = 0; i < drawing.size(); ++i) {
+        HgtType *ty = drawing[i];
+        check_status(tsamd_hgt_commit(key_s + off, id_s + off, takes[i], words(*ty), ty->M, ty->tag,
+                                      ty->fresh.data_ptr<int64_t>(), st(*ty) + 1, stream),
+                     "tsamd_hgt_commit");
+        off += ty->C;
+      }
+    } else {
+      for (size_t i = 0; i < drawing.size(); ++i) {
+        HgtType *ty = drawing[i];
+        Tensor ws = workspace(tsamd_hgt_select_workspace_bytes(ty->C), ty->word);
+        check_status(tsamd_hgt_select(ty->cand.data_ptr<int64_t>(), ty->C, words(*ty), ty->M, takes[i], select_seed, ell,
+                                      ty->tag, ty->fresh.data_ptr<int64_t>(), st(*ty) + 1, ws.data_ptr(),
+                                      (size_t)ws.numel(), stream),
+                     "tsamd_hgt_select");
+      }
+    }
+    for (size_t i = 0; i < drawing.size(); ++i) {
+      drawing[i]->blocks.push_back(drawing[i]->fresh);
+      drawing[i]->drawn += takes[i];
+    }
+    if (ell < num_hops - 1) update_budget();
+  }
+
+  // the edges: per relation the (at most 50 per column) entries of the final dst list whose source is listed
+  TensorDict out_node, out_row, out_col, out_edge;
+  for (const auto &t : node_types) {
+    HgtType &ty = types.at(t);
+    ty.nodes = ty.blocks.empty() ? torch::empty({0}, iopt) : (ty.blocks.size() == 1 ? ty.blocks[0] : torch::cat(ty.blocks));
+    if (ty.nodes.numel() > 0) out_node.insert(t, ty.nodes);
+  }
+  std::vector<Drawn> plans;
+  std::vector<size_t> plan_rel;
+  for (size_t r = 0; r < rels.size(); ++r) {
+    HgtType &src = types.at(std::get<0>(edge_types[r])), &dst = types.at(std::get<2>(edge_types[r]));
+    ++draw_no;
+    const Tensor row = row_dict.at(rels[r]).contiguous();
+    if (dst.nodes.numel() == 0 || src.nodes.numel() == 0 || row.numel() == 0) continue;
+    plans.push_back(plan_neighbors(colptr_dict.at(rels[r]).contiguous(), row, dst.nodes, kCap, false,
+                                   seed0 + 0x9E3779B97F4A7C15ull * draw_no));
+    plan_rel.push_back(r);
+  }
+  read_plans(plans);  // host sync: the draws of all relations
+  std::map<node_t, Tensor> assoc;  // node -> local id, a duplicate's LAST position (the reference assigns)
+  std::vector<Tensor> segs, counts, filter_ws;
+  Tensor scratch_err = torch::empty({1}, iopt);
+  for (size_t i = 0; i < plans.size(); ++i) {
+    Drawn &d = plans[i];
+    const node_t &src_t = std::get<0>(edge_types[plan_rel[i]]);
+    HgtType &src = types.at(src_t);
+    draw_planned(d);
+    check_status(tsamd_hgt_check_ids(d.nbr.data_ptr<int64_t>(), d.T, src.M, st(src) + 1, stream), "tsamd_hgt_check_ids");
+    if (!assoc.count(src_t)) {
+      assoc[src_t] = torch::empty({src.M}, iopt);
+      check_status(tsamd_subset_assoc(src.nodes.data_ptr<int64_t>(), src.nodes.numel(), src.M,
+                                      assoc[src_t].data_ptr<int64_t>(), scratch_err.data_ptr<int64_t>(), stream),
+                   "tsamd_subset_assoc");
+    }
+    segs.push_back(segment_ids(d.out_ptr, d.F, d.T));
+    counts.push_back(torch::zeros({1}, iopt));
+    filter_ws.push_back(workspace(tsamd_filter_tiles_workspace_bytes(d.T), d.colptr));
+    check_status(tsamd_filter_count(TSAMD_KEEP_COL_MAPPED, nullptr, d.nbr.data_ptr<int64_t>(), nullptr,
+                                    assoc[src_t].data_ptr<int64_t>(), d.T, 0, 0, counts[i].data_ptr<int64_t>(),
+                                    filter_ws[i].data_ptr(), (size_t)filter_ws[i].numel(), stream),
+                 "tsamd_filter_count");
+  }
+  {
+    std::vector<Tensor> parts = counts;
+    parts.push_back(state);
+    const Tensor host = torch::cat(parts).cpu();  // host sync: the kept entries of all relations + the error words
+    check_state(host.data_ptr<int64_t>() + counts.size());
+    std::map<rel_t, size_t> plan_of;
+    for (size_t i = 0; i < plans.size(); ++i) plan_of[rels[plan_rel[i]]] = i;
+    for (const auto &kv : colptr_dict) {
+      const rel_t &rel = kv.key();
+      const int64_t kept = plan_of.count(rel) ? host.data_ptr<int64_t>()[plan_of.at(rel)] : 0;
+      Tensor r_out = torch::empty({kept}, iopt), c_out = torch::empty({kept}, iopt), e_out = torch::empty({kept}, iopt);
+      if (kept > 0) {
+        const size_t i = plan_of.at(rel);
+        Drawn &d = plans[i];
+        const Tensor &a = assoc.at(std::get<0>(edge_types[plan_rel[i]]));
+        Tensor src_pos = torch::empty({kept}, iopt);
+        check_status(tsamd_filter_write(TSAMD_KEEP_COL_MAPPED, segs[i].data_ptr<int64_t>(), d.nbr.data_ptr<int64_t>(), nullptr,
+                                        a.data_ptr<int64_t>(), d.T, 0, 0, filter_ws[i].data_ptr(), nullptr,
+                                        a.data_ptr<int64_t>(), 0, 0, c_out.data_ptr<int64_t>(), r_out.data_ptr<int64_t>(),
+                                        src_pos.data_ptr<int64_t>(), stream),
+                     "tsamd_filter_write");
+        e_out = d.e.index_select(0, src_pos);
+      }
+      out_row.insert(rel, r_out);
+      out_col.insert(rel, c_out);
+      out_edge.insert(rel, e_out);
+    }
+  }
+  return std::make_tuple(out_node, out_row, out_col, out_edge);
+}
+
 }  // namespace
 }  // namespace tsamd_ops
 
@@ -936,4 +1207,5 @@ static auto registry_sample = torch::RegisterOperators()
                            .op("torch_sparse::neighbor_sample", &neighbor_sample)
                            .op("torch_sparse::hetero_neighbor_sample", &hetero_neighbor_sample)
                            .op("torch_sparse::hetero_temporal_neighbor_sample", &hetero_temporal_neighbor_sample)
-                           .op("torch_sparse::ego_k_hop_sample_adj", &ego_k_hop_sample_adj);
+                           .op("torch_sparse::ego_k_hop_sample_adj", &ego_k_hop_sample_adj)
+                           .op("torch_sparse::hgt_sample", &hgt_sample);

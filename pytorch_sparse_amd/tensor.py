@@ -4,10 +4,10 @@ Covers construction, format views (coo/csr/csc), caches, dtype/device plumbing, 
 torch.sparse conversions, and -- attached by the sibling modules, as the reference does --
 ``matmul/spmm/spspmm/@``, ``t()``, ``coalesce()``, reductions, element-wise ``mul/add``, diagonal
 edits, ``narrow/select/index_select/masked_select/permute/[]``, ``sample/sample_adj``,
-``random_walk``, ``saint_subgraph`` and ``reverse_cuthill_mckee``.  Not provided: ``hgt_sample`` and the METIS
-partitioner; the heterogeneous / temporal neighbour samplers and ShaDow-GNN's ego sampler are
-operators (``torch.ops.torch_sparse.hetero_neighbor_sample`` / ``hetero_temporal_neighbor_sample`` /
-``ego_k_hop_sample_adj``), as in the reference.
+``random_walk``, ``saint_subgraph`` and ``reverse_cuthill_mckee``.  Not provided: the METIS
+partitioner; the heterogeneous / temporal neighbour samplers, ShaDow-GNN's ego sampler and
+HGTLoader's budget sampler are operators (``torch.ops.torch_sparse.hetero_neighbor_sample`` /
+``hetero_temporal_neighbor_sample`` / ``ego_k_hop_sample_adj`` / ``hgt_sample``), as in the reference.
 
 Like the reference's (tensor.py:12) the class is a TorchScript class: ``torch.jit.script`` functions and
 modules can take, build and return it (``matmul(adj, x, reduce)`` inside a scripted ``nn.Module``,
