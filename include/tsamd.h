@@ -510,11 +510,26 @@ int tsamd_exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, int64_t
  *   3. host: rowptrC = exclusive scan of nnzC over M + 1 entries (tsamd_exclusive_scan_i64, entry
  *        M = 0), reads nnz(C) (sync 2), allocates colC / valC at their FINAL size.
  *   4. tsamd_spspmm_numeric   every row is expanded, sorted by column (registers / LDS), its equal
- *        columns summed in product order (large rows: in atomic order, not bit-reproducible), and
+ *        columns summed in product order (large rows: in a fixed order too up to 2048 column ranges; beyond
+ *        that -- tsamd_spspmm_route: sub = 1 -- in atomic order, values not bit-reproducible), and
  *        stored at rowptrC[i].  valA / valB may be NULL (all ones); valC may be NULL (structure
  *        only).  `workspace` is the one stage 2 filled.
  * M < 2^31, N < 2^32 - 1.
+ *
+ * tsamd_spspmm_route: which kernels stages 2 and 4 take for B with N columns and values of `dtype`
+ * (host arithmetic only, no HIP call, no device needed).  out[0] = log2 of the columns per range of
+ * the large-row path; [1] = number of ranges; [2] = wave segments per (row, range) bin: 4 = the
+ * sums of the large rows are bit-reproducible run to run, 1 = bins above 1024 products are summed
+ * in atomic order (more than 2048 ranges: N > 2^24 fp32, N > 2^23 fp64); [3] = 1 when the bin
+ * kernel keeps its segment offsets in LDS, 0 = read from global memory; [4] = small rows: 0 =
+ * register sort of 32-bit (column, index) keys, 1 = one-wave radix sort of (column, value) pairs
+ * (N > 2^23); [5] = 8-bit radix passes of that sort; [6] = 1 when the symbolic hash sets use the
+ * 24-bit multiply (N <= 2^24); [7] = 1 when rows of more than 1024 products are supported (at most
+ * 8192 ranges: N <= 2^26 fp32, N <= 2^25 fp64), 0 = tsamd_spspmm_symbolic returns
+ * TSAMD_ERR_UNSUPPORTED for an operand that has such a row.  N outside [0, 2^32 - 1) or a dtype
+ * other than fp32 / fp64: TSAMD_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------ */
+int tsamd_spspmm_route(int dtype, int64_t N, int64_t out[8]);
 int tsamd_spspmm_plan(const int64_t *rowptrA, const int64_t *colA, const int64_t *rowptrB,
                       const int64_t *colB, int64_t nnzB, int64_t M, int64_t *prod, int64_t *bins,
                       uint32_t *colB32, int64_t *stats, void *stream);

@@ -31,7 +31,7 @@ SYMBOLS = [
     'tsamd_coalesce_workspace_bytes', 'tsamd_coalesce_index', 'tsamd_segment_reduce',
     'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
-    'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
+    'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
     'tsamd_select_workspace_bytes', 'tsamd_select_plan', 'tsamd_select_fill',
     'tsamd_filter_workspace_bytes', 'tsamd_filter_plan', 'tsamd_filter_apply',
     'tsamd_filter_tiles_workspace_bytes', 'tsamd_filter_count', 'tsamd_filter_write',
@@ -73,6 +73,8 @@ def lib():
         L.tsamd_hip_version.restype = ctypes.c_int64
         L.tsamd_status_string.restype = ctypes.c_char_p
         L.tsamd_spmm_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_spspmm_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_exclusive_scan_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_partial_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_csc_workspace_bytes.restype = ctypes.c_size_t

@@ -932,8 +932,9 @@ __global__ __launch_bounds__(BLOCK) void spspmm_numeric_pairs_kernel(
 //             in column order, store (column, sum) at the bin's final position and put the touched
 //             accumulators back to zero
 // Duplicates cost nothing extra, the output comes out sorted by construction, explicit zeros are kept
-// (an entry exists when its bit is set).  The sums of a big bin are formed in atomic order: unlike the
-// small / medium rows they are not bit-reproducible from run to run (fp32 rounding order).
+// (an entry exists when its bit is set).  With more than kMaxRanges / 4 ranges (sub = 1, see "Sub-bins" below)
+// the sums of a big bin are formed in atomic order: unlike the small / medium rows they are then not
+// bit-reproducible from run to run (rounding order).
 // Limit: kMaxRanges ranges, i.e. N <= 2^26 (fp32) / 2^25 (fp64) columns for operands that have such rows.
 // ---------------------------------------------------------------------------
 // Range size / workgroup shape of the dense accumulation, same-box A/B on the R-MAT scale-19 stress product
@@ -1682,6 +1683,36 @@ __global__ __launch_bounds__(64) void spspmm_smallbin_accum_kernel(
   }
 }
 
+// Every decision the host takes from N (columns of B) and the value type, in one place: numeric_rows,
+// tsamd_spspmm_symbolic, carve_large and the large-row stages read it, tsamd_spspmm_route() exports it
+// (tests/test_spspmm_route.py pins the thresholds).  Pure host arithmetic, no HIP call.
+struct Route {
+  int lg_range;      // log2 of the columns per range of the large-row path (value type)
+  int nr;            // column ranges
+  int sub;           // wave segments per (row, range) bin: 4 (reproducible bin order) or 1 (the counters would not fit LDS)
+  bool off_lds;      // bin kernel: segment offsets in LDS beside the cursors (else read from global memory)
+  bool small_pairs;  // small rows: one-wave radix sort of (column, value) pairs (else the register sort of 32-bit keys)
+  int passes;        // 8-bit radix passes over a column id
+  bool narrow_hash;  // symbolic hash sets: 24-bit multiply
+  bool large_ok;     // rows beyond kMediumCap products are supported at this N
+};
+
+Route spspmm_route(size_t esize, int64_t N) {
+  Route r;
+  int bits = 1;
+  while (bits < 32 && ((int64_t)1 << bits) < N) ++bits;
+  r.passes = (bits + 7) / 8;
+  r.small_pairs = bits + kIdxBits > 32;
+  r.narrow_hash = N <= ((int64_t)1 << 24);  // hash_slot: 24-bit multiply
+  r.lg_range = esize == 8 ? TSAMD_SPSPMM_LG_RANGE - 1 : TSAMD_SPSPMM_LG_RANGE;
+  r.nr = (int)((N + ((int64_t)1 << r.lg_range) - 1) >> r.lg_range);
+  if (r.nr < 1) r.nr = 1;
+  r.sub = r.nr <= kMaxRanges / (kLargeThreads / 64) ? kLargeThreads / 64 : 1;
+  r.off_lds = (int64_t)r.nr * r.sub <= kOffLdsMax;  // (the bin kernel takes the same decision from nr * sub)
+  r.large_ok = r.nr <= kMaxRanges;
+  return r;
+}
+
 struct LargeWs {
   int64_t *hist;      // [n_large * nr * sub + 1] products per (bin, wave segment), scanned in place -> segment offsets
   int64_t *bin_off;   // [n_large * nr + 1] offset of every bin = of its first segment
@@ -1694,6 +1725,7 @@ struct LargeWs {
   unsigned long long *counts; // [2] their numbers
   void *scan_ws;
   int nr, lg_range;
+  bool off_lds, large_ok;  // (spspmm_route)
   int64_t ntask;
 };
 
@@ -1707,11 +1739,13 @@ size_t carve_large(void *base, int64_t n_large, int64_t P_large, int64_t N, size
     return r;
   };
   LargeWs l;
-  l.lg_range = esize == 8 ? TSAMD_SPSPMM_LG_RANGE - 1 : TSAMD_SPSPMM_LG_RANGE;
-  l.nr = (int)((N + ((int64_t)1 << l.lg_range) - 1) >> l.lg_range);
-  if (l.nr < 1) l.nr = 1;
+  const Route route = spspmm_route(esize, N);
+  l.lg_range = route.lg_range;
+  l.nr = route.nr;
+  l.sub = route.sub;
+  l.off_lds = route.off_lds;
+  l.large_ok = route.large_ok;
   l.ntask = n_large * (int64_t)l.nr;
-  l.sub = l.nr <= kMaxRanges / (kLargeThreads / 64) ? kLargeThreads / 64 : 1;
   l.hist = (int64_t *)take(8 * (size_t)(l.ntask * l.sub + 1));
   l.bin_off = (int64_t *)take(8 * (size_t)(l.ntask + 1));
   l.bin_cnt = (int64_t *)take(8 * (size_t)(l.ntask + 1));
@@ -1753,11 +1787,11 @@ unsigned int persistent_blocks() {
 }
 
 // dynamic LDS of the hist / bin kernels: their nr * sub counters
-static size_t large_counter_bytes(int nr, int sub) {
-  const size_t n = (size_t)nr * (size_t)sub;
+static size_t large_counter_bytes(const LargeWs &w) {
+  const size_t n = (size_t)w.nr * (size_t)w.sub;
   // (the bin kernel keeps an int64 offset beside every cursor when there are at most kOffLdsMax of them; the hist kernel
   // uses the first part only)
-  const size_t off_bytes = n <= (size_t)kOffLdsMax ? n * sizeof(int64_t) : 0;
+  const size_t off_bytes = w.off_lds ? n * sizeof(int64_t) : 0;
   return (((n + 1) & ~(size_t)1) * sizeof(int) + off_bytes + 255) / 256 * 256;
 }
 
@@ -1771,9 +1805,9 @@ int symbolic_large(const int64_t *rowptrA, const int64_t *colA, const void *valA
   constexpr size_t esize = sizeof(T);
   LargeWs w;
   carve_large(workspace, n_large, P_large, N, esize, &w);
-  if (w.nr > kMaxRanges) return TSAMD_ERR_UNSUPPORTED;
+  if (!w.large_ok) return TSAMD_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(spspmm_large_hist_kernel, dim3((unsigned int)n_large), dim3(kLargeThreads),
-                     large_counter_bytes(w.nr, w.sub), stream,
+                     large_counter_bytes(w), stream,
                      rowptrA, colA, rowptrB, colB, rows, w.lg_range, w.nr, w.sub, w.hist);
   TSAMD_LAUNCH_CHECK();
   TSAMD_HIP_TRY(hipMemsetAsync(w.hist + w.ntask * w.sub, 0, 8, stream));
@@ -1783,12 +1817,12 @@ int symbolic_large(const int64_t *rowptrA, const int64_t *colA, const void *valA
                      (const int64_t *)w.hist, w.sub, w.ntask, w.bin_off);
   TSAMD_LAUNCH_CHECK();
   if (with_values)
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w.nr, w.sub),
+    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
                        stream, rowptrA, colA, reinterpret_cast<const T *>(valA), rowptrB, colB,
                        reinterpret_cast<const T *>(valB), rows, w.lg_range, w.nr, w.sub, (const int64_t *)w.hist,
                        w.bcol, reinterpret_cast<T *>(w.bval));
   else
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, false>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w.nr, w.sub),
+    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, false>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
                        stream, rowptrA, colA, (const T *)nullptr, rowptrB, colB, (const T *)nullptr, rows,
                        w.lg_range, w.nr, w.sub, (const int64_t *)w.hist, w.bcol, (T *)nullptr);
   TSAMD_LAUNCH_CHECK();
@@ -1821,10 +1855,10 @@ int numeric_large(const int64_t *rowptrA, const int64_t *colA, const void *valA,
                   bool values_binned, void *workspace, hipStream_t stream) {
   LargeWs w;
   carve_large(workspace, n_large, P_large, N, sizeof(T), &w);
-  if (w.nr > kMaxRanges) return TSAMD_ERR_UNSUPPORTED;
+  if (!w.large_ok) return TSAMD_ERR_UNSUPPORTED;
   T *bv = reinterpret_cast<T *>(w.bval);
   if (valC != nullptr && !values_binned) {  // the symbolic stage binned the columns only; the values follow the same offsets
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w.nr, w.sub),
+    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
                        stream, rowptrA, colA, reinterpret_cast<const T *>(valA), rowptrB, colB,
                        reinterpret_cast<const T *>(valB), rows, w.lg_range, w.nr, w.sub, (const int64_t *)w.hist,
                        w.bcol, bv);
@@ -1860,14 +1894,13 @@ int numeric_rows(const int64_t *rowptrA, const int64_t *colA, const void *valA, 
                  const uint32_t *colB, const void *valB, const int64_t *prod, const int64_t *bins,
                  int64_t M, int64_t N, int64_t n_medium, const int64_t *rowptrC, int64_t *colC, void *valC,
                  hipStream_t stream) {
-  int bits = 1;
-  while (bits < 32 && ((int64_t)1 << bits) < N) ++bits;
-  const int passes = (bits + 7) / 8;  // 8-bit radix passes over the column ids
+  const Route route = spspmm_route(sizeof(T), N);
+  const int passes = route.passes;  // 8-bit radix passes over the column ids
   const T *va = reinterpret_cast<const T *>(valA);
   const T *vb = reinterpret_cast<const T *>(valB);
   T *vc = reinterpret_cast<T *>(valC);
   {  // small rows: all M rows in natural order, the kernel skips the others
-    if (bits + kIdxBits <= 32) {
+    if (!route.small_pairs) {
       // (one workgroup per row: a persistent launch pipelined across rows measured slower,
       // profiles/r04_ab_spspmm_row_pipe.log)
       hipLaunchKernelGGL((spspmm_numeric_small_kernel<T>), dim3((unsigned int)M), dim3(64), 0, stream,
@@ -1931,6 +1964,22 @@ extern "C" size_t tsamd_spspmm_workspace_bytes(int dtype, int64_t n_large, int64
   return carve_large(nullptr, n_large, P_large, N, dtype == TSAMD_F64 ? 8 : 4, nullptr);
 }
 
+extern "C" int tsamd_spspmm_route(int dtype, int64_t N, int64_t out[8]) {
+  if (!out) return TSAMD_ERR_INVALID;
+  if (dtype != TSAMD_F32 && dtype != TSAMD_F64) return TSAMD_ERR_UNSUPPORTED;
+  if (N < 0 || N >= ((int64_t)1 << 32) - 1) return TSAMD_ERR_UNSUPPORTED;
+  const Route r = spspmm_route(dtype == TSAMD_F64 ? 8 : 4, N);
+  out[0] = r.lg_range;
+  out[1] = r.nr;
+  out[2] = r.sub;
+  out[3] = r.off_lds ? 1 : 0;
+  out[4] = r.small_pairs ? 1 : 0;
+  out[5] = r.passes;
+  out[6] = r.narrow_hash ? 1 : 0;
+  out[7] = r.large_ok ? 1 : 0;
+  return TSAMD_OK;
+}
+
 extern "C" int tsamd_spspmm_symbolic(int dtype, const int64_t *rowptrA, const int64_t *colA,
                                      const void *valA, const int64_t *rowptrB, const uint32_t *colB,
                                      const void *valB, int bin_values, int64_t M, int64_t N,
@@ -1948,7 +1997,7 @@ extern "C" int tsamd_spspmm_symbolic(int dtype, const int64_t *rowptrA, const in
   if (n_large > 0 && (!workspace || workspace_bytes < tsamd_spspmm_workspace_bytes(dtype, n_large, P_large, N)))
     return TSAMD_ERR_WORKSPACE;
   TSAMD_HIP_TRY(hipMemsetAsync(nnzC, 0, sizeof(int64_t) * (size_t)M, stream));
-  const bool narrow_cols = N <= ((int64_t)1 << 24);  // hash_slot: 24-bit multiply
+  const bool narrow_cols = spspmm_route(dtype == TSAMD_F64 ? 8 : 4, N).narrow_hash;
   if (narrow_cols)
     hipLaunchKernelGGL((spspmm_symbolic_kernel<64, 10, true>), dim3((unsigned int)M), dim3(64), 0, stream, rowptrA,
                        colA, rowptrB, colB, prod, bins, nnzC);
