@@ -434,6 +434,23 @@ int tsamd_sort_coo_values(int mode, const int64_t *row, const int64_t *col, int6
  * the self-test if no sort has run yet: one synchronising round trip of 4 bytes; call it once before capturing a
  * stream), 0 / 1 = force a mode, 2 = forget the decision and run the self-test again.  Returns the mode in force. */
 int tsamd_sort_rank_mode(int set);
+/* tsamd_sort_route: what the sorts above (coalesce = 0) and tsamd_sort_coalesce* (coalesce = 1) decide from the sizes
+ * alone, for E entries of an M x N matrix with a riding value of value_bytes = 0 (none), 4 or 8 bytes.  Host
+ * arithmetic only -- no HIP call, no device -- through the very functions the driver plans with.
+ *   out[0] route   1 = the one-launch sort in LDS (1 <= E <= 8192, 0 < N < 2^32 and max(M, 1) * N <= 2^32; tried
+ *                  first), else 0 = nothing to order (E <= 1 or keys of zero bits: a copy + the identity) or 2 = the
+ *                  general path
+ *   out[1] key_bits, out[2] idx_bits, out[3] packed (position in the key's word), out[4] passes (8-bit one-sweep
+ *                  passes).  Route 1: the bits of M * N, 0, 0 and the passes of the one-launch kernel.
+ *   out[5] ride    a 4-byte value travels through the one-sweep passes (else the last pass gathers it)
+ *   out[6] tiles   workgroups of a one-sweep pass
+ *   out[7..15]     the bucket plan: on, levels, strip, bits, bits1, kshift, shift, nb, cap (all 0 when off: below 2^17
+ *                  entries, no plan within 14 bucket bits, or a compacting sort whose full-word buckets would cut
+ *                  through a key)
+ * Routes 0 and 1 leave out[5..15] = 0.  Whether the bucket path or the passes then sort an input of route 2 is
+ * decided on the device (a bucket beyond `cap` falls back).  TSAMD_ERR_UNSUPPORTED where the sorts refuse the sizes,
+ * TSAMD_ERR_INVALID for negative sizes, a value_bytes other than 0 / 4 / 8 or out == NULL. */
+int tsamd_sort_route(int64_t E, int64_t M, int64_t N, int value_bytes, int coalesce, int64_t out[16]);
 size_t tsamd_sort_coo_workspace_bytes(int64_t E);
 int tsamd_sort_coo(const int64_t *row, const int64_t *col, int64_t E, int64_t M,
                    int64_t N, int64_t *row_out, int64_t *col_out, int64_t *perm_out,

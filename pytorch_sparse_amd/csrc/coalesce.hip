@@ -9,6 +9,8 @@
 // with fused kernels: one order probe, one radix sort that emits sorted (row, col) and the
 // permutation, one flag+scan+compaction, one segmented reduction that reads the values
 // through the permutation (no materialised value[perm]).
+// This file: the order probes, the compaction, the segment reduce and tsamd_sort_coalesce*; the sort itself, its
+// driver and tsamd_sort_coo* are in sort.hip.
 #include "common.h"
 #include "sort.h"
 
@@ -288,278 +290,10 @@ __global__ void segment_reduce_kernel(const T *__restrict__ value, const int64_t
   out[t] = Traits<T>::from_acc(acc);
 }
 
-int key_bits_for(int64_t rows, int64_t cols) {
-  // keys are < rows * cols
-  unsigned __int128 lim = (unsigned __int128)(rows > 0 ? rows : 1) * (unsigned __int128)(cols > 0 ? cols : 1);
-  int bits = 0;
-  while (bits < 63 && ((unsigned __int128)1 << bits) < lim) ++bits;
-  return bits;
-}
-
-// ---------------------------------------------------------------------------
-// Small inputs: the whole sort_coo in ONE launch.  A COO set of a few thousand entries (a mini-batch
-// sub-graph, BASELINE config 1) spends its time in ~16 dependent launches of the general path (probe, keys,
-// (histogram, scan, scatter) per digit, decode: ~4 us each on the GPU, a HIP graph replays them no faster).
-// Here one 1024-thread workgroup keeps the (32-bit key, 16-bit index) pairs of up to 8192 entries in LDS and
-// runs every 8-bit LSD pass there: per-wave match ranking (8 ballots per key, stable), per-wave digit counts,
-// one scan over the 256 digits, scatter into the other LDS buffer.  Needs row * N + col < 2^32.
-// counts (nullable): [#descents, #adjacent duplicates] of the input (lexicographic); with `auto_mode` an input
-// without descents skips the passes (outputs = copy + identity), exactly like tsamd_sort_coo_auto.
-// ---------------------------------------------------------------------------
-constexpr int kSmallSortThreads = 1024;
-constexpr int kSmallSortItems = 8;
-constexpr int kSmallSortMax = kSmallSortThreads * kSmallSortItems;  // 8192
-
-__global__ __launch_bounds__(kSmallSortThreads) void small_sort_coo_kernel(
-    const int64_t *__restrict__ row, const int64_t *__restrict__ col, int n, uint32_t ncols, int passes,
-    int64_t *__restrict__ row_out, int64_t *__restrict__ col_out, int64_t *__restrict__ perm_out,
-    unsigned long long *__restrict__ counts, int auto_mode) {
-  __shared__ uint32_t kbuf[2][kSmallSortMax];
-  __shared__ uint16_t vbuf[2][kSmallSortMax];
-  __shared__ uint32_t cnt[kSmallSortThreads / 64][256];
-  __shared__ uint32_t dig_off[256];
-  __shared__ uint32_t wsum[4];
-  __shared__ unsigned int s_order[2];
-  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid < 2) s_order[tid] = 0;
-  __syncthreads();
-  // load, build keys, probe the order
-  unsigned int desc = 0, dup = 0;
-#pragma unroll
-  for (int j = 0; j < kSmallSortItems; ++j) {
-    const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
-    if (i < n) {
-      const int64_t r = row[i], c = col[i];
-      kbuf[0][i] = (uint32_t)((uint64_t)r * ncols + (uint64_t)c);
-      vbuf[0][i] = (uint16_t)i;
-      if (i > 0) {
-        const int64_t pr = row[i - 1], pc = col[i - 1];
-        desc += (r < pr) || (r == pr && c < pc);
-        dup += (r == pr) && (c == pc);
-      }
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    desc += lane_xor(desc, off);
-    dup += lane_xor(dup, off);
-  }
-  if (lane == 0) {
-    if (desc) atomicAdd(&s_order[0], desc);
-    if (dup) atomicAdd(&s_order[1], dup);
-  }
-  __syncthreads();
-  if (counts != nullptr && tid < 2) counts[tid] = s_order[tid];
-  const bool skip = auto_mode != 0 && s_order[0] == 0;
-  int cur = 0;
-  for (int pass = 0; pass < passes && !skip; ++pass) {
-    const int shift = pass * 8;
-    const uint32_t *ks = kbuf[cur];
-    const uint16_t *vs = vbuf[cur];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cnt[w][q * 64 + lane] = 0;  // this wave's counters (wave-local: no barrier)
-    uint32_t key[kSmallSortItems], lrank[kSmallSortItems];
-    uint16_t val[kSmallSortItems];
-#pragma unroll
-    for (int j = 0; j < kSmallSortItems; ++j) {
-      const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
-      const bool valid = i < n;
-      key[j] = valid ? ks[i] : 0u;
-      val[j] = valid ? vs[i] : (uint16_t)0;
-      const uint32_t d = (key[j] >> shift) & 255u;
-      unsigned long long peers = __ballot(valid);
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long m = __ballot(valid && bit);
-        peers &= bit ? m : ~m;
-      }
-      const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
-      const int leader = valid ? (__ffsll((long long)peers) - 1) : lane;
-      uint32_t pre = 0;
-      if (valid && lane == leader) {
-        pre = cnt[w][d];
-        cnt[w][d] = pre + (uint32_t)__popcll(peers);
-      }
-      pre = lane_read(pre, leader);
-      lrank[j] = pre + rank;
-    }
-    __syncthreads();
-    if (tid < 256) {  // thread t owns digit t: exclusive prefix over the waves, then over the digits
-      uint32_t run = 0;
-#pragma unroll
-      for (int ww = 0; ww < kSmallSortThreads / 64; ++ww) {
-        const uint32_t c = cnt[ww][tid];
-        cnt[ww][tid] = run;
-        run += c;
-      }
-      uint32_t inc = run;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = lane_read(inc, lane >= off ? lane - off : lane);
-        if (lane >= off) inc += o;
-      }
-      if (lane == 63) wsum[w] = inc;
-      dig_off[tid] = inc - run;  // exclusive inside the wave; the wave bases are added below
-    }
-    __syncthreads();
-    if (tid < 256) {
-      uint32_t base = 0;
-      for (int ww = 0; ww < w; ++ww) base += wsum[ww];
-      dig_off[tid] += base;
-    }
-    __syncthreads();
-    uint32_t *kd = kbuf[cur ^ 1];
-    uint16_t *vd = vbuf[cur ^ 1];
-#pragma unroll
-    for (int j = 0; j < kSmallSortItems; ++j) {
-      const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
-      if (i < n) {
-        const uint32_t d = (key[j] >> shift) & 255u;
-        const uint32_t pos = dig_off[d] + cnt[w][d] + lrank[j];
-        kd[pos] = key[j];
-        vd[pos] = val[j];
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  for (int i = tid; i < n; i += kSmallSortThreads) {
-    if (skip) {
-      if (row_out) row_out[i] = row[i];
-      if (col_out) col_out[i] = col[i];
-      perm_out[i] = i;
-    } else {
-      const uint32_t k = kbuf[cur][i];
-      const uint32_t r = k / ncols;
-      if (row_out) row_out[i] = (int64_t)r;
-      if (col_out) col_out[i] = (int64_t)(k - r * ncols);
-      perm_out[i] = (int64_t)vbuf[cur][i];
-    }
-  }
-}
-
-// true when the one-launch path applies (and was launched)
-bool small_sort_coo(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N, int64_t *row_out,
-                    int64_t *col_out, int64_t *perm_out, int64_t *counts, bool auto_mode, hipStream_t stream) {
-  if (E > kSmallSortMax || N <= 0 || N >= ((int64_t)1 << 32)) return false;
-  const int bits = key_bits_for(M, N);
-  if (bits > 32) return false;
-  const int passes = E > 1 ? (bits + 7) / 8 : 0;
-  hipLaunchKernelGGL(small_sort_coo_kernel, dim3(1), dim3(kSmallSortThreads), 0, stream, row, col, (int)E,
-                     (uint32_t)N, passes, row_out, col_out, perm_out,
-                     reinterpret_cast<unsigned long long *>(counts), auto_mode ? 1 : 0);
-  return true;
-}
-
 }  // namespace
 }  // namespace tsamd
 
 using namespace tsamd;
-
-extern "C" size_t tsamd_sort_coo_workspace_bytes(int64_t E) { return sort_coo_workspace_bytes(E); }
-
-extern "C" int tsamd_sort_rank_mode(int set) {
-  if (set == 0 || set == 1) sort_set_rank_mode(set);
-  else if (set == 2) sort_set_rank_mode(-1);
-  return sort_rank_mode(nullptr);
-}
-
-extern "C" int tsamd_sort_coo(const int64_t *row, const int64_t *col, int64_t E, int64_t M,
-                              int64_t N, int64_t *row_out, int64_t *col_out, int64_t *perm_out,
-                              void *workspace, size_t workspace_bytes, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (E < 0 || M < 0 || N < 0) return TSAMD_ERR_INVALID;
-  if (E == 0) return TSAMD_OK;
-  if (!row || !col || !perm_out) return TSAMD_ERR_INVALID;
-  if (!sort_coo_supported(E, M, N)) return TSAMD_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < tsamd_sort_coo_workspace_bytes(E)) return TSAMD_ERR_WORKSPACE;
-  if (small_sort_coo(row, col, E, M, N, row_out, col_out, perm_out, nullptr, false, stream)) {
-    TSAMD_LAUNCH_CHECK();
-    return TSAMD_OK;
-  }
-  return sort_coo_onesweep(row, col, E, M, N, row_out, col_out, perm_out, nullptr, false, nullptr, workspace, stream);
-}
-
-// sort_coo decided on the device: counts_out[0..1] = (#descents, #adjacent duplicates) of the INPUT; when
-// there is no descent the radix passes return at once and the outputs are a copy + the identity.
-static int sort_coo_auto_impl(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
-                              int64_t *row_out, int64_t *col_out, int64_t *perm_out, int64_t *counts_out,
-                              bool probe, void *workspace, size_t workspace_bytes, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (E < 0 || M < 0 || N < 0 || !counts_out) return TSAMD_ERR_INVALID;
-  if (E == 0) {
-    if (probe) TSAMD_HIP_TRY(hipMemsetAsync(counts_out, 0, 2 * sizeof(int64_t), stream));
-    return TSAMD_OK;
-  }
-  if (!row || !col || !perm_out) return TSAMD_ERR_INVALID;
-  if (!sort_coo_supported(E, M, N)) return TSAMD_ERR_UNSUPPORTED;
-  if (small_sort_coo(row, col, E, M, N, row_out, col_out, perm_out, probe ? counts_out : nullptr, true, stream)) {
-    TSAMD_LAUNCH_CHECK();  // probe, sort and decode in one launch (the small kernel probes for itself)
-    return TSAMD_OK;
-  }
-  if (!workspace || workspace_bytes < tsamd_sort_coo_workspace_bytes(E)) return TSAMD_ERR_WORKSPACE;
-  // probe = true: the build kernel counts the descents itself (one read of the input serves the probe, the keys and
-  // the digit histograms); probe = false: counts_out[0] already holds them (tsamd_coo_check)
-  return sort_coo_onesweep(row, col, E, M, N, row_out, col_out, perm_out, probe ? nullptr : counts_out, probe,
-                           probe ? counts_out : nullptr, workspace, stream);
-}
-
-extern "C" int tsamd_sort_coo_auto(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
-                                   int64_t *row_out, int64_t *col_out, int64_t *perm_out,
-                                   int64_t *counts_out, void *workspace, size_t workspace_bytes,
-                                   void *stream_) {
-  return sort_coo_auto_impl(row, col, E, M, N, row_out, col_out, perm_out, counts_out, true, workspace,
-                            workspace_bytes, stream_);
-}
-
-// The same with the order already probed: descents[0] (device) = #descents of the input, e.g. counts[0] of
-// tsamd_coo_check -- the constructor enqueues check, sort and gathers back to back and reads the check's
-// result once everything is in flight.
-extern "C" int tsamd_sort_coo_probed(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
-                                     int64_t *row_out, int64_t *col_out, int64_t *perm_out,
-                                     const int64_t *descents, void *workspace, size_t workspace_bytes,
-                                     void *stream_) {
-  return sort_coo_auto_impl(row, col, E, M, N, row_out, col_out, perm_out, const_cast<int64_t *>(descents), false,
-                            workspace, workspace_bytes, stream_);
-}
-
-// One entry point for the three flavours with the entries' values riding along (include/tsamd.h).
-extern "C" int tsamd_sort_coo_values(int mode, const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
-                                     int64_t *row_out, int64_t *col_out, int64_t *perm_out, int64_t *counts,
-                                     const void *value, void *value_out, int64_t value_bytes, void *workspace,
-                                     size_t workspace_bytes, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (E < 0 || M < 0 || N < 0 || mode < 0 || mode > 3 || (mode != 0 && !counts)) return TSAMD_ERR_INVALID;
-  if ((value == nullptr) != (value_out == nullptr)) return TSAMD_ERR_INVALID;
-  if (value != nullptr && value_bytes != 4 && value_bytes != 8) return TSAMD_ERR_UNSUPPORTED;
-  if (E == 0) {
-    if (mode == 1 || mode == 3) TSAMD_HIP_TRY(hipMemsetAsync(counts, 0, (mode == 3 ? 4 : 2) * sizeof(int64_t), stream));
-    return TSAMD_OK;
-  }
-  if (!row || !col || !perm_out) return TSAMD_ERR_INVALID;
-  if (!sort_coo_supported(E, M, N)) return TSAMD_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < tsamd_sort_coo_workspace_bytes(E)) return TSAMD_ERR_WORKSPACE;
-  if (mode == 3) {
-    // the constructor's range check (max row / col id) rides in the sort's build pass -- except on the one-launch
-    // path and for keys of zero bits, where the check is its own (tiny) launch and the sort runs "probed"
-    if (E <= kSmallSortMax || key_bits_for(M, N) == 0 || (M <= 1 && N <= 1)) {
-      int st = tsamd_coo_check(row, col, E, counts, stream_);
-      if (st != TSAMD_OK) return st;
-      mode = 2;
-    } else {
-      return sort_coo_onesweep(row, col, E, M, N, row_out, col_out, perm_out, nullptr, true, counts, workspace, stream,
-                               value, value_out, (int)value_bytes, true);
-    }
-  }
-  if (small_sort_coo(row, col, E, M, N, row_out, col_out, perm_out, mode == 1 ? counts : nullptr, mode != 0, stream)) {
-    TSAMD_LAUNCH_CHECK();
-    if (value != nullptr)  // the one-launch path has no payload: a gather through the permutation behind it
-      return tsamd_gather_rows(value, perm_out, value_out, E, E, value_bytes, stream_);
-    return TSAMD_OK;
-  }
-  return sort_coo_onesweep(row, col, E, M, N, row_out, col_out, perm_out, mode == 2 ? counts : nullptr, mode == 1,
-                           mode == 1 ? counts : nullptr, workspace, stream, value, value_out, (int)value_bytes);
-}
 
 // counts_out[0..3] = (#descents, #adjacent duplicates, max row id, max col id): everything the
 // SparseStorage constructor has to read back, in one pass and one transfer
@@ -652,30 +386,33 @@ int sort_coalesce_impl(const int64_t *row, const int64_t *col, int64_t E, int64_
   const size_t co_bytes = tsamd_coalesce_workspace_bytes(E);
   const size_t pre_zero = align_up(sizeof(unsigned long long) * kSortCoalesceStatusWords, 256) + co_bytes;
   void *sort_ws = wsp + pre_zero;
-  const unsigned long long *skip = nullptr;
-  if (E <= kSmallSortMax && small_sort_coo(row, col, E, M, N, row_tmp, col_tmp, seg_ptr /* perm: scratch, rewritten below */,
-                                           counts, true, stream)) {
-    TSAMD_LAUNCH_CHECK();
-    if (value != nullptr) {
-      int st = tsamd_gather_rows(value, seg_ptr, value_out, E, E, value_bytes, stream_);
-      if (st != TSAMD_OK) return st;
-    }
-    TSAMD_HIP_TRY(hipMemsetAsync(co_ws, 0, co_bytes, stream));
-  } else {
-    SortCoalesce co{row_u, col_u, seg_ptr, counts + 2, status};
-    co.pre_zero_bytes = pre_zero;
-    if (reduce >= 0) co.fused_out = counts + 3;
-    co.no_seg = reduce >= 0 && value == nullptr;  // tsamd_sort_coalesce_reduce without a value: index only
-    if (reduce >= 0 && value != nullptr && value_bytes == 4 && value_u != nullptr) {
-      co.value_u = value_u;
-      co.reduce = reduce;
-      co.is_float = is_float;
-    }
-    int st = sort_coo_onesweep(row, col, E, M, N, row_tmp, col_tmp, nullptr, nullptr, true, counts, sort_ws, stream, value,
-                               value_out, (int)value_bytes, false, &co);
-    if (st != TSAMD_OK) return st;
-    skip = sort_fast_flag(sort_ws, E);
+  SortCoalesce sc{row_u, col_u, seg_ptr, counts + 2, status};
+  sc.pre_zero_bytes = pre_zero;
+  if (reduce >= 0) sc.fused_out = counts + 3;
+  sc.no_seg = reduce >= 0 && value == nullptr;  // tsamd_sort_coalesce_reduce without a value: index only
+  if (reduce >= 0 && value != nullptr && value_bytes == 4 && value_u != nullptr) {
+    sc.value_u = value_u;
+    sc.reduce = reduce;
+    sc.is_float = is_float;
   }
+  SortCall c{row, col, E, M, N, row_tmp, col_tmp, nullptr};
+  c.order = SortOrder::kProbe;
+  c.counts = counts;
+  c.src = value;
+  c.dst = value_out;
+  c.bytes = value_bytes;
+  c.co = &sc;
+  c.workspace = sort_ws;
+  c.workspace_bytes = workspace_bytes - pre_zero;
+  c.stream = stream;
+  SortRoute route = kSortGeneral;
+  int st = sort_coo_run(c, &route);
+  if (st != TSAMD_OK) return st;
+  // the one-launch sort knows no bucket path and fills nothing: the compaction's state is still to zero, and there is
+  // no flag to look at; every other route zeroed the pre_zero bytes with its own fill and left the flag in its header
+  const unsigned long long *skip = nullptr;
+  if (route == kSortSmall) TSAMD_HIP_TRY(hipMemsetAsync(co_ws, 0, co_bytes, stream));
+  else skip = sort_fast_flag(sort_ws, E);
   // the one-sweep passes (or the one-launch sort) left sorted pairs in row_tmp / col_tmp: compact them -- returns at
   // once when the bucket path wrote the compacted outputs itself
   hipLaunchKernelGGL(coalesce_compact_kernel, dim3((unsigned int)ceil_div(E, kCompactTile)), dim3(256), 0, stream, row_tmp,

@@ -79,72 +79,46 @@ Tensor coo_check(Tensor row, Tensor col) {
   return counts;
 }
 
-// sort_coo decided on the device, no host sync: -> (row_sorted, col_sorted, perm, counts[2] on the device)
-std::tuple<Tensor, Tensor, Tensor, Tensor> sort_coo_auto(Tensor row, Tensor col, int64_t M, int64_t N) {
-  check_index(row, "row");
-  check_index(col, "col");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
-  Tensor perm = torch::empty({E}, row.options()), row_s = torch::empty({E}, row.options()),
-         col_s = torch::empty({E}, row.options()), counts = torch::empty({2}, row.options());
-  Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(E), row);
-  check_status(tsamd_sort_coo_auto(row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N,
-                                   row_s.data_ptr<int64_t>(), col_s.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
-                                   counts.data_ptr<int64_t>(), ws.data_ptr(), (size_t)ws.numel(), current_stream(row)),
-               "tsamd_sort_coo_auto");
-  return std::make_tuple(row_s, col_s, perm, counts);
-}
-
-// sort_coo decided on the device from an EXISTING probe: counts[0] (device) = #descents (tsamd::coo_check)
-std::tuple<Tensor, Tensor, Tensor> sort_coo_probed(Tensor row, Tensor col, int64_t M, int64_t N, Tensor counts) {
-  check_index(row, "row");
-  check_index(col, "col");
-  check_index(counts, "counts");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
-  TORCH_CHECK(counts.numel() >= 1 && counts.is_contiguous(), "counts must hold the number of descents");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
-  Tensor perm = torch::empty({E}, row.options()), row_s = torch::empty({E}, row.options()),
-         col_s = torch::empty({E}, row.options());
-  Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(E), row);
-  check_status(tsamd_sort_coo_probed(row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N,
-                                     row_s.data_ptr<int64_t>(), col_s.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
-                                     counts.data_ptr<int64_t>(), ws.data_ptr(), (size_t)ws.numel(), current_stream(row)),
-               "tsamd_sort_coo_probed");
-  return std::make_tuple(row_s, col_s, perm);
-}
+// What the sort wrappers below open with: index checks, equal lengths, the device guard (a member: it is in force for
+// as long as the wrapper's local lives, i.e. the whole call), contiguous inputs; and their outputs' allocation.
+struct CooArgs {
+  static int device_of(const Tensor &row, const Tensor &col) {
+    check_index(row, "row");
+    check_index(col, "col");
+    TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
+    return row.get_device();
+  }
+  c10::hip::HIPGuard guard;
+  Tensor row, col;
+  int64_t E;
+  CooArgs(const Tensor &r, const Tensor &c) : guard(device_of(r, c)), row(r.contiguous()), col(c.contiguous()), E(r.numel()) {}
+  Tensor empty(at::IntArrayRef size) const { return torch::empty(size, row.options()); }
+  int64_t *rowp() const { return row.data_ptr<int64_t>(); }
+  int64_t *colp() const { return col.data_ptr<int64_t>(); }
+};
 
 // The sorts with the entries' values riding along: mode 0 plain | 1 device-decided (probe) | 2 device-decided from
 // counts[0] (tsamd::coo_check) | 3 = check + device-decided sort in one go (counts[4]) -> (row_sorted, col_sorted, perm, counts, value[perm] or an empty tensor).
 // 1-D values of 4- or 8-byte elements that need no gradient are written by the sort's last pass
 // (tsamd_sort_coo_values); anything else is gathered through the permutation afterwards (differentiable).
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coo_values(Tensor row, Tensor col, int64_t M, int64_t N,
-                                                                 int64_t mode, OptTensor opt_counts, OptTensor opt_value) {
-  check_index(row, "row");
-  check_index(col, "col");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
+// index = false: only perm (row_sorted / col_sorted stay empty).
+// tsamd::sort_coo, sort_coo_auto and sort_coo_probed are this function with fewer outputs: they too allocate the
+// (2-word) counts and the empty value tensor, and a failing status names tsamd_sort_coo_values, the entry really called.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coo_impl(const Tensor &row, const Tensor &col, int64_t M, int64_t N,
+                                                               int64_t mode, OptTensor opt_counts, OptTensor opt_value,
+                                                               bool index) {
+  CooArgs a(row, col);
   TORCH_CHECK(mode >= 0 && mode <= 3, "mode must be 0 .. 3");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
-  Tensor perm = torch::empty({E}, row.options()), row_s = torch::empty({E}, row.options()),
-         col_s = torch::empty({E}, row.options());
-  Tensor counts;
   if (mode == 2) {
     TORCH_CHECK(opt_counts.has_value(), "mode 2 needs the probe's counts");
-    counts = opt_counts.value();
-    check_index(counts, "counts");
-    TORCH_CHECK(counts.numel() >= 1 && counts.is_contiguous(), "counts must hold the number of descents");
-  } else {
-    counts = torch::empty({mode == 3 ? 4 : 2}, row.options());
+    check_index(opt_counts.value(), "counts");
+    TORCH_CHECK(opt_counts.value().numel() >= 1 && opt_counts.value().is_contiguous(),
+                "counts must hold the number of descents");
   }
-  Tensor value, value_s = torch::empty({0}, row.options());
+  const int64_t E = a.E;
+  Tensor perm = a.empty({E}), row_s = a.empty({index ? E : 0}), col_s = a.empty({index ? E : 0});
+  Tensor counts = mode == 2 ? opt_counts.value() : a.empty({mode == 3 ? 4 : 2});
+  Tensor value, value_s = a.empty({0});
   bool fused = false;
   if (opt_value.has_value()) {
     value = opt_value.value();
@@ -156,37 +130,38 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coo_values(Tensor row, T
       value_s = torch::empty_like(value);
     }
   }
-  Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(E), row);
-  check_status(tsamd_sort_coo_values((int)mode, row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N,
-                                     row_s.data_ptr<int64_t>(), col_s.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
+  Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(E), a.row);
+  check_status(tsamd_sort_coo_values((int)mode, a.rowp(), a.colp(), E, M, N, index ? row_s.data_ptr<int64_t>() : nullptr,
+                                     index ? col_s.data_ptr<int64_t>() : nullptr, perm.data_ptr<int64_t>(),
                                      mode == 0 ? nullptr : counts.data_ptr<int64_t>(), fused ? value.data_ptr() : nullptr,
                                      fused ? value_s.data_ptr() : nullptr, fused ? (int64_t)value.element_size() : 0,
-                                     ws.data_ptr(), (size_t)ws.numel(), current_stream(row)),
+                                     ws.data_ptr(), (size_t)ws.numel(), current_stream(a.row)),
                "tsamd_sort_coo_values");
   if (opt_value.has_value() && !fused) value_s = value.index_select(0, perm);
   return std::make_tuple(row_s, col_s, perm, counts, value_s);
 }
 
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coo_values(Tensor row, Tensor col, int64_t M, int64_t N,
+                                                                 int64_t mode, OptTensor opt_counts, OptTensor opt_value) {
+  return sort_coo_impl(row, col, M, N, mode, opt_counts, opt_value, true);
+}
+
 // stable sort by row * N + col -> (row_sorted, col_sorted, perm); with index=false only perm
-std::tuple<Tensor, Tensor, Tensor> sort_coo(Tensor row, Tensor col, int64_t M, int64_t N,
-                                            bool index) {
-  check_index(row, "row");
-  check_index(col, "col");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
-  Tensor perm = torch::empty({E}, row.options());
-  Tensor row_s = index ? torch::empty({E}, row.options()) : torch::empty({0}, row.options());
-  Tensor col_s = index ? torch::empty({E}, row.options()) : torch::empty({0}, row.options());
-  Tensor ws = workspace(tsamd_sort_coo_workspace_bytes(E), row);
-  check_status(tsamd_sort_coo(row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N,
-                              index ? row_s.data_ptr<int64_t>() : nullptr,
-                              index ? col_s.data_ptr<int64_t>() : nullptr, perm.data_ptr<int64_t>(),
-                              ws.data_ptr(), (size_t)ws.numel(), current_stream(row)),
-               "tsamd_sort_coo");
-  return std::make_tuple(row_s, col_s, perm);
+std::tuple<Tensor, Tensor, Tensor> sort_coo(Tensor row, Tensor col, int64_t M, int64_t N, bool index) {
+  auto r = sort_coo_impl(row, col, M, N, 0, c10::nullopt, c10::nullopt, index);
+  return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+}
+
+// sort_coo decided on the device, no host sync: -> (row_sorted, col_sorted, perm, counts[2] on the device)
+std::tuple<Tensor, Tensor, Tensor, Tensor> sort_coo_auto(Tensor row, Tensor col, int64_t M, int64_t N) {
+  auto r = sort_coo_impl(row, col, M, N, 1, c10::nullopt, c10::nullopt, true);
+  return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r));
+}
+
+// sort_coo decided on the device from an EXISTING probe: counts[0] (device) = #descents (tsamd::coo_check)
+std::tuple<Tensor, Tensor, Tensor> sort_coo_probed(Tensor row, Tensor col, int64_t M, int64_t N, Tensor counts) {
+  auto r = sort_coo_impl(row, col, M, N, 2, counts, c10::nullopt, true);
+  return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r));
 }
 
 // tsamd_sort_coalesce: unsorted (row, col) [+ a 1-D value of 4- / 8-byte elements without a gradient] ->
@@ -194,19 +169,14 @@ std::tuple<Tensor, Tensor, Tensor> sort_coo(Tensor row, Tensor col, int64_t M, i
 //  value in sorted order or an empty tensor); only the first counts[2] (+1) columns of index_u / entries of seg_ptr count.
 std::tuple<Tensor, Tensor, Tensor, Tensor> sort_coalesce(Tensor row, Tensor col, int64_t M, int64_t N,
                                                        OptTensor opt_value) {
-  check_index(row, "row");
-  check_index(col, "col");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
+  CooArgs a(row, col);
+  const int64_t E = a.E;
   // (the two rows of ONE [2, E] tensor: without duplicates it IS the result, nothing is stacked afterwards)
-  Tensor index_u = torch::empty({2, E}, row.options());
+  Tensor index_u = a.empty({2, E});
   Tensor row_u = index_u.select(0, 0), col_u = index_u.select(0, 1);
-  Tensor row_t = torch::empty({E}, row.options()), col_t = torch::empty({E}, row.options());
-  Tensor seg = torch::empty({E + 1}, row.options()), counts = torch::empty({3}, row.options());
-  Tensor value, value_s = torch::empty({0}, row.options());
+  Tensor row_t = a.empty({E}), col_t = a.empty({E});
+  Tensor seg = a.empty({E + 1}), counts = a.empty({3});
+  Tensor value, value_s = a.empty({0});
   if (opt_value.has_value()) {
     value = opt_value.value();
     check_gpu(value, "value");
@@ -218,7 +188,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> sort_coalesce(Tensor row, Tensor col,
   }
   const bool with_value = opt_value.has_value() && E > 0;
   Tensor ws = workspace(tsamd_sort_coalesce_workspace_bytes(E), row);
-  check_status(tsamd_sort_coalesce(row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N, row_t.data_ptr<int64_t>(),
+  check_status(tsamd_sort_coalesce(a.rowp(), a.colp(), E, M, N, row_t.data_ptr<int64_t>(),
                                    col_t.data_ptr<int64_t>(), row_u.data_ptr<int64_t>(), col_u.data_ptr<int64_t>(),
                                    seg.data_ptr<int64_t>(), counts.data_ptr<int64_t>(),
                                    with_value ? value.data_ptr() : nullptr, with_value ? value_s.data_ptr() : nullptr,
@@ -234,17 +204,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> sort_coalesce(Tensor row, Tensor col,
 // value in sorted order (valid when counts[3] == 0), value_u[E] (valid when counts[3] == 1)).
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coalesce_reduce(Tensor row, Tensor col, int64_t M, int64_t N,
                                                                       OptTensor opt_value, int64_t reduce) {
-  check_index(row, "row");
-  check_index(col, "col");
-  TORCH_CHECK(row.numel() == col.numel(), "row and col differ in length");
-  c10::hip::HIPGuard guard(row.get_device());
-  row = row.contiguous();
-  col = col.contiguous();
-  const int64_t E = row.numel();
+  CooArgs a(row, col);
+  const int64_t E = a.E;
   TORCH_CHECK(reduce >= 0 && reduce <= 3, "sort_coalesce_reduce: reduce must be 0 (sum), 1 (mean), 2 (min) or 3 (max)");
   // without a value: index only (seg_ptr is then meaningful on the one-sweep route only -- nobody needs it)
   const bool with_value = opt_value.has_value();
-  Tensor value, value_s = torch::empty({0}, row.options()), value_u = torch::empty({0}, row.options());
+  Tensor value, value_s = a.empty({0}), value_u = a.empty({0});
   bool is_float = true;
   if (with_value) {
     value = opt_value.value();
@@ -257,17 +222,17 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sort_coalesce_reduce(Tensor r
     value_s = torch::empty_like(value);
     value_u = torch::empty_like(value);
   }
-  Tensor index_u = torch::empty({2, E}, row.options());
+  Tensor index_u = a.empty({2, E});
   Tensor row_u = index_u.select(0, 0), col_u = index_u.select(0, 1);
-  Tensor row_t = torch::empty({E}, row.options()), col_t = torch::empty({E}, row.options());
-  Tensor seg = torch::empty({E + 1}, row.options()), counts = torch::empty({4}, row.options());
+  Tensor row_t = a.empty({E}), col_t = a.empty({E});
+  Tensor seg = a.empty({E + 1}), counts = a.empty({4});
   if (E == 0) {
     counts.zero_();
     seg.zero_();
     return std::make_tuple(index_u, seg, counts, value_s, value_u);
   }
   Tensor ws = workspace(tsamd_sort_coalesce_workspace_bytes(E), row);
-  check_status(tsamd_sort_coalesce_reduce(row.data_ptr<int64_t>(), col.data_ptr<int64_t>(), E, M, N,
+  check_status(tsamd_sort_coalesce_reduce(a.rowp(), a.colp(), E, M, N,
                                           row_t.data_ptr<int64_t>(), col_t.data_ptr<int64_t>(), row_u.data_ptr<int64_t>(),
                                           col_u.data_ptr<int64_t>(), seg.data_ptr<int64_t>(), counts.data_ptr<int64_t>(),
                                           is_float ? TSAMD_F32 : TSAMD_I32, (int)reduce,

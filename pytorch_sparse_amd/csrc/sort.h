@@ -1,15 +1,8 @@
 #pragma once
 #include "common.h"
 namespace tsamd {
-// Stable sort of COO entries by (row, col) -- the order of row * N + col -- see sort.hip.
-//   row_out / col_out (nullable): the sorted ids; perm_out: position of every sorted entry in the input.
-//   todo (nullable, device): number of descents of the input known from an earlier probe; 0 at run time = nothing to
-//     sort: every kernel returns at once and the finish kernel writes (copy, identity);
-//   probe: the build kernel counts descents / adjacent duplicates itself (counts_out[0..1], device), and the passes
-//     are decided by that count -- a sort decided on the device without a host sync.  check4: the probe also takes
-//     the maxima of the ids (as unsigned numbers) into counts_out[2..3] -- the range check of the constructor.
-//   gather_src / gather_dst (nullable): gather_dst[o] = gather_src[perm_out[o]] for arrays of 4- or 8-byte elements,
-//     written by the last pass (the values of the entries ride along instead of a gather through perm_out later).
+// Stable sort of COO entries by (row, col) -- the order of row * N + col -- see sort.hip.  One call descriptor
+// (SortCall) and one host driver (sort_coo_run) behind every entry point of the sort and of sort + coalesce.
 // Inputs are not modified; outputs must not alias them.  E < 2^32, bits(M) + bits(N) <= 64.
 // Ranking used by the radix kernels: 0 = one returning LDS atomic per entry (stable when the LDS unit serves the lanes
 // of one instruction in ascending order -- checked on the device by a self-test the first time this is called),
@@ -24,7 +17,8 @@ bool sort_coo_supported(int64_t E, int64_t M, int64_t N);
 //   and their number to co->nnz_out, and row_out / col_out / perm_out stay untouched; otherwise the one-sweep passes
 //   write row_out / col_out (/ perm_out, nullable) as usual and the CALLER compacts them (it can tell on the device:
 //   *sort_fast_flag(workspace, E) != 0 means the compacted outputs are already there).  co->status: nb words of scratch.
-//   Fused reduction (round 6): with a riding 4-byte value (gather_bytes == 4) and co->reduce >= 0 the bucket path also
+//   The one-launch sort (kSortSmall) compacts nothing, zeroes nothing and uses co->seg_ptr as its permutation.
+//   Fused reduction (round 6): with a riding 4-byte value (SortCall::bytes == 4) and co->reduce >= 0 the bucket path also
 //   REDUCES the values of every run -- sequentially in sorted order, in the accumulator type of
 //   segment_reduce_kernel, i.e. the same bits -- into co->value_u (capacity E, entry p = the p-th distinct pair),
 //   writes neither seg_ptr nor the sorted values, and sets *co->fused_out = 1 (the caller zeroes it beforehand).
@@ -43,9 +37,46 @@ struct SortCoalesce {
 };
 constexpr int kSortCoalesceStatusWords = 1 << 14;
 const unsigned long long *sort_fast_flag(void *workspace, int64_t E);
-int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N, int64_t *row_out,
-                      int64_t *col_out, int64_t *perm_out, const int64_t *todo, bool probe, int64_t *counts_out,
-                      void *workspace, hipStream_t stream, const void *gather_src = nullptr,
-                      void *gather_dst = nullptr, int gather_bytes = 0, bool check4 = false,
-                      const SortCoalesce *co = nullptr);
+
+// What decides whether the input is ordered at all -- on the device, without a host sync:
+enum class SortOrder {
+  kAlways,  // sort
+  kProbe,   // the sort's first read of the input counts descents / adjacent duplicates into counts[0..1] (device), and
+            // with 0 descents every later kernel returns at once: the outputs are a copy + the identity
+  kProbed,  // the same, decided by counts[0] (device) of an earlier probe (tsamd_coo_check); nothing is written to it
+};
+// The route the driver took (tsamd_sort_route reports the same numbers from the sizes alone).
+enum SortRoute {
+  kSortIdentity = 0,  // nothing to order: at most one entry, or keys of zero bits
+  kSortSmall = 1,     // the one-launch sort in LDS (plus a gather of the value through the permutation)
+  kSortGeneral = 2,   // build + bucket path / one-sweep passes; which of the two sorted is decided on the device
+};
+struct SortCall {
+  // input and outputs: row_out / col_out (nullable) the sorted ids, perm_out the position of every sorted entry in
+  // the input (nullable only for a compacting sort)
+  const int64_t *row, *col;
+  int64_t E, M, N;
+  int64_t *row_out, *col_out, *perm_out;
+  SortOrder order = SortOrder::kAlways;
+  int64_t *counts = nullptr;  // device; kProbe: written, kProbed: [0] read, kAlways: null
+  // kProbe only: the probe also takes the maxima of the ids (as unsigned numbers) into counts[2..3] -- the range
+  // check of the constructor.  Where it cannot ride in the build pass the driver launches tsamd_coo_check itself.
+  bool range_check = false;
+  // the riding value (both or neither): dst[o] = src[perm_out[o]] for arrays of 4- or 8-byte elements, written by
+  // the sort's last kernel instead of a gather through perm_out later
+  const void *src = nullptr;
+  void *dst = nullptr;
+  int64_t bytes = 0;
+  const SortCoalesce *co = nullptr;  // a compacting sort, see above
+  void *workspace = nullptr;         // sort_coo_workspace_bytes(E)
+  size_t workspace_bytes = 0;
+  // true: no workspace is asked for where the one-launch sort applies.  Kept for the C-ABI only: tsamd_sort_coo_auto /
+  // _probed have always accepted a missing workspace there, every other entry point refuses it at any size.
+  bool workspace_optional = false;
+  hipStream_t stream = nullptr;
+};
+// Validates (TSAMD_ERR_INVALID / _UNSUPPORTED / _WORKSPACE as the entry points of include/tsamd.h document), picks
+// the route and enqueues every launch of it; E == 0 is TSAMD_OK (kProbe: counts zeroed).  route_out (nullable): the
+// route taken, written whenever something was launched.
+int sort_coo_run(const SortCall &c, SortRoute *route_out = nullptr);
 }  // namespace tsamd

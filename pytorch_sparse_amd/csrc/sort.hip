@@ -1,4 +1,4 @@
-// Stable one-sweep LSD radix sort of COO entries on gfx950.
+// Stable radix sort of COO entries on gfx950: kernels, planning, host driver and entry points.
 //
 // Replaces the generic device sort the reference calls through `index_sort` / `torch.sort` when a
 // SparseStorage is built from unsorted COO, when csr2csc is computed and inside coalesce / transpose
@@ -6,7 +6,7 @@
 // build in front of it and the gathers / divisions behind it.  Unlike the reference's default `torch.sort` the
 // order of equal keys is stable.
 //
-// Design (round 4; the round 1-3 version took three launches per digit -- histogram, device scan, scatter --
+// The one-sweep passes (round 4; the round 1-3 version took three launches per digit -- histogram, device scan, scatter --
 // over 16-byte (key, payload) pairs plus a key-build and a decode pass: 1.39 GB of fabric traffic for 300 MB of
 // in + out bytes at 7.5 M entries, ~35 dispatches per coalesce):
 //   * key = (row << col_bits) | col  -- the same order as row * N + col without a multiply in front and a 64-bit
@@ -26,6 +26,17 @@
 //   * the last pass writes the sorted row / col / permutation themselves (shifts and masks).
 // 2 + passes launches (memset, build, passes), also for the device-decided variants; a value array can ride along in
 // the last pass (dst[o] = src[perm[o]], 4- or 8-byte elements) instead of being gathered through the permutation later.
+//
+// Map of this file, in order:
+//   build         sort_build_kernel: words / keys, every pass's digit histogram, the bucket histogram, the order probe
+//   plan          bucket_plan_kernel: bucket offsets and the device-side decision between the next two (hdr[kHdrFast])
+//   passes        onesweep_pass_kernel (as above), sort_identity_kernel, the ranking self-test
+//   bucket path   (round 6) bucket_scatter_kernel + bucket_sort_kernel: one most-significant-digit scatter and one sort
+//                 of every bucket inside LDS, instead of the passes, when every bucket fits
+//   small sort    small_sort_coo_kernel: up to 8192 entries with keys below 2^32 in ONE launch
+//   host plan     layout_for, plan_buckets, sort_bits_for, carve_sort, sort_plan: everything decided from the sizes
+//   driver        sort_coo_run (sort.h: SortCall): validation, the route, every fill and launch, idle ones included
+//   entry points  tsamd_sort_route, tsamd_sort_coo*, tsamd_sort_rank_mode (tsamd_sort_coalesce*: coalesce.hip)
 #include "common.h"
 #include "sort.h"
 
@@ -1442,6 +1453,164 @@ __global__ __launch_bounds__(THREADS, (2 * THREADS / 256)) void bucket_sort_kern
   }
 }
 
+int key_bits_for(int64_t rows, int64_t cols) {
+  // keys are < rows * cols
+  unsigned __int128 lim = (unsigned __int128)(rows > 0 ? rows : 1) * (unsigned __int128)(cols > 0 ? cols : 1);
+  int bits = 0;
+  while (bits < 63 && ((unsigned __int128)1 << bits) < lim) ++bits;
+  return bits;
+}
+
+// ---------------------------------------------------------------------------
+// Small inputs: the whole sort_coo in ONE launch.  A COO set of a few thousand entries (a mini-batch
+// sub-graph, BASELINE config 1) spends its time in ~16 dependent launches of the general path (probe, keys,
+// (histogram, scan, scatter) per digit, decode: ~4 us each on the GPU, a HIP graph replays them no faster).
+// Here one 1024-thread workgroup keeps the (32-bit key, 16-bit index) pairs of up to 8192 entries in LDS and
+// runs every 8-bit LSD pass there: per-wave match ranking (8 ballots per key, stable), per-wave digit counts,
+// one scan over the 256 digits, scatter into the other LDS buffer.  Needs row * N + col < 2^32.
+// counts (nullable): [#descents, #adjacent duplicates] of the input (lexicographic); with `auto_mode` an input
+// without descents skips the passes (outputs = copy + identity), exactly like tsamd_sort_coo_auto.
+// ---------------------------------------------------------------------------
+constexpr int kSmallSortThreads = 1024;
+constexpr int kSmallSortItems = 8;
+constexpr int kSmallSortMax = kSmallSortThreads * kSmallSortItems;  // 8192
+
+__global__ __launch_bounds__(kSmallSortThreads) void small_sort_coo_kernel(
+    const int64_t *__restrict__ row, const int64_t *__restrict__ col, int n, uint32_t ncols, int passes,
+    int64_t *__restrict__ row_out, int64_t *__restrict__ col_out, int64_t *__restrict__ perm_out,
+    unsigned long long *__restrict__ counts, int auto_mode) {
+  __shared__ uint32_t kbuf[2][kSmallSortMax];
+  __shared__ uint16_t vbuf[2][kSmallSortMax];
+  __shared__ uint32_t cnt[kSmallSortThreads / 64][256];
+  __shared__ uint32_t dig_off[256];
+  __shared__ uint32_t wsum[4];
+  __shared__ unsigned int s_order[2];
+  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid < 2) s_order[tid] = 0;
+  __syncthreads();
+  // load, build keys, probe the order
+  unsigned int desc = 0, dup = 0;
+#pragma unroll
+  for (int j = 0; j < kSmallSortItems; ++j) {
+    const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
+    if (i < n) {
+      const int64_t r = row[i], c = col[i];
+      kbuf[0][i] = (uint32_t)((uint64_t)r * ncols + (uint64_t)c);
+      vbuf[0][i] = (uint16_t)i;
+      if (i > 0) {
+        const int64_t pr = row[i - 1], pc = col[i - 1];
+        desc += (r < pr) || (r == pr && c < pc);
+        dup += (r == pr) && (c == pc);
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    desc += lane_xor(desc, off);
+    dup += lane_xor(dup, off);
+  }
+  if (lane == 0) {
+    if (desc) atomicAdd(&s_order[0], desc);
+    if (dup) atomicAdd(&s_order[1], dup);
+  }
+  __syncthreads();
+  if (counts != nullptr && tid < 2) counts[tid] = s_order[tid];
+  const bool skip = auto_mode != 0 && s_order[0] == 0;
+  int cur = 0;
+  for (int pass = 0; pass < passes && !skip; ++pass) {
+    const int shift = pass * 8;
+    const uint32_t *ks = kbuf[cur];
+    const uint16_t *vs = vbuf[cur];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cnt[w][q * 64 + lane] = 0;  // this wave's counters (wave-local: no barrier)
+    uint32_t key[kSmallSortItems], lrank[kSmallSortItems];
+    uint16_t val[kSmallSortItems];
+#pragma unroll
+    for (int j = 0; j < kSmallSortItems; ++j) {
+      const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
+      const bool valid = i < n;
+      key[j] = valid ? ks[i] : 0u;
+      val[j] = valid ? vs[i] : (uint16_t)0;
+      const uint32_t d = (key[j] >> shift) & 255u;
+      unsigned long long peers = __ballot(valid);
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long m = __ballot(valid && bit);
+        peers &= bit ? m : ~m;
+      }
+      const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+      const int leader = valid ? (__ffsll((long long)peers) - 1) : lane;
+      uint32_t pre = 0;
+      if (valid && lane == leader) {
+        pre = cnt[w][d];
+        cnt[w][d] = pre + (uint32_t)__popcll(peers);
+      }
+      pre = lane_read(pre, leader);
+      lrank[j] = pre + rank;
+    }
+    __syncthreads();
+    if (tid < 256) {  // thread t owns digit t: exclusive prefix over the waves, then over the digits
+      uint32_t run = 0;
+#pragma unroll
+      for (int ww = 0; ww < kSmallSortThreads / 64; ++ww) {
+        const uint32_t c = cnt[ww][tid];
+        cnt[ww][tid] = run;
+        run += c;
+      }
+      uint32_t inc = run;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = lane_read(inc, lane >= off ? lane - off : lane);
+        if (lane >= off) inc += o;
+      }
+      if (lane == 63) wsum[w] = inc;
+      dig_off[tid] = inc - run;  // exclusive inside the wave; the wave bases are added below
+    }
+    __syncthreads();
+    if (tid < 256) {
+      uint32_t base = 0;
+      for (int ww = 0; ww < w; ++ww) base += wsum[ww];
+      dig_off[tid] += base;
+    }
+    __syncthreads();
+    uint32_t *kd = kbuf[cur ^ 1];
+    uint16_t *vd = vbuf[cur ^ 1];
+#pragma unroll
+    for (int j = 0; j < kSmallSortItems; ++j) {
+      const int i = w * (64 * kSmallSortItems) + j * 64 + lane;
+      if (i < n) {
+        const uint32_t d = (key[j] >> shift) & 255u;
+        const uint32_t pos = dig_off[d] + cnt[w][d] + lrank[j];
+        kd[pos] = key[j];
+        vd[pos] = val[j];
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  for (int i = tid; i < n; i += kSmallSortThreads) {
+    if (skip) {
+      if (row_out) row_out[i] = row[i];
+      if (col_out) col_out[i] = col[i];
+      perm_out[i] = i;
+    } else {
+      const uint32_t k = kbuf[cur][i];
+      const uint32_t r = k / ncols;
+      if (row_out) row_out[i] = (int64_t)r;
+      if (col_out) col_out[i] = (int64_t)(k - r * ncols);
+      perm_out[i] = (int64_t)vbuf[cur][i];
+    }
+  }
+}
+
+// 8-bit passes of the one-launch sort over keys of key_bits_for(M, N) bits; -1 = it does not apply
+int small_sort_passes(int64_t E, int64_t M, int64_t N) {
+  if (E > kSmallSortMax || N <= 0 || N >= ((int64_t)1 << 32)) return -1;
+  const int bits = key_bits_for(M, N);
+  if (bits > 32) return -1;
+  return E > 1 ? (bits + 7) / 8 : 0;
+}
+
 KeyLayout layout_for(int64_t E, int64_t M, int64_t N) {
   KeyLayout L;
   L.col_bits = bits_for(N > 0 ? N : 1);
@@ -1560,7 +1729,7 @@ size_t carve_sort(void *base, int64_t E, SortWs *ws) {
   w.hdr = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * kHdrWords));
   w.hist = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * kMaxPasses * kRadix));
   w.tile_state = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * ntiles * kRadix));
-  w.zero_bytes = off;  // (+ the part of bhist a plan uses: sort_coo_onesweep)
+  w.zero_bytes = off;  // (+ the part of bhist a plan uses: sort_coo_run)
   w.bhist = reinterpret_cast<unsigned int *>(take(sizeof(unsigned int) * kBkMaxHist * kBkHistCopies));
   w.boff = reinterpret_cast<unsigned int *>(take(sizeof(unsigned int) * (kBkMaxHist + 1)));
   w.cursor = reinterpret_cast<unsigned int *>(take(sizeof(unsigned int) * kBkMaxHist));
@@ -1574,6 +1743,35 @@ size_t carve_sort(void *base, int64_t E, SortWs *ws) {
   return off;
 }
 
+// What the driver decides from the sizes alone (tsamd_sort_route reports it, tests/test_sort_route.py pins it).
+struct SortPlan {
+  KeyLayout L;
+  bool identity;   // nothing to order (at most one entry, or a 1 x 1 matrix: every key is equal)
+  bool ride;       // a 4-byte value rides through the passes of a packed sort
+  int64_t ntiles;  // workgroups of a pass kernel
+  BucketPlan B;
+};
+SortPlan sort_plan(int64_t E, int64_t M, int64_t N, int64_t value_bytes, bool compacting) {
+  SortPlan P;
+  P.L = layout_for(E, M, N);
+  P.identity = P.L.passes == 0 || E <= 1;
+  const bool want4 = value_bytes == 4;
+  P.ride = P.L.packed && want4 && P.L.passes >= 2;
+  P.ntiles = ceil_div(E, kSortThreads * (P.L.packed ? (P.ride ? kItemsOf<true, true> : kItemsOf<true>) : kItemsOf<false>));
+  P.B = plan_buckets(E, M, N, P.L, want4);
+  // a compacting sort needs buckets that end where keys end (the bucket id inside the key bits)
+  if (compacting && P.B.on && !P.B.strip && P.B.shift < P.L.idx_bits) P.B.on = 0;
+  return P;
+}
+
+// A run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}) -- the kernels' template
+// arguments are picked where the launch is written.
+template <typename F>
+void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 // 0 = returning LDS atomics are a stable rank (checked on the device), 1 = ballot matching; -1 = not decided yet
 std::atomic<int> g_rank_mode{-1};
 std::mutex g_rank_mutex;
@@ -1581,7 +1779,7 @@ std::mutex g_rank_mutex;
 }  // namespace
 
 // The ranking the radix kernels use.  The first call runs `sort_selftest_kernel` (one synchronising round trip of
-// a few words; callers that must not synchronise -- stream capture -- call tsamd_sort_selftest() beforehand, the
+// a few words; callers that must not synchronise -- stream capture -- call tsamd_sort_rank_mode(-1) beforehand, the
 // Python package does at import).
 int sort_rank_mode(hipStream_t) {
   int m = g_rank_mode.load(std::memory_order_acquire);
@@ -1624,27 +1822,79 @@ bool sort_coo_supported(int64_t E, int64_t M, int64_t N) {
          (bits_for(M > 0 ? M : 1) + bits_for(N > 0 ? N : 1) + kRadixBits - 1) / kRadixBits <= kMaxPasses;
 }
 
-int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N, int64_t *row_out,
-                      int64_t *col_out, int64_t *perm_out, const int64_t *todo, bool probe, int64_t *counts_out,
-                      void *workspace, hipStream_t stream, const void *gather_src, void *gather_dst,
-                      int gather_bytes, bool check4, const SortCoalesce *co) {
-  if (E <= 0) return TSAMD_OK;
+// ---------------------------------------------------------------------------
+// driver: validation, the route, every launch of a sort (sort.h: SortCall)
+// ---------------------------------------------------------------------------
+int sort_coo_run(const SortCall &c, SortRoute *route_out) {
+  const int64_t *const row = c.row, *const col = c.col;
+  const int64_t E = c.E, M = c.M, N = c.N;
+  int64_t *const row_out = c.row_out, *const col_out = c.col_out, *const perm_out = c.perm_out;
+  hipStream_t stream = c.stream;
+  const SortCoalesce *const co = c.co;
+  if (E < 0 || M < 0 || N < 0) return TSAMD_ERR_INVALID;
+  // the combinations SortCall cannot rule out by its types: counts exactly with a decision that uses them, the range
+  // check only in a probe, the riding value's two ends together
+  if ((c.order != SortOrder::kAlways) != (c.counts != nullptr) || (c.range_check && c.order != SortOrder::kProbe))
+    return TSAMD_ERR_INVALID;
+  if ((c.src == nullptr) != (c.dst == nullptr)) return TSAMD_ERR_INVALID;
+  if (c.src != nullptr && c.bytes != 4 && c.bytes != 8) return TSAMD_ERR_UNSUPPORTED;
+  if (E == 0) {
+    if (c.order == SortOrder::kProbe)
+      TSAMD_HIP_TRY(hipMemsetAsync(c.counts, 0, (c.range_check ? 4 : 2) * sizeof(int64_t), stream));
+    return TSAMD_OK;
+  }
+  // (a compacting sort has no permutation to deliver: the one-launch sort, which must write one, borrows seg_ptr, which
+  // the caller's compaction rewrites afterwards)
+  if (!row || !col || (!perm_out && !co)) return TSAMD_ERR_INVALID;
   if (!sort_coo_supported(E, M, N)) return TSAMD_ERR_UNSUPPORTED;
-  const KeyLayout L = layout_for(E, M, N);
-  const unsigned int eblocks = (unsigned int)ceil_div(E, 256);
-  if (gather_dst != nullptr && (gather_src == nullptr || (gather_bytes != 4 && gather_bytes != 8))) return TSAMD_ERR_INVALID;
+  const int small_passes = small_sort_passes(E, M, N);
+  if (!(small_passes >= 0 && c.workspace_optional) && (!c.workspace || c.workspace_bytes < sort_coo_workspace_bytes(E)))
+    return TSAMD_ERR_WORKSPACE;
+  const SortPlan P = sort_plan(E, M, N, c.dst != nullptr ? c.bytes : 0, co != nullptr);
+  SortOrder order = c.order;
+  bool check4 = c.range_check;
+  // the constructor's range check (max row / col id) rides in the sort's build pass -- except at the sizes of the
+  // one-launch path and for keys of zero bits, where the check is its own (tiny) launch and the sort runs "probed".
+  // (Deliberately not `small_passes >= 0`: at E <= kSmallSortMax with keys too wide for the one-launch sort the check
+  // has always been its own launch in front of the general path, and the sequence of launches stays what it was.)
+  if (check4 && (E <= kSmallSortMax || P.identity)) {
+    int st = tsamd_coo_check(row, col, E, c.counts, stream);
+    if (st != TSAMD_OK) return st;
+    order = SortOrder::kProbed;
+    check4 = false;
+  }
+  const bool probe = order == SortOrder::kProbe;
+  const int64_t *const todo = order == SortOrder::kProbed ? c.counts : nullptr;
+  int64_t *const counts_out = probe ? c.counts : nullptr;
+  if (small_passes >= 0) {
+    // probe, sort and decode in one launch (the small kernel probes for itself: an earlier probe's count is not read)
+    int64_t *const perm = perm_out ? perm_out : co->seg_ptr;
+    hipLaunchKernelGGL(small_sort_coo_kernel, dim3(1), dim3(kSmallSortThreads), 0, stream, row, col, (int)E,
+                       (uint32_t)N, small_passes, row_out, col_out, perm,
+                       reinterpret_cast<unsigned long long *>(counts_out), order != SortOrder::kAlways ? 1 : 0);
+    TSAMD_LAUNCH_CHECK();
+    if (route_out) *route_out = kSortSmall;
+    if (c.dst != nullptr)  // the one-launch path has no payload: a gather through the permutation behind it
+      return tsamd_gather_rows(c.src, perm, c.dst, E, E, c.bytes, stream);
+    return TSAMD_OK;
+  }
+  if (route_out) *route_out = P.identity ? kSortIdentity : kSortGeneral;
+  const KeyLayout L = P.L;
+  const void *const gather_src = c.src;
+  void *const gather_dst = c.dst;
+  const int gather_bytes = (int)c.bytes;
   SortWs ws;
-  carve_sort(workspace, E, &ws);
+  carve_sort(c.workspace, E, &ws);
   const size_t pre_zero = co != nullptr ? co->pre_zero_bytes : 0;
   char *const zero_from = reinterpret_cast<char *>(ws.hdr) - pre_zero;
-  if (L.passes == 0 || E == 1) {  // nothing to order (a 1 x 1 matrix: every key is equal)
+  if (P.identity) {  // nothing to order
     TSAMD_HIP_TRY(hipMemsetAsync(zero_from, 0, pre_zero + sizeof(unsigned long long) * kHdrWords, stream));  // (kHdrFast = 0 for a caller that asks)
-    if (probe && counts_out != nullptr) {
-      const int64_t c[2] = {0, E - 1};  // no descent, every adjacent pair a duplicate
-      TSAMD_HIP_TRY(hipMemcpyAsync(counts_out, c, sizeof(c), hipMemcpyHostToDevice, stream));
+    if (probe) {
+      const int64_t cnt[2] = {0, E - 1};  // no descent, every adjacent pair a duplicate
+      TSAMD_HIP_TRY(hipMemcpyAsync(counts_out, cnt, sizeof(cnt), hipMemcpyHostToDevice, stream));
     }
-    hipLaunchKernelGGL(sort_identity_kernel, dim3(eblocks), dim3(256), 0, stream, row, col, E, row_out, col_out,
-                       perm_out);
+    hipLaunchKernelGGL(sort_identity_kernel, dim3((unsigned int)ceil_div(E, 256)), dim3(256), 0, stream, row, col, E,
+                       row_out, col_out, perm_out);
     TSAMD_LAUNCH_CHECK();
     if (gather_dst != nullptr)
       TSAMD_HIP_TRY(hipMemcpyAsync(gather_dst, gather_src, (size_t)E * gather_bytes, hipMemcpyDeviceToDevice, stream));
@@ -1652,24 +1902,18 @@ int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t
   }
   // a 4-byte value array rides through the passes of a packed sort / through the bucket kernels
   const bool want4 = gather_dst != nullptr && gather_bytes == 4;
-  const bool ride = L.packed && want4 && L.passes >= 2;
-  const int64_t ntiles = ceil_div(E, kSortThreads * (L.packed ? (ride ? kItemsOf<true, true> : kItemsOf<true>) : kItemsOf<false>));
-  BucketPlan B = plan_buckets(E, M, N, L, want4);
-  // a compacting sort needs buckets that end where keys end (the bucket id inside the key bits)
-  if (co != nullptr && B.on && !B.strip && B.shift < L.idx_bits) B.on = 0;
+  const BucketPlan B = P.B;
   const bool ballot = sort_rank_mode(stream) == 1;
+  const int probe_arg = probe ? (check4 ? 2 : 1) : 0;
   TSAMD_HIP_TRY(hipMemsetAsync(zero_from, 0, pre_zero + ws.zero_bytes + (B.on ? sizeof(unsigned int) * (size_t)B.nb * kBkHistCopies : 0), stream));
-  int build_wgs = 1;
-  {
-    const int64_t nb = ceil_div(E, kBuildThreads * 4);
-    build_wgs = (int)(nb < kBuildMaxWgs ? nb : kBuildMaxWgs);
-    hipLaunchKernelGGL(sort_build_kernel, dim3((unsigned int)build_wgs), dim3(kBuildThreads), 0, stream,
-                       row, col, E, L, ws.a, ws.hist, ws.hdr, todo, probe ? (check4 ? 2 : 1) : 0, B, ws.bhist, ws.wgstat);
-    TSAMD_LAUNCH_CHECK();
-  }
+  const int64_t build_nb = ceil_div(E, kBuildThreads * 4);
+  const int build_wgs = (int)(build_nb < kBuildMaxWgs ? build_nb : kBuildMaxWgs);
+  hipLaunchKernelGGL(sort_build_kernel, dim3((unsigned int)build_wgs), dim3(kBuildThreads), 0, stream,
+                     row, col, E, L, ws.a, ws.hist, ws.hdr, todo, probe_arg, B, ws.bhist, ws.wgstat);
+  TSAMD_LAUNCH_CHECK();
   if (B.on) {
     hipLaunchKernelGGL(bucket_plan_kernel, dim3(1), dim3(kBuildThreads), 0, stream, ws.bhist, ws.boff, ws.cursor,
-                       ws.cursor1, ws.hdr, todo, probe ? (check4 ? 2 : 1) : 0, B, E, ws.wgstat, build_wgs);
+                       ws.cursor1, ws.hdr, todo, probe_arg, B, E, ws.wgstat, build_wgs);
     TSAMD_LAUNCH_CHECK();
     // bucket path: scatter into ws.b (two levels: on into ws.a), sort every bucket in LDS, write the outputs.  These
     // kernels return at once unless the plan kernel raised hdr[kHdrFast]; the passes below return at once when it did (~5 us
@@ -1679,26 +1923,27 @@ int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t
     // five (sort 0.195 -> 0.179 ms at 7.5 M entries) but 1.5 instead of 1.0 ms on the 21 M-entry R-MAT input that needs it).
     const SortBits SB = sort_bits_for(B.shift);
     const unsigned int *vin = reinterpret_cast<const unsigned int *>(gather_src);
-    unsigned int *cur1 = B.levels == 2 ? ws.cursor1 : ws.cursor;
-#define TSAMD_BK_SCATTER(V, LV, ST, SRC, DST, CUR)                                                                            \
-  hipLaunchKernelGGL((bucket_scatter_kernel<V, LV, ST>), dim3((unsigned int)ceil_div(E, kBkScatterThreads * kBkScatterItems<V>)), \
-                     dim3(kBkScatterThreads), 0, stream, SRC, vin, E, B, L, ws.boff, CUR, DST, ws.hdr)
-    if (B.strip) {
-      if (want4) TSAMD_BK_SCATTER(true, 1, true, ws.a, ws.b, cur1);
-      else TSAMD_BK_SCATTER(false, 1, true, ws.a, ws.b, cur1);
-    } else {
-      if (want4) TSAMD_BK_SCATTER(true, 1, false, ws.a, ws.b, cur1);
-      else TSAMD_BK_SCATTER(false, 1, false, ws.a, ws.b, cur1);
-    }
+    auto scatter = [&](auto val, auto level, auto strip, const unsigned long long *in, unsigned long long *out,
+                       unsigned int *cur) {
+      constexpr bool V = decltype(val)::value;
+      hipLaunchKernelGGL((bucket_scatter_kernel<V, decltype(level)::value, decltype(strip)::value>),
+                         dim3((unsigned int)ceil_div(E, kBkScatterThreads * kBkScatterItems<V>)), dim3(kBkScatterThreads), 0,
+                         stream, in, vin, E, B, L, ws.boff, cur, out, ws.hdr);
+    };
+    with_bool(want4, [&](auto val) {
+      with_bool(B.strip != 0, [&](auto strip) {
+        scatter(val, std::integral_constant<int, 1>{}, strip, ws.a, ws.b, B.levels == 2 ? ws.cursor1 : ws.cursor);
+      });
+    });
     TSAMD_LAUNCH_CHECK();
     const unsigned long long *sorted_in = ws.b;
-    if (B.levels == 2) {
-      if (want4) TSAMD_BK_SCATTER(true, 2, true, ws.b, ws.a, ws.cursor);
-      else TSAMD_BK_SCATTER(false, 2, true, ws.b, ws.a, ws.cursor);
+    if (B.levels == 2) {  // (strip mode only)
+      with_bool(want4, [&](auto val) {
+        scatter(val, std::integral_constant<int, 2>{}, std::true_type{}, ws.b, ws.a, ws.cursor);
+      });
       TSAMD_LAUNCH_CHECK();
       sorted_in = ws.a;
     }
-#undef TSAMD_BK_SCATTER
     CoalesceOut Co{nullptr, nullptr, nullptr, E, nullptr, nullptr, -1, 1};
     if (co != nullptr) {
       if (pre_zero == 0) TSAMD_HIP_TRY(hipMemsetAsync(co->status, 0, sizeof(unsigned long long) * (size_t)B.nb, stream));
@@ -1712,27 +1957,21 @@ int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t
         Co.is_float = co->is_float;
       }
     }
-#define TSAMD_BK_SORT(ITEMS, V, BAL)                                                                                     \
-  do {                                                                                                                   \
-    if (co != nullptr)                                                                                                   \
-      hipLaunchKernelGGL((bucket_sort_kernel<TSAMD_BK_SORT_THREADS, ITEMS, V, BAL, true>), dim3((unsigned int)B.nb),     \
-                         dim3(TSAMD_BK_SORT_THREADS), 0, stream, sorted_in, (const unsigned int *)nullptr, ws.boff, SB, L, \
-                         B, co->row_u, co->col_u, (int64_t *)nullptr, ws.hdr, probe ? counts_out : (int64_t *)nullptr,   \
-                         check4 ? 1 : 0, gather_src, gather_dst, gather_bytes, Co);                                      \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((bucket_sort_kernel<TSAMD_BK_SORT_THREADS, ITEMS, V, BAL>), dim3((unsigned int)B.nb),           \
-                         dim3(TSAMD_BK_SORT_THREADS), 0, stream, sorted_in, (const unsigned int *)nullptr, ws.boff, SB, L, \
-                         B, row_out, col_out, perm_out, ws.hdr, probe ? counts_out : (int64_t *)nullptr, check4 ? 1 : 0, \
-                         gather_src, gather_dst, gather_bytes, Co);                                                      \
-  } while (0)
-    if (want4) {
-      if (ballot) TSAMD_BK_SORT(TSAMD_BK_SORT_ITEMS_VAL, true, true);
-      else TSAMD_BK_SORT(TSAMD_BK_SORT_ITEMS_VAL, true, false);
-    } else {
-      if (ballot) TSAMD_BK_SORT(TSAMD_BK_SORT_ITEMS, false, true);
-      else TSAMD_BK_SORT(TSAMD_BK_SORT_ITEMS, false, false);
-    }
-#undef TSAMD_BK_SORT
+    // a compacting sort writes the distinct pairs and no permutation
+    int64_t *const b_row = co != nullptr ? co->row_u : row_out, *const b_col = co != nullptr ? co->col_u : col_out;
+    int64_t *const b_perm = co != nullptr ? nullptr : perm_out;
+    with_bool(want4, [&](auto val) {
+      with_bool(ballot, [&](auto bal) {
+        with_bool(co != nullptr, [&](auto coal) {
+          constexpr bool V = decltype(val)::value;
+          hipLaunchKernelGGL((bucket_sort_kernel<TSAMD_BK_SORT_THREADS, V ? TSAMD_BK_SORT_ITEMS_VAL : TSAMD_BK_SORT_ITEMS, V,
+                                                 decltype(bal)::value, decltype(coal)::value>),
+                             dim3((unsigned int)B.nb), dim3(TSAMD_BK_SORT_THREADS), 0, stream, sorted_in,
+                             (const unsigned int *)nullptr, ws.boff, SB, L, B, b_row, b_col, b_perm, ws.hdr, counts_out,
+                             check4 ? 1 : 0, gather_src, gather_dst, gather_bytes, Co);
+        });
+      });
+    });
     TSAMD_LAUNCH_CHECK();
   }
   // the passes of a probing sort are decided by the probe's own counter
@@ -1744,36 +1983,20 @@ int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t
     unsigned long long *dst = (src == ws.a) ? ws.b : ws.a;
     unsigned int *idst = (isrc == ws.ia) ? ws.ib : ws.ia;
     const int shift = pass * kRadixBits + (L.packed ? L.idx_bits : 0);
-#define TSAMD_SORT_PASS(P, LST)                                                                                     \
-  if (ballot) TSAMD_SORT_PASS_(P, LST, true); else TSAMD_SORT_PASS_(P, LST, false)
-#define TSAMD_SORT_PASS_(P, LST, BAL)                                                                                     \
-  hipLaunchKernelGGL((onesweep_pass_kernel<P, LST, false, BAL>), dim3((unsigned int)ntiles), dim3(kSortThreads), 0, stream, src, \
-                     isrc, dst, idst, row_out, col_out, perm_out, E, shift, L, ws.hist + pass * kRadix,              \
-                     ws.tile_state, ws.hdr, (unsigned int)(pass + 1), pass_todo, row, col,                          \
-                     (last && probe) ? counts_out : (int64_t *)nullptr, gather_src, gather_dst, gather_bytes,          \
-                     check4 ? 1 : 0)
-    if (ride) {
-#define TSAMD_SORT_PASS_VAL(LST)                                                                                      \
-  if (ballot) TSAMD_SORT_PASS_VAL_(LST, true); else TSAMD_SORT_PASS_VAL_(LST, false)
-#define TSAMD_SORT_PASS_VAL_(LST, BAL)                                                                                      \
-  hipLaunchKernelGGL((onesweep_pass_kernel<true, LST, true, BAL>), dim3((unsigned int)ntiles), dim3(kSortThreads), 0,      \
-                     stream, src, isrc, dst, idst, row_out, col_out, perm_out, E, shift, L, ws.hist + pass * kRadix,  \
-                     ws.tile_state, ws.hdr, (unsigned int)(pass + 1), pass_todo, row, col,                           \
-                     (last && probe) ? counts_out : (int64_t *)nullptr, gather_src, gather_dst, gather_bytes,           \
-                     check4 ? 1 : 0)
-      if (last) { TSAMD_SORT_PASS_VAL(true); }
-      else { TSAMD_SORT_PASS_VAL(false); }
-#undef TSAMD_SORT_PASS_VAL
-#undef TSAMD_SORT_PASS_VAL_
-    } else if (L.packed) {
-      if (last) { TSAMD_SORT_PASS(true, true); }
-      else { TSAMD_SORT_PASS(true, false); }
-    } else {
-      if (last) { TSAMD_SORT_PASS(false, true); }
-      else { TSAMD_SORT_PASS(false, false); }
-    }
-#undef TSAMD_SORT_PASS
-#undef TSAMD_SORT_PASS_
+    auto launch_pass = [&](auto packed, auto val) {
+      with_bool(last, [&](auto lst) {
+        with_bool(ballot, [&](auto bal) {
+          hipLaunchKernelGGL((onesweep_pass_kernel<decltype(packed)::value, decltype(lst)::value, decltype(val)::value,
+                                                   decltype(bal)::value>),
+                             dim3((unsigned int)P.ntiles), dim3(kSortThreads), 0, stream, src, isrc, dst, idst, row_out,
+                             col_out, perm_out, E, shift, L, ws.hist + pass * kRadix, ws.tile_state, ws.hdr,
+                             (unsigned int)(pass + 1), pass_todo, row, col, last ? counts_out : (int64_t *)nullptr,
+                             gather_src, gather_dst, gather_bytes, check4 ? 1 : 0);
+        });
+      });
+    };
+    if (P.ride) launch_pass(std::true_type{}, std::true_type{});  // (only packed words carry a value)
+    else with_bool(L.packed, [&](auto packed) { launch_pass(packed, std::false_type{}); });
     TSAMD_LAUNCH_CHECK();
     src = dst;
     isrc = idst;
@@ -1782,3 +2005,96 @@ int sort_coo_onesweep(const int64_t *row, const int64_t *col, int64_t E, int64_t
 }
 
 }  // namespace tsamd
+
+using namespace tsamd;
+
+// ---------------------------------------------------------------------------
+// entry points (include/tsamd.h): what is specific to each, then a SortCall
+// ---------------------------------------------------------------------------
+extern "C" int tsamd_sort_route(int64_t E, int64_t M, int64_t N, int value_bytes, int coalesce, int64_t out[16]) {
+  if (!out || E < 0 || M < 0 || N < 0 || (value_bytes != 0 && value_bytes != 4 && value_bytes != 8))
+    return TSAMD_ERR_INVALID;
+  if (!sort_coo_supported(E, M, N)) return TSAMD_ERR_UNSUPPORTED;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  const int small_passes = small_sort_passes(E, M, N);
+  if (E > 0 && small_passes >= 0) {  // (the driver tries the one-launch sort first)
+    out[0] = kSortSmall;
+    out[1] = key_bits_for(M, N);
+    out[4] = small_passes;
+    return TSAMD_OK;
+  }
+  const SortPlan P = sort_plan(E, M, N, value_bytes, coalesce != 0);
+  const int64_t v[16] = {P.identity ? kSortIdentity : kSortGeneral, P.L.key_bits, P.L.idx_bits, P.L.packed, P.L.passes,
+                         P.ride, P.ntiles, P.B.on, P.B.levels, P.B.strip, P.B.bits, P.B.bits1, P.B.kshift, P.B.shift, P.B.nb, P.B.cap};
+  for (int i = 0; i < (P.identity ? 5 : P.B.on ? 16 : 7); ++i) out[i] = v[i];
+  return TSAMD_OK;
+}
+
+extern "C" size_t tsamd_sort_coo_workspace_bytes(int64_t E) { return sort_coo_workspace_bytes(E); }
+
+extern "C" int tsamd_sort_rank_mode(int set) {
+  if (set == 0 || set == 1) sort_set_rank_mode(set);
+  else if (set == 2) sort_set_rank_mode(-1);
+  return sort_rank_mode(nullptr);
+}
+
+// the fields every entry point fills alike
+static SortCall sort_call(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N, int64_t *row_out,
+                          int64_t *col_out, int64_t *perm_out, void *workspace, size_t workspace_bytes, void *stream_) {
+  SortCall c{row, col, E, M, N, row_out, col_out, perm_out};
+  c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes;
+  c.stream = reinterpret_cast<hipStream_t>(stream_);
+  return c;
+}
+
+extern "C" int tsamd_sort_coo(const int64_t *row, const int64_t *col, int64_t E, int64_t M,
+                              int64_t N, int64_t *row_out, int64_t *col_out, int64_t *perm_out,
+                              void *workspace, size_t workspace_bytes, void *stream_) {
+  return sort_coo_run(sort_call(row, col, E, M, N, row_out, col_out, perm_out, workspace, workspace_bytes, stream_));
+}
+
+// sort_coo decided on the device: counts_out[0..1] = (#descents, #adjacent duplicates) of the INPUT; when
+// there is no descent the radix passes return at once and the outputs are a copy + the identity.  The build kernel
+// counts the descents itself: one read of the input serves the probe, the keys and the digit histograms.
+// (This entry and the next never asked for a workspace where the one-launch sort applies.)
+extern "C" int tsamd_sort_coo_auto(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
+                                   int64_t *row_out, int64_t *col_out, int64_t *perm_out,
+                                   int64_t *counts_out, void *workspace, size_t workspace_bytes,
+                                   void *stream_) {
+  SortCall c = sort_call(row, col, E, M, N, row_out, col_out, perm_out, workspace, workspace_bytes, stream_);
+  c.order = SortOrder::kProbe;
+  c.counts = counts_out;
+  c.workspace_optional = true;
+  return sort_coo_run(c);
+}
+
+// The same with the order already probed: descents[0] (device) = #descents of the input, e.g. counts[0] of
+// tsamd_coo_check -- the constructor enqueues check, sort and gathers back to back and reads the check's
+// result once everything is in flight.
+extern "C" int tsamd_sort_coo_probed(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
+                                     int64_t *row_out, int64_t *col_out, int64_t *perm_out,
+                                     const int64_t *descents, void *workspace, size_t workspace_bytes,
+                                     void *stream_) {
+  SortCall c = sort_call(row, col, E, M, N, row_out, col_out, perm_out, workspace, workspace_bytes, stream_);
+  c.order = SortOrder::kProbed;
+  c.counts = const_cast<int64_t *>(descents);
+  c.workspace_optional = true;
+  return sort_coo_run(c);
+}
+
+// One entry point for the three flavours with the entries' values riding along (include/tsamd.h).
+extern "C" int tsamd_sort_coo_values(int mode, const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
+                                     int64_t *row_out, int64_t *col_out, int64_t *perm_out, int64_t *counts,
+                                     const void *value, void *value_out, int64_t value_bytes, void *workspace,
+                                     size_t workspace_bytes, void *stream_) {
+  if (mode < 0 || mode > 3 || (mode != 0 && !counts)) return TSAMD_ERR_INVALID;
+  SortCall c = sort_call(row, col, E, M, N, row_out, col_out, perm_out, workspace, workspace_bytes, stream_);
+  c.order = mode == 0 ? SortOrder::kAlways : mode == 2 ? SortOrder::kProbed : SortOrder::kProbe;
+  c.counts = mode == 0 ? nullptr : counts;
+  c.range_check = mode == 3;
+  c.src = value;
+  c.dst = value_out;
+  c.bytes = value_bytes;
+  return sort_coo_run(c);
+}

@@ -331,7 +331,16 @@ def test_fused_coalesce_under_both_rankings(dev, ops):
 
 
 def test_device_decided_sort_and_probe(dev, ops):
-    E, m, n = 300000, 4000, 5000
+    for E, m, n in [(300000, 4000, 5000),
+                    (8192, 300, 500),            # the last one-launch size
+                    (8193, 300, 500),            # the first on the general path, passes only
+                    (5000, 1 << 20, 1 << 20),    # 40-bit keys: small E, but not the one-launch sort
+                    (131071, 700, 900),          # either side of the bucket threshold
+                    (131072, 700, 900)]:
+        _device_decided_sort_and_probe(dev, ops, E, m, n)
+
+
+def _device_decided_sort_and_probe(dev, ops, E, m, n):
     g = torch.Generator().manual_seed(2)
     row = torch.randint(0, m, (E, ), generator=g)
     col = torch.randint(0, n, (E, ), generator=g)
@@ -352,9 +361,31 @@ def test_device_decided_sort_and_probe(dev, ops):
         chk = ops.coo_check(r_.to(dev), c_.to(dev))
         rs, cs, perm = ops.sort_coo_probed(r_.to(dev), c_.to(dev), m, n, chk)
         assert np.array_equal(perm.cpu().numpy(), want_p) and np.array_equal(rs.cpu().numpy(), er)
+    # every entry point of the sort on the same input: the same sorted ids, permutation and counts
+    rd, cd = row.to(dev), col.to(dev)
+    want_counts = [int((key[1:] < key[:-1]).sum()), int((key[1:] == key[:-1]).sum())]
+    want_check = want_counts + [int(row.max()), int(col.max())]
+    chk = ops.coo_check(rd, cd)
+    assert chk.tolist() == want_check
+    val = torch.rand(E, generator=g)
+    outs = [ops.sort_coo(rd, cd, m, n, True), ops.sort_coo_auto(rd, cd, m, n)[:3], ops.sort_coo_probed(rd, cd, m, n, chk)]
+    for v in (None, val, val.double()):
+        for mode in (0, 1, 2, 3):
+            rs, cs, perm, counts, vs = ops.sort_coo_values(rd, cd, m, n, mode, chk.clone() if mode == 2 else None,
+                                                           None if v is None else v.to(dev))
+            outs.append((rs, cs, perm))
+            if mode in (1, 3):
+                assert counts.tolist() == (want_counts if mode == 1 else want_check), (mode, v is None)
+            if v is None:
+                assert vs.numel() == 0
+            else:
+                assert np.array_equal(vs.cpu().numpy(), v.numpy()[ep]), (mode, v.dtype)
+    for i, (rs, cs, perm) in enumerate(outs):
+        assert np.array_equal(perm.cpu().numpy(), ep), i
+        assert np.array_equal(rs.cpu().numpy(), er) and np.array_equal(cs.cpu().numpy(), ec), i
     # negative ids read as huge maxima (the constructor's range assert then fires)
     bad = row.clone()
-    bad[12345] = -1
+    bad[E // 3] = -1
     chk = ops.coo_check(bad.to(dev), col.to(dev)).tolist()
     assert chk[2] < 0 or chk[2] >= m
 
