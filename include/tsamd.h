@@ -832,6 +832,93 @@ int tsamd_hgt_commit(const int64_t *key_sorted, const int64_t *id_sorted, int64_
                      int64_t type_tag, int64_t *out, int64_t *err, void *stream);
 int tsamd_hgt_check_ids(int64_t *ids, int64_t n, int64_t M, int64_t *err, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Multilevel k-way graph partitioning (csrc/partition.hip, docs/design/partition.md).  Stands in for the METIS calls
+ * behind torch_sparse::partition / partition2 / mt_partition (csrc/metis.cpp:18-64 -> csrc/cpu/metis_cpu.cpp:9-113,
+ * METIS_PartGraphKway / METIS_PartGraphRecursive / mtmetis on the CPU; the reference refuses device tensors,
+ * csrc/metis.cpp:21-26).  It is a partitioner of its own behind that interface, not a port: no METIS exists for this
+ * build.  The entries below are the phases; the level loop with its allocations and read-backs lives in the caller
+ * (csrc/ops_partition.cpp).  The working graph is a symmetric CSR (rowptr [n + 1], row / col / weight [E]) without
+ * self-loops or duplicates, int64 edge weights >= 0, int64 vertex weights; n and k < 2^31.
+ *
+ *   tsamd_partition_edges            the entry list of a level: entry e -> (cmap[row], cmap[col], weight) (cmap NULL:
+ *        identity, weight NULL: ones), with mirror != 0 its transpose at slot E + e as well (outputs of 2 E entries:
+ *        A + A^T, what METIS expects the caller to pass, metis_cpu.cpp:36-42); an entry whose ends coincide is parked
+ *        on the key (n_key, 0) with weight 0.  Sorting + coalescing the list (tsamd_sort_coalesce) and summing the
+ *        duplicates (tsamd_segment_reduce, TSAMD_I64) gives the level's CSR, the parked entries last.  info (DEVICE
+ *        int64[4], zeroed by the caller) += (low 32 bits, high 32 bits of the kept weights, #entries out of range or
+ *        negative, #parked entries).
+ *   tsamd_partition_vertex_weights   vweight_c[c] = sum of vweight[v] over cmap[v] == c.
+ *   tsamd_partition_match            `rounds` handshake rounds of heavy-edge matching: an unmatched vertex proposes to
+ *        its heaviest unmatched neighbour u with vweight[v] + vweight[u] <= cap, ties by the larger hash(round, u), then
+ *        the smaller u; mutual proposals match.  match[v] = partner or -1; cmap[v] = rank of the pair's leader (the
+ *        smaller id; an unmatched vertex leads itself) among the leaders; *n_coarse (DEVICE) = number of leaders.
+ *   tsamd_partition_bfs_init / _seed / _step / tsamd_partition_assign      the initial partition: a level-synchronous
+ *        BFS, cl[v] = component << 31 | level (-1 unvisited; vertices without edges form one last component).
+ *        _init marks the isolated vertices and finds the start (minimum degree, then id); _seed starts component
+ *        `component` there (first != 0) or at the smallest unvisited id, state[2] = 1 if there was one; _step adds the
+ *        unvisited neighbours of (component, level) at level + 1, state[3] = 1 if any.  state is a DEVICE int64[4]; the
+ *        caller reads state[2] / state[3] (one 8-byte read-back per BFS level and per component).  _assign sorts by
+ *        (component, level, id), scans vweight in that order and sets part = min(k - 1, floor((prefix + w / 2) k / W)).
+ *   tsamd_partition_part_weights     pweight[p] = sum of vweight over part == p (k entries).
+ *   tsamd_partition_conn             per vertex, the best ELIGIBLE other part among those it has an edge to: largest
+ *        summed weight, ties to the smaller id; eligible = it has room (pweight + vweight[v] <= cap) and lies above
+ *        (mode 0) / below (mode 1) the own part, or anywhere (mode 2).  gain = weight to it - weight to the own part.
+ *        Modes 0 / 1 keep it (dest[v], gain[v]) when gain > 0 or the own part is over cap, else dest = -1.  Mode 2
+ *        (rebalance) reports only for vertices of parts over cap, and falls back to part *lightest (DEVICE, nullable)
+ *        with gain = -(weight to the own part) when no adjacent part has room.  Rows of up to 32 entries take a lane,
+ *        longer ones a wave with a 128-slot LDS hash, rows touching more parts than that a dense table of k counters
+ *        per workgroup in the workspace (64 * k words: nothing is n x k).
+ *   tsamd_partition_recount          drops candidates whose gain is no longer positive once the neighbours that move
+ *        first (higher gain, then smaller id) are counted at their destinations; acc [n] is scratch.
+ *   tsamd_partition_commit           select = 0: sorts the candidates by (dest, gain descending, id), takes a segmented
+ *        prefix sum of their weights and resets dest to -1 where the prefix no longer fits cap - pweight[dest];
+ *        select = 1: the same by (own part, ...) over the candidates of parts over cap, keeping only the prefix that
+ *        covers the part's excess.
+ *   tsamd_partition_apply            part[v] = dest[v] where dest[v] >= 0, pweight updated, *moved (DEVICE) += #moves.
+ *   tsamd_partition_cut              *cut (DEVICE) = summed weight of the entries whose ends differ (twice the cut).
+ *   tsamd_partition_keep_better      cuts (DEVICE int64[2]) = (before, after): when after > before and *over == 0 the
+ *        round is undone (part / pweight restored); then cuts[0] = the cut in force, cuts[1] = 0.
+ *   tsamd_partition_balance          balance (DEVICE int64[3]) = (#parts over cap, smallest part weight, its smallest id).
+ * ------------------------------------------------------------------------ */
+int tsamd_partition_edges(const int64_t *row, const int64_t *col, const int64_t *weight, const int64_t *cmap, int64_t E,
+                          int64_t n, int64_t n_key, int mirror, int64_t *row_out, int64_t *col_out, int64_t *weight_out,
+                          int64_t *info, void *stream);
+int tsamd_partition_vertex_weights(const int64_t *vweight, const int64_t *cmap, int64_t n, int64_t n_c,
+                                   int64_t *vweight_c, void *stream);
+size_t tsamd_partition_match_workspace_bytes(int64_t n);
+int tsamd_partition_match(const int64_t *rowptr, const int64_t *col, const int64_t *weight, const int64_t *vweight,
+                          int64_t n, int64_t cap, int64_t rounds, int64_t *match, int64_t *cmap, int64_t *n_coarse,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_partition_bfs_init(const int64_t *rowptr, int64_t n, int64_t *cl, int64_t *state, void *stream);
+int tsamd_partition_bfs_seed(int64_t *cl, int64_t n, int64_t component, int first, int64_t *state, void *stream);
+int tsamd_partition_bfs_step(const int64_t *rowptr, const int64_t *col, int64_t n, int64_t *cl, int64_t component,
+                             int64_t level, int64_t *state, void *stream);
+size_t tsamd_partition_assign_workspace_bytes(int64_t n);
+int tsamd_partition_assign(const int64_t *cl, const int64_t *vweight, int64_t n, int64_t k, int64_t *part,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_partition_part_weights(const int64_t *part, const int64_t *vweight, int64_t n, int64_t k, int64_t *pweight,
+                                 void *stream);
+size_t tsamd_partition_conn_workspace_bytes(int64_t n, int64_t k);
+int tsamd_partition_conn(const int64_t *rowptr, const int64_t *col, const int64_t *weight, const int64_t *vweight,
+                         const int64_t *part, const int64_t *pweight, int64_t n, int64_t k, int64_t cap, int mode,
+                         const int64_t *lightest, int64_t *dest, int64_t *gain, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int tsamd_partition_recount(const int64_t *row, const int64_t *col, const int64_t *weight, const int64_t *part,
+                            const int64_t *pweight, const int64_t *gain, int64_t n, int64_t E, int64_t cap, int64_t *dest,
+                            int64_t *acc, void *stream);
+size_t tsamd_partition_commit_workspace_bytes(int64_t n, int64_t k);
+int tsamd_partition_commit(int64_t *dest, const int64_t *gain, const int64_t *vweight, const int64_t *part,
+                           const int64_t *pweight, int64_t n, int64_t k, int64_t cap, int select, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int tsamd_partition_apply(const int64_t *dest, const int64_t *vweight, int64_t n, int64_t k, int64_t *part,
+                          int64_t *pweight, int64_t *moved, void *stream);
+int tsamd_partition_cut(const int64_t *row, const int64_t *col, const int64_t *weight, const int64_t *part, int64_t E,
+                        int64_t *cut, void *stream);
+int tsamd_partition_keep_better(int64_t *cuts, const int64_t *over, const int64_t *part_old, const int64_t *pweight_old,
+                                int64_t n, int64_t k, int64_t *part, int64_t *pweight, void *stream);
+int tsamd_partition_balance(const int64_t *pweight, int64_t k, int64_t cap, int64_t *balance, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

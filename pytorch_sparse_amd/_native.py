@@ -45,6 +45,12 @@ SYMBOLS = [
     'tsamd_ego_induced_workspace_bytes', 'tsamd_ego_induced_count', 'tsamd_ego_induced_write',
     'tsamd_hgt_seen', 'tsamd_hgt_budget_add', 'tsamd_hgt_select_workspace_bytes', 'tsamd_hgt_select', 'tsamd_hgt_keys',
     'tsamd_hgt_commit', 'tsamd_hgt_check_ids',
+    'tsamd_partition_edges', 'tsamd_partition_vertex_weights', 'tsamd_partition_match_workspace_bytes',
+    'tsamd_partition_match', 'tsamd_partition_bfs_init', 'tsamd_partition_bfs_seed', 'tsamd_partition_bfs_step',
+    'tsamd_partition_assign_workspace_bytes', 'tsamd_partition_assign', 'tsamd_partition_part_weights',
+    'tsamd_partition_conn_workspace_bytes', 'tsamd_partition_conn', 'tsamd_partition_recount',
+    'tsamd_partition_commit_workspace_bytes', 'tsamd_partition_commit', 'tsamd_partition_apply', 'tsamd_partition_cut',
+    'tsamd_partition_keep_better', 'tsamd_partition_balance',
 ]
 
 DTYPES = {
