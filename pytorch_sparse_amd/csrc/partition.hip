@@ -10,7 +10,8 @@
 //                   an int64 segment sum
 //   initial         level-synchronous pull BFS (one packed (component, level) word per vertex), sort by (component,
 //                   level, id), scan of the vertex weights, part = floor((prefix + w / 2) k / W)
-//   refinement      synchronous rounds: connectivity of every vertex to its adjacent parts (short rows: a lane and a
+//   refinement      synchronous rounds: connectivity of every vertex to its adjacent parts -- those of positive
+//                   connectivity; zero-weight edges alone do not make a part adjacent -- (short rows: a lane and a
 //                   short loop; longer rows: a wave and a 128-slot LDS hash; rows that overflow it: a dense per-workgroup
 //                   table of k counters in global scratch), a recount of the gain against the neighbours that move first,
 //                   and a commit by sort + segmented prefix sum -- no cursor atomics
@@ -320,7 +321,7 @@ __global__ void conn_lane_kernel(const int64_t *__restrict__ rowptr, const int64
     if (!first || !eligible(p, own, mode, pw, vwv, cap)) continue;
     int64_t c = 0;
     for (int64_t i = j; i < e; ++i) c += part[col[i]] == p ? w[i] : 0;
-    better_part(best, c_best, p, c);
+    if (c != 0) better_part(best, c_best, p, c);  // zero-weight edges alone make no adjacent part (as in every route)
   }
   report(v, own, c_own, best, c_best, mode, pw, vwv, cap, lightest, dest, gain);
 }
@@ -385,7 +386,7 @@ __global__ void __launch_bounds__(64) conn_wave_kernel(const int64_t *__restrict
     const int64_t p = key[s];
     if (p < 0) continue;
     if (p == own) c_own = (int64_t)val[s];
-    else if (eligible(p, own, mode, pw, vwv, cap)) better_part(best, c_best, p, (int64_t)val[s]);
+    else if (val[s] != 0 && eligible(p, own, mode, pw, vwv, cap)) better_part(best, c_best, p, (int64_t)val[s]);
   }
   for (int off = 32; off >= 1; off >>= 1) c_own += __shfl_xor((long long)c_own, off);
   wave_best(best, c_best);
