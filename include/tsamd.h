@@ -682,6 +682,25 @@ int tsamd_set_diag_apply(const int64_t *pos, const int64_t *row, const int64_t *
  *                       column.  Without replacement the draws of a row are distinct (keyed
  *                       bijection of [0, deg) evaluated at 0..k-1, see csrc/sample.hip).
  *                       (num_neighbors < 0 is tsamd_select_fill with ind_out = nbr, pos_out = e_id.)
+ *                       Every draw is a pure function of (seed, i, j, deg): i = position of the row in idx (NOT the
+ *                       node id), j = index of the draw, k = num_neighbors, p = the drawn position in the row,
+ *                       e_id = rowptr[idx[i]] + p.  Philox(seed; c_lo, c2, c3) is Philox4x32-10 with counter words
+ *                       (lo32(c_lo), hi32(c_lo), c2, c3) and key words (lo32(seed), hi32(seed)); u = x | y << 32 of its
+ *                       output (x, y, z, w); mulhi(a, b) = the high 64 bits of the 128-bit product.
+ *                         with replacement       p = mulhi(u, deg), u of Philox(seed; i, lo32(j), 0xD4A3 ^ hi32(j))
+ *                         deg <= k               p = j (the whole row in stored order)
+ *                         k < deg <= 64          Floyd: used = {}; for t = deg - k .. deg - 1, in this order of emission:
+ *                                                pick = mulhi(u, t + 1), u of Philox(seed; i, t, 0xF10D); if pick is in
+ *                                                used, pick = t; used += pick; the next draw of the row is pick
+ *                         deg > 64               p = pi(j): b = bits of deg - 1, h = (b + 1) / 2, keys K[0..5] = x, y,
+ *                                                z, w of Philox(seed; i, 0, 0x5A17) then x, y of Philox(seed; i, 1,
+ *                                                0x5A17); v = j; repeat { L = v >> h, R = v & (2^h - 1); six rounds r:
+ *                                                (L, R) = (R, (L ^ (fmix32(lo32(R * 0x9E3779B1 + K[r])) >> (32 - h)))
+ *                                                & (2^h - 1)); v = L << h | R } until v < deg; fmix32 = MurmurHash3's
+ *                                                32-bit finaliser
+ *                       tsamd_temporal_redraw: pick j of node i copies its (mulhi(u, cnt))-th draw with keep = 1 in
+ *                       stored order, cnt = their number, u of Philox(seed; i, lo32(j), 0x7E4D ^ hi32(j)).
+ *                       oracle/np_draws.py restates all of it in numpy; docs/design/oracle_parity.md has the seeds.
  *   tsamd_relabel_plan / _apply   replaces the std::unordered_map walk of relabel_cpu /
  *                       relabel_one_hop_cpu / sample_adj_cpu (csrc/cpu/relabel_cpu.cpp:5-155):
  *                       ids in idx[n] keep local id = their position, every other id in nbr[T]

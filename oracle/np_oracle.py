@@ -134,10 +134,23 @@ def relabel_one_hop(rowptr, col, idx, bipartite):
     return out_ptr, out_col, pos, out_idx
 
 
-def sample_adj_all(rowptr, col, idx):
-    """csrc/cpu/sample_cpu.cpp:40-58,116-137 with num_neighbors < 0: every neighbour, relabelled in
-    first-occurrence order, rows sorted by the new column id -> (rowptr, col, n_id, e_id)."""
-    out_ptr, seg, pos = _gather_rows(rowptr, idx)
+def _drawn_rows(ptr, frontier, k, draws, hop):
+    """(out_ptr, seg, positions) of one hop: every entry in stored order when k < 0, else what the draw source says:
+    draws(hop, ptr, frontier, k) -> (out_ptr, positions), oracle/np_draws.py.  Without a source only k < 0 is defined."""
+    if k < 0:
+        return _gather_rows(ptr, frontier)
+    if draws is None:
+        raise ValueError('random draw: fan-out %d needs a draw source' % k)
+    out_ptr, pos = draws(hop, ptr, frontier, k)
+    seg = np.repeat(np.arange(np.asarray(frontier).size), np.diff(out_ptr))
+    return out_ptr, seg, np.asarray(pos, np.int64)
+
+
+def sample_adj_all(rowptr, col, idx, num_neighbors=-1, draws=None):
+    """csrc/cpu/sample_cpu.cpp:40-58,116-137: the neighbours of idx (every one with num_neighbors < 0, else the entries
+    the draw source `draws` picks, oracle/np_draws.py: sample_adj_draws), relabelled in first-occurrence order, rows
+    sorted by the new column id -> (rowptr, col, n_id, e_id)."""
+    out_ptr, seg, pos = _drawn_rows(rowptr, idx, num_neighbors, draws, 0)
     local, n_id = relabel(np.asarray(col, np.int64)[pos], idx)
     order = np.lexsort((local, seg))
     return out_ptr, local[order], n_id, pos[order]
@@ -154,17 +167,19 @@ def saint_subgraph(idx, rowptr, col):
     return seg[keep], w[keep], pos[keep]
 
 
-def neighbor_sample_all(colptr, row, input_node, num_hops, directed):
-    """csrc/cpu/neighbor_sample_cpu.cpp:15-124 with num_neighbors = [-1] * num_hops (every in-neighbour):
-    -> (node, row, col, edge).  Hop l expands the nodes found in hop l-1; new nodes are appended in
-    first-occurrence order; directed=False returns every stored edge between the sampled nodes."""
+def neighbor_sample(colptr, row, input_node, num_neighbors, directed, draws=None):
+    """csrc/cpu/neighbor_sample_cpu.cpp:15-124 -> (node, row, col, edge).  num_neighbors: the fan-out per hop; a hop
+    with a negative one takes every in-neighbour, any other asks the draw source `draws` (oracle/np_draws.py:
+    neighbor_draws, keyed by the position in the hop's frontier) for its entries.  Hop l expands the nodes found in hop
+    l-1; new nodes are appended in first-occurrence order; directed=False returns every stored edge between the
+    sampled nodes."""
     colptr, row = np.asarray(colptr, np.int64), np.asarray(row, np.int64)
     samples = np.asarray(input_node, np.int64)
     begin, end = 0, samples.size
     rows, cols, edges = [], [], []
-    for _ in range(num_hops):
+    for hop, k in enumerate(num_neighbors):
         frontier = samples[begin:end]
-        _, seg, pos = _gather_rows(colptr, frontier)
+        _, seg, pos = _drawn_rows(colptr, frontier, k, draws, hop)
         local, samples = relabel(row[pos], samples)
         rows.append(local), cols.append(seg + begin), edges.append(pos)
         begin, end = end, samples.size
@@ -175,7 +190,8 @@ def neighbor_sample_all(colptr, row, input_node, num_hops, directed):
     return samples, cat(rows), cat(cols), cat(edges)
 
 
-def hetero_neighbor_sample_det(node_types, edge_types, colptr, row, inputs, fan, num_hops, directed, node_time=None):
+def hetero_neighbor_sample_det(node_types, edge_types, colptr, row, inputs, fan, num_hops, directed, node_time=None,
+                               replace=False, draws=None):
     """csrc/cpu/neighbor_sample_cpu.cpp:135-430 (hetero_sample) for the draws that are NOT random: fan < 0, or at
     least as many draws as the node has neighbours ("select all neighbors", :253-293) -- any other node raises.
     colptr / row: {relation: array} with relation = 'src__rel__dst'; inputs: {node type: ids}; fan: {relation: [k per
@@ -184,6 +200,11 @@ def hetero_neighbor_sample_det(node_types, edge_types, colptr, row, inputs, fan,
     unconstrained, :119-130).  Sequential dict model, statement by statement: relations in sorted key order per hop
     (:216-219), frontier slices moved at the end of a hop (:352-361), map INSERT semantics (a seed listed twice keeps
     its first position, :192-195), the undirected edge list at the end (:366-412).
+    With a draw source (draws=, oracle/np_draws.py: HeteroDraws) the random draws are defined too: the entries of
+    (hop, relation, frontier slice) are draws.sample(draw_no, colptr, frontier, k) -- draw_no counts every (hop,
+    relation) from 1, empty frontiers included; the temporal sampler drops the violating ones afterwards (:326-346) --
+    and, for the temporal sampler with replace=True, every entry is listed and marked and draws.redraw(draw_no, out_ptr,
+    keep, k) picks k of the valid ones per node (the library's law for :268-300).  Without it nothing changes.
     -> (node {type: ids}, row, col, edge {relation: ids})."""
     temporal = node_time is not None
     to_edge = {'__'.join(e): e for e in edge_types}
@@ -201,12 +222,30 @@ def hetero_neighbor_sample_det(node_types, edge_types, colptr, row, inputs, fan,
             if temporal:
                 root_time[t].append(int(node_time[t][v]))
     slices = {t: (0, len(samples[t])) for t in node_types}
+    draw_no = 0
     for ell in range(num_hops):
         for rel in sorted(fan):
             src_t, _, dst_t = to_edge[rel]
             k = fan[rel][ell]
             cp, rw = np.asarray(colptr[rel], np.int64), np.asarray(row[rel], np.int64)
             begin, end = slices[dst_t]
+            draw_no += 1
+            drawn = None  # (out_ptr, entries) of the frontier slice when a draw source decides them
+            if draws is not None and end > begin:
+                frontier = np.asarray([p[0] if temporal else p for p in samples[dst_t][begin:end]], np.int64)
+                if temporal and replace and k >= 0:
+                    out_ptr, listed = draws.sample(draw_no, cp, frontier, -1, False)
+                    f_time = np.repeat(np.asarray(root_time[dst_t][begin:end], np.int64), np.diff(out_ptr))
+                    keep = (np.asarray(node_time[src_t], np.int64)[rw[listed]] <= f_time if src_t in node_time
+                            else np.ones(listed.size, bool)).astype(np.int64)
+                    if listed.size == 0 or k == 0:
+                        drawn = (np.zeros(end - begin + 1, np.int64), listed[:0])
+                    else:
+                        t, keep2 = draws.redraw(draw_no, out_ptr, keep, k)
+                        picked = np.cumsum(np.concatenate([[0], keep2]))
+                        drawn = (picked[::k], listed[t[keep2 > 0]])
+                else:
+                    drawn = draws.sample(draw_no, cp, frontier, k)
             for i in range(begin, end):
                 w = samples[dst_t][i][0] if temporal else samples[dst_t][i]
                 root_w = samples[dst_t][i][1] if temporal else -1
@@ -214,9 +253,13 @@ def hetero_neighbor_sample_det(node_types, edge_types, colptr, row, inputs, fan,
                 s, e = int(cp[w]), int(cp[w + 1])
                 if e == s:
                     continue
-                if not (k < 0 or k >= e - s):
+                if drawn is not None:
+                    offs = drawn[1][drawn[0][i - begin]:drawn[0][i - begin + 1]].tolist()
+                elif not (k < 0 or k >= e - s):
                     raise ValueError('random draw: node %d of %s has %d neighbours, fan-out %d' % (w, dst_t, e - s, k))
-                for off in range(s, e):
+                else:
+                    offs = range(s, e)
+                for off in offs:
                     v = int(rw[off])
                     if temporal:
                         if src_t in node_time and not int(node_time[src_t][v]) <= dst_time:

@@ -9,11 +9,26 @@ with sets and loops like the reference.  Two halves:
 import numpy as np
 
 
-def ego_node_sets(rowptr, col, idx, depth, num_neighbors):
+def ego_node_sets(rowptr, col, idx, depth, num_neighbors, draws=None):
     """The node set of every seed: a list of sorted int64 arrays.  Raises ValueError where the reference would draw
-    at random (a row with more than num_neighbors > 0 entries is expanded)."""
+    at random (a row with more than num_neighbors > 0 entries is expanded) -- unless a draw source says what is drawn:
+    draws(hop, rowptr, frontier, k) -> (out_ptr, positions in col) (oracle/np_draws.py: ego_draws).  The frontier of
+    hop 0 is idx; the one of hop l + 1 is every draw of hop l in draw order, duplicates included, each with the seed
+    it was drawn for; the draws are keyed by the position in that frontier."""
     rowptr = np.asarray(rowptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int64)
+    if draws is not None:
+        frontier = np.asarray(idx, dtype=np.int64)
+        fseg = np.arange(frontier.size, dtype=np.int64)
+        segs, nodes = [fseg], [frontier]
+        for hop in range(depth if num_neighbors > 0 else 0):
+            if frontier.size == 0:
+                break
+            out_ptr, pos = draws(hop, rowptr, frontier, num_neighbors)
+            frontier, fseg = col[pos], np.repeat(fseg, np.diff(out_ptr))
+            segs.append(fseg), nodes.append(frontier)
+        seg, node = np.concatenate(segs), np.concatenate(nodes)
+        return [np.unique(node[seg == g]) for g in range(len(idx))]
     sets = []
     for seed in np.asarray(idx, dtype=np.int64).tolist():
         n_id_set = {seed}

@@ -113,9 +113,30 @@ def test_random_draws_keep_the_reference_guarantees(ops, replace, temporal):
             first_hop = cnt[:inp[d].numel()] if d in inp else cnt[:0]
             deg = (colptr[rel][1:] - colptr[rel][:-1])[inp[d]] if d in inp else first_hop
             assert torch.equal(first_hop, torch.minimum(deg, torch.full_like(deg, 4)))
-        if temporal:
-            # the drawn source is not younger than the ROOT of the tree it was drawn into; roots: the input nodes
-            pass
+    if temporal:
+        # the drawn source is not younger than the ROOT TIME of the node it was drawn for.  Root times: the input nodes
+        # have their own; a (node, root) pair keeps the root time of the draw that FIRST listed it (roots are numbered
+        # per input type, so trees of two input types may meet in one pair: neighbor_sample_cpu.cpp:271-275 pushes the
+        # time only on insertion).  Draws in the sampler's order: hop by hop -- the first hop's destinations are the
+        # input nodes --, relations in sorted key order, then stored order
+        root_time = {t: torch.full((node[t].numel(), ), -1, dtype=torch.long) for t in NODE_TYPES}
+        for t, x in inp.items():
+            root_time[t][:x.numel()] = times[t][x]
+        checked = 0
+        for hop in (0, 1):
+            for rel in sorted(RELS):
+                s, _, d = rel.split('__')
+                r, c = out[1][rel].cpu(), out[2][rel].cpu()
+                n_inp = inp[d].numel() if d in inp else 0
+                of_hop = (c < n_inp) if hop == 0 else (c >= n_inp)
+                r, c = r[of_hop], c[of_hop]
+                assert bool((root_time[d][c] >= 0).all())  # the destination was listed in an earlier hop
+                assert bool((times[s][node[s][r]] <= root_time[d][c]).all())
+                checked += r.numel()
+                for x, y in zip(r.tolist(), c.tolist()):
+                    if root_time[s][x] < 0:
+                        root_time[s][x] = root_time[d][y]
+        assert checked == total
     assert total > 0
     # reproducible under torch.manual_seed
     torch.manual_seed(11)

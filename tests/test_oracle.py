@@ -390,8 +390,8 @@ def test_np_neighbor_sample_matches_fixtures_and_compiled_reference():
     assert len(paths) == 24
     for path in paths:
         z = np.load(path)
-        got = npo.neighbor_sample_all(z['colptr'], z['row'], z['input_node'], len(z['num_neighbors']),
-                                      bool(z['directed']))
+        got = npo.neighbor_sample(z['colptr'], z['row'], z['input_node'], [-1] * len(z['num_neighbors']),
+                                  bool(z['directed']))
         for g, key in zip(got, ('node', 'out_row', 'out_col', 'out_edge')):
             np.testing.assert_array_equal(g, z[key], err_msg=os.path.basename(path) + ':' + key)
     if not ref.available():
@@ -410,7 +410,7 @@ def test_np_neighbor_sample_matches_fixtures_and_compiled_reference():
             for directed in (True, False):
                 want = r.neighbor_sample(torch.from_numpy(colptr), torch.from_numpy(row), torch.from_numpy(inp),
                                          [-1] * hops, False, directed)
-                for g, w in zip(npo.neighbor_sample_all(colptr, row, inp, hops, directed), want):
+                for g, w in zip(npo.neighbor_sample(colptr, row, inp, [-1] * hops, directed), want):
                     np.testing.assert_array_equal(g, w.numpy())
 
 
