@@ -938,6 +938,51 @@ int tsamd_partition_keep_better(int64_t *cuts, const int64_t *over, const int64_
                                 int64_t n, int64_t k, int64_t *part, int64_t *pweight, void *stream);
 int tsamd_partition_balance(const int64_t *pweight, int64_t k, int64_t cap, int64_t *balance, void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * Reverse Cuthill-McKee ordering (csrc/rcm.hip).  Replaces the scipy call of reverse_cuthill_mckee
+ * (torch_sparse/bandwidth.py:8-20: `sp.csgraph.reverse_cuthill_mckee(sp_src, symmetric_mode=True)` on the host) and
+ * returns the same permutation bit for bit when seeded in scipy's order; docs/design/rcm.md has the scheme.  The
+ * building blocks of the host driver (csrc/ops_rcm.cpp); n < 2^31.
+ *
+ *   tsamd_rcm_limits        out[0..2] = (largest node capacity of the one-workgroup route, its capacity in frontier
+ *        entries, the levels one of its launches may run under tsamd::rcm).
+ *   tsamd_rcm_degree        deg[i] = rowptr[i + 1] - rowptr[i], plus one where row i holds its own diagonal (scipy's
+ *        degree; a repeated diagonal counts once).  Balanced by entries.
+ *   tsamd_rcm_relabel       out[i] = table[idx[i]]; an id outside [0, n) gives 0 and state[7] = max(state[7], 1).
+ *   tsamd_rcm_begin         by_rank [n] = the nodes in stable (degree, id) order, seeds [n] = the order in which nodes are
+ *        tried as component seeds -> rank (the inverse of by_rank), seeds_r[i] = rank[seeds[i]], pos = -1, owner = max.
+ *        state[7] = 2 when seeds is not a permutation of [0, n).  scratch: n words.
+ *   state (DEVICE int64[8], zeroed by the caller): [0] lo and [1] hi, the frontier is order[lo, hi); [2] the seed
+ *        cursor; [3] why the last one-workgroup launch ended: 0 everything is ordered, 1 the frontier exceeds the
+ *        route's capacity, 2 level budget, 3 seed-search budget; [4] levels (non-empty frontiers); [5] components;
+ *        [6] entries of the frontier's rows (written by _level_plan); [7] input errors.
+ *   tsamd_rcm_small         ONE workgroup on the RELABELLED graph (node = rank, rows sorted): runs levels -- claim by
+ *        min, flag, scan, write -- and, when a frontier empties, takes the next unvisited node of seeds_r (isolated
+ *        seeds in batches), until the frontier exceeds cap_nodes nodes (clamped to the limit; 0: seed search only) or the
+ *        entry capacity, everything is ordered, or `budget` levels have run.  The caller reads state and relaunches.
+ *        With state[7] != 0 (bad input) the launch returns at once with reason 0; no position >= n is ever written.
+ *   tsamd_rcm_level_plan / _level_run      one level on the whole device, work divided by frontier ENTRIES: _plan
+ *        scans the row lengths of the nf = hi - lo frontier nodes into fptr [nf + 1] and state[6] = T; the caller reads
+ *        T; _run(T, n) claims, flags, scans and writes (ej, ep, off: T words each) and advances lo / hi / levels.
+ *        Workspace of both: tsamd_rcm_level_workspace_bytes(count) with count = nf resp. T.
+ *   tsamd_rcm_finish        perm[i] = by_rank[order[n - 1 - i]].
+ * ------------------------------------------------------------------------ */
+int tsamd_rcm_limits(int64_t out[3]);
+int tsamd_rcm_degree(const int64_t *rowptr, const int64_t *col, int64_t n, int64_t E, int64_t *deg, void *stream);
+int tsamd_rcm_relabel(const int64_t *idx, const int64_t *table, int64_t count, int64_t n, int64_t *out, int64_t *state,
+                      void *stream);
+int tsamd_rcm_begin(const int64_t *by_rank, const int64_t *seeds, int64_t n, int64_t *rank, int64_t *seeds_r,
+                    int64_t *pos, int64_t *owner, int64_t *scratch, int64_t *state, void *stream);
+int tsamd_rcm_small(const int64_t *rowptr, const int64_t *col, const int64_t *seeds_r, int64_t n, int64_t cap_nodes,
+                    int64_t budget, int64_t *pos, int64_t *owner, int64_t *order, int64_t *state, void *stream);
+size_t tsamd_rcm_level_workspace_bytes(int64_t count);
+int tsamd_rcm_level_plan(const int64_t *rowptr, const int64_t *order, int64_t nf, int64_t *fptr, int64_t *state,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_rcm_level_run(const int64_t *rowptr, const int64_t *col, const int64_t *fptr, int64_t T, int64_t n, int64_t *pos,
+                        int64_t *owner, int64_t *order, int64_t *ej, int64_t *ep, int64_t *off, int64_t *state,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_rcm_finish(const int64_t *order, const int64_t *by_rank, int64_t n, int64_t *perm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ SYMBOLS = [
     'tsamd_partition_conn_workspace_bytes', 'tsamd_partition_conn', 'tsamd_partition_recount',
     'tsamd_partition_commit_workspace_bytes', 'tsamd_partition_commit', 'tsamd_partition_apply', 'tsamd_partition_cut',
     'tsamd_partition_keep_better', 'tsamd_partition_balance',
+    'tsamd_rcm_limits', 'tsamd_rcm_degree', 'tsamd_rcm_relabel', 'tsamd_rcm_begin', 'tsamd_rcm_small',
+    'tsamd_rcm_level_workspace_bytes', 'tsamd_rcm_level_plan', 'tsamd_rcm_level_run', 'tsamd_rcm_finish',
 ]
 
 DTYPES = {
