@@ -88,6 +88,16 @@ const char *tsamd_status_string(int status);
  * ------------------------------------------------------------------------ */
 size_t tsamd_spmm_workspace_bytes(int dtype, int reduce, int64_t B, int64_t M,
                                   int64_t N, int64_t K, int64_t E);
+
+/* Hot rows (inspection and tests; no device work).  Sums / means of one floating-point matrix whose column ids camp copy
+ * only the rows that a sample of `col` names into a side table inside the workspace.  Returns 1 when tsamd_spmm with
+ * these operands and this workspace takes that route once its probe flags the graph, and fills layout[0..3]: byte
+ * offsets in `workspace` of the N flag bytes (1 = hot), of the lookup words (per 32 ids: {flags, slot of the first
+ * hot id}) and of the table (hot rows in id order), and the table's distance from `mat` in rows.  Returns 0 when the
+ * call keeps the full copy of `mat`. */
+int tsamd_spmm_hot_rows_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                               const void *mat, const void *out, void *workspace, int64_t *layout);
+
 int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const int64_t *col,
                const void *value, const void *mat, void *out, int64_t *arg_out,
                int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,

@@ -50,8 +50,10 @@
 #endif
 
 #include "common.h"
+#include "scan.h"
 #include "spmm_internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -123,6 +125,15 @@ struct Workspace {
   uint32_t *rec_out;      // [B][E][8] or nullptr
   const void *rec_value;  // the matrix's values (or nullptr) for the fix-up kernel's records
   int64_t snap;           // see spmm_partition_kernel
+  // sampled hot-row side table (see "hot rows" below): instead of the full copy, the rows that a sample of `col` hits are
+  // copied to consecutive slots of `hot_side` (inside the xperm region) and the gather of a hot id goes there
+  uint8_t *hot_flag;       // [N] 1 = a sampled entry names this id; nullptr = the call is out of scope
+  uint32_t *hot_word;      // [ceil(N / 64)][4]: per half of 32 ids {flags, slot of the half's first hot id}
+  int64_t *hot_count;      // [ceil(N / 64)] hot ids per word, then their exclusive scan
+  void *hot_scan;          // scratch of that scan
+  void *hot_side;          // the table; (hot_side - mat) is a whole number of rows
+  int32_t hot_side_row;    // (hot_side - mat) / row bytes: a gathered index stays `mat`-relative and signed
+  int64_t hot_stride;      // every hot_stride-th entry of `col` is sampled
 };
 
 // One SpMM call: the operands of tsamd_spmm (include/tsamd.h), then the optional modes (see Workspace), off unless set.
@@ -298,6 +309,96 @@ __global__ __launch_bounds__(256) void spmm_permute_rows_kernel(const T *__restr
 }
 
 // ---------------------------------------------------------------------------
+// 0b. hot rows: the full copy moves every row of `mat` although almost all gathers go to a small share of them.  For
+//    sums of one matrix (B = 1) without an operand cache, only the rows that a sample of `col` hits are copied, to
+//    consecutive slots of a side table (slot order = id order: deterministic); the merge kernel looks every id up in
+//    one 16-byte word per 64 ids (two halves of {32 flags, slot of the half's first hot id}: an 8-byte load per entry) and gathers hot ids from the table, the others in place.  Consecutive slots have
+//    uniform low address bits, which is all the hashed copy was for.  Every kernel leaves at once unless the probe
+//    flagged the graph.  Only addresses change: sums are bit-identical with the full copy.
+// ---------------------------------------------------------------------------
+#ifndef TSAMD_HOT_STRIDE
+#define TSAMD_HOT_STRIDE 32
+#endif
+constexpr int kHotBlocks = 2048;
+
+__global__ __launch_bounds__(256) void spmm_hot_mark_kernel(const int64_t *__restrict__ col, int64_t E, Workspace ws) {
+  if (!use_relabel(ws.relabel_mode, ws.relabel_flag)) return;
+  const int64_t samples = (E + ws.hot_stride - 1) / ws.hot_stride;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < samples; i += (int64_t)gridDim.x * 256)
+    ws.hot_flag[col[i * ws.hot_stride]] = 1;  // racing stores all write the same byte
+}
+
+// one wave per 64 ids: their flags as a bit mask and its population count (the scan's input)
+__global__ __launch_bounds__(256) void spmm_hot_bits_kernel(int64_t N, Workspace ws) {
+  if (!use_relabel(ws.relabel_mode, ws.relabel_flag)) return;
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t words = (N + 63) >> 6;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (int64_t)gridDim.x * 4) {
+    const int64_t id = w * 64 + lane;
+    const unsigned long long m = __ballot(id < N && ws.hot_flag[id] != 0);
+    if (lane == 0) {
+      ws.hot_word[4 * w] = (uint32_t)m;
+      ws.hot_word[4 * w + 2] = (uint32_t)(m >> 32);
+      ws.hot_count[w] = __popcll(m);
+    }
+  }
+}
+
+// A 256-thread block per word of 64 ids: 2^lgL lanes copy one hot row, 16 bytes per lane and step, eight rows per
+// lane in flight; the word's slot base (the scanned count) is entered on the way.
+__global__ __launch_bounds__(256) void spmm_hot_copy_kernel(const void *__restrict__ mat, int64_t N, uint32_t slots,
+                                                           int lgL, Workspace ws) {
+  if (!use_relabel(ws.relabel_mode, ws.relabel_flag)) return;
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 *src = reinterpret_cast<const u32x4 *>(mat);
+  u32x4 *dst = reinterpret_cast<u32x4 *>(ws.hot_side);
+  const uint32_t lanes = 1u << lgL;
+  const uint32_t sl0 = threadIdx.x & (lanes - 1);
+  const int rows_per_step = 256 >> lgL;
+  const int grp = (int)(threadIdx.x >> lgL);
+  const int64_t words = (N + 63) >> 6;
+  constexpr int kRows = 8;
+  auto word_mask = [&](int64_t w) -> unsigned long long {
+    if (w >= words) return 0ull;
+    return (unsigned long long)ws.hot_word[4 * w] | ((unsigned long long)ws.hot_word[4 * w + 2] << 32);
+  };
+  auto word_base = [&](int64_t w) -> uint64_t { return w < words ? (uint64_t)ws.hot_count[w] : 0u; };
+  unsigned long long m_next = word_mask(blockIdx.x);
+  uint64_t base_next = word_base(blockIdx.x);
+  for (int64_t w = blockIdx.x; w < words; w += gridDim.x) {
+    const unsigned long long m = m_next;
+    const uint64_t base = base_next;
+    m_next = word_mask(w + gridDim.x);  // the next word is on its way while this one's rows move
+    base_next = word_base(w + gridDim.x);
+    if (threadIdx.x == 0) {
+      ws.hot_word[4 * w + 1] = (uint32_t)base;
+      ws.hot_word[4 * w + 3] = (uint32_t)base + (uint32_t)__popc((uint32_t)m);
+    }
+    for (int b0 = 0; b0 < 64; b0 += kRows * rows_per_step) {
+      if (((m >> b0) & (kRows * rows_per_step >= 64 ? ~0ull : (1ull << (kRows * rows_per_step)) - 1ull)) == 0ull) continue;
+      bool on[kRows];
+      uint64_t from[kRows], to[kRows];
+#pragma unroll
+      for (int t = 0; t < kRows; ++t) {
+        const int b = b0 + t * rows_per_step + grp;
+        on[t] = b < 64 && ((m >> b) & 1ull) != 0;  // (set bits name ids < N: spmm_hot_bits_kernel)
+        from[t] = (uint64_t)(w * 64 + b) * slots;
+        to[t] = (base + (uint64_t)__popcll(m & ((1ull << (b & 63)) - 1ull))) * slots;
+      }
+      for (uint32_t sl = sl0; sl < slots; sl += lanes) {
+        u32x4 v[kRows];
+#pragma unroll
+        for (int t = 0; t < kRows; ++t)
+          if (on[t]) v[t] = __builtin_nontemporal_load(src + from[t] + sl);  // streamed once, as in the full copy
+#pragma unroll
+        for (int t = 0; t < kRows; ++t)
+          if (on[t]) dst[to[t] + sl] = v[t];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // 1. merge-path partition: list A = row ends rowptr[1..M], list B = edge ids
 // ---------------------------------------------------------------------------
 __global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, int64_t M, int64_t E,
@@ -394,7 +495,7 @@ __device__ __forceinline__ void round_products(typename Traits<T>::acc_t w, type
 // MASKED (sums only): e_l holds the window's entry ids; feature j of this lane's packet contributes iff bit
 // (mask_shift + j) of maskk[entry * mask_words] is set, and the product is rounded to the element type
 // before it is added (what value.index_select(0, arg) * grad_out does in SPMMMin/Max::backward).
-template <typename T, int VEC, int RED, bool MASKED = false>
+template <typename T, int VEC, int RED, bool MASKED = false, bool SIGNED = false>
 __device__ __forceinline__ void accumulate_window(
     int lo, int hi, uint32_t wrel, uint32_t c_l, typename Traits<T>::acc_t w_l, bool has_value,
     const T *__restrict__ matk, uint32_t K, int lgG, int g,
@@ -471,7 +572,9 @@ __device__ __forceinline__ void accumulate_window(
         em[u] = lane_read(e_l, src);
         on[u] = (lane_read(z_l, src) >> mask_seg) & 1u;
       } else {
-        x[u] = *reinterpret_cast<const P *>(matk + (uint64_t)c * K);
+        // SIGNED (hot rows): c is a signed row index relative to `mat`, the side table may lie below it
+        if constexpr (SIGNED) x[u] = *reinterpret_cast<const P *>(matk + (int64_t)(int32_t)c * (int64_t)(int32_t)K);  // (K < 2^31: one v_mad_i64_i32)
+        else x[u] = *reinterpret_cast<const P *>(matk + (uint64_t)c * K);
       }
     }
     if constexpr (MASKED) {
@@ -816,7 +919,11 @@ constexpr int kMinWavesPerEU = kPartial ? ((RED == RED_ADD && !SHORT && !MASKED)
 // slower at 128 features -- more live registers, more LDS traffic -- which is why the common case keeps its own code)
 // -- its own instantiation: as a run-time branch of the A32 kernel the record writer cost that kernel 52 bytes of
 // scratch per lane (it sits at its register limit), here the int64 ids of the row store are gone instead
-template <typename T, int VEC, int RED, bool SHORT, bool MASKED = false, bool A32 = false, int REC = 0>
+// HOT: the sum kernel of the hot-row side table (section 0b).  It never gathers from the hashed copy: when the probe
+// flagged the graph, a column id becomes a signed row index relative to `mat` -- the id itself, or the id's slot in the
+// side table -- through one 8-byte lookup per entry, which runs as a third window stage: raw ids of window k + 2 and the
+// lookup of window k + 1 are in flight while window k is consumed.
+template <typename T, int VEC, int RED, bool SHORT, bool MASKED = false, bool A32 = false, int REC = 0, bool HOT = false>
 __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, MASKED, REC>)) void spmm_merge_kernel(
     const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col,
     const T *__restrict__ value, const T *__restrict__ mat, T *__restrict__ out,
@@ -845,7 +952,10 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
   const int kl = lane & (lpr - 1);
   const uint32_t k0 = (kt * 64u + (uint32_t)kl) * VEC;
   const bool kok = k0 < K;
-  const bool relabel = use_relabel(ws.relabel_mode, ws.relabel_flag);  // wave-uniform
+  static_assert(!HOT || (RED == RED_ADD && !SHORT && !MASKED && !A32 && REC == 0 && !kPartial), "hot rows: plain sums only");
+  const bool flagged = use_relabel(ws.relabel_mode, ws.relabel_flag);  // wave-uniform
+  const bool relabel = HOT ? false : flagged;
+  const bool hot = HOT ? flagged : false;
   const T *src = relabel ? reinterpret_cast<const T *>(ws.xperm) : mat;
   const T *matk = src + (uint64_t)b * N * K + (kok ? k0 : 0u);
   const uint64_t out_b = (uint64_t)b * M * K + k0;
@@ -910,8 +1020,61 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
       if (relabel) c_l = hash_row(c_l, (uint32_t)N, ws.hash_bits, ws.hash_mul, ws.hash_shift);
     }
   };
-  load_window(wbase, c_cur, w_cur, e_cur, z_cur);
-  load_window(wbase + kWave, c_nxt, w_nxt, e_nxt, z_nxt);
+  // HOT: a third register set (c_far / w_far) -- the three sets rotate through the roles "being consumed", "raw ids, lookup
+  // in flight" and "raw ids in flight"; hw = the lookup word of the one window whose lookup is in flight
+  [[maybe_unused]] uint32_t c_far = 0, hw0 = 0, hw1 = 0;
+  [[maybe_unused]] A w_far = A(1);
+  auto hot_ids = [&](int64_t base) -> uint32_t {
+    const int64_t e = base + lane;
+    uint32_t c = 0;
+    if (e < e1) c = (uint32_t)col[e];  // (no entry permutation in this instantiation: launch_spmm)
+    return c;
+  };
+  auto hot_weights = [&](int64_t base) -> A {
+    const int64_t e = base + lane;
+    A w = A(1);
+    if (e < e1 && value != nullptr) w = Traits<T>::to_acc(value[e]);
+    return w;
+  };
+  auto hot_lookup = [&](uint32_t c) {  // (lanes past e1 hold id 0: word 0 exists)
+    if (!hot) return;
+    const uint2 wd = *reinterpret_cast<const uint2 *>(ws.hot_word + (uint64_t)(c >> 5) * 2u);  // the id's half word
+    hw0 = wd.x;
+    hw1 = wd.y;
+  };
+  auto hot_resolve = [&](uint32_t c) -> uint32_t {
+    if (!hot) return c;
+    const uint32_t b = c & 31u;
+    const uint32_t slot = (uint32_t)ws.hot_side_row + hw1 + (uint32_t)__popc(hw0 & ((1u << b) - 1u));
+    return ((hw0 >> b) & 1u) != 0 ? slot : c;
+  };
+  // Between two windows: the ids of the next window (c_res) become gatherable from the lookup word that was requested
+  // one window ago; the window behind it (c_look: raw ids requested two windows ago) gets its lookup and weights
+  // requested; the set just consumed (c_free) takes the raw ids of the window after that.  Every load goes straight
+  // into the register it stays in (no register is renamed, see below), and nothing requested here is used here.
+  auto hot_advance = [&](uint32_t &c_res, uint32_t c_look, A &w_look, uint32_t &c_free) {
+    // the registers about to be reloaded count as read HERE, where everything in flight is a window old: a window that
+    // consumed nothing (an empty tail) would otherwise leave their old loads "pending", and the compiler would drain
+    // the queue -- the lookup just requested included -- in front of the overwrite
+    asm volatile("" : : "v"(w_look), "v"(c_free), "v"(hw0), "v"(hw1));
+    c_res = hot_resolve(c_res);
+    hot_lookup(c_look);
+    w_look = hot_weights(wbase + 2 * kWave);
+    c_free = hot_ids(wbase + 3 * kWave);
+  };
+  if constexpr (HOT) {
+    c_cur = hot_ids(wbase);
+    c_nxt = hot_ids(wbase + kWave);
+    c_far = hot_ids(wbase + 2 * kWave);
+    w_cur = hot_weights(wbase);
+    w_nxt = hot_weights(wbase + kWave);
+    hot_lookup(c_cur);  // (the one lookup a wave waits for: its first window)
+    c_cur = hot_resolve(c_cur);
+    hot_lookup(c_nxt);
+  } else {
+    load_window(wbase, c_cur, w_cur, e_cur, z_cur);
+    load_window(wbase + kWave, c_nxt, w_nxt, e_nxt, z_nxt);
+  }
 
   // row ends: lane j holds rowptr[rp_base + 1 + j]
   int64_t rp_base = r0;
@@ -1111,7 +1274,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
       }
       const int64_t stop = rend < wend ? rend : wend;
       if (e < stop) {
-        accumulate_window<T, VEC, RED, MASKED>((int)(e - wbase), (int)(stop - wbase), (uint32_t)(wbase - e0),
+        accumulate_window<T, VEC, RED, MASKED, HOT>((int)(e - wbase), (int)(stop - wbase), (uint32_t)(wbase - e0),
                                                c_w, w_w, has_value, matk, K, lgG, g, val, arg, e_w, maskk,
                                                ws.rec_stride, mask_shift, z_w, mask_seg);
         e = stop;
@@ -1200,17 +1363,31 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
     }
   };
   if (!incoming) short_row_batches();  // the partition starts at a row start
-  for (;;) {
-    int st = process_window(c_cur, w_cur, e_cur, z_cur);
-    if (st == 1) break;
-    if (st == 2) continue;
-    load_window(wbase + 2 * kWave, c_cur, w_cur, e_cur, z_cur);
-    wbase += kWave;
-    st = process_window(c_nxt, w_nxt, e_nxt, z_nxt);
-    if (st == 1) break;
-    if (st == 2) continue;
-    load_window(wbase + 2 * kWave, c_nxt, w_nxt, e_nxt, z_nxt);
-    wbase += kWave;
+  if constexpr (HOT) {
+    for (;;) {  // (no short-row batches in this instantiation: process_window never returns 2)
+      if (process_window(c_cur, w_cur, e_cur, z_cur) == 1) break;
+      hot_advance(c_nxt, c_far, w_far, c_cur);
+      wbase += kWave;
+      if (process_window(c_nxt, w_nxt, e_nxt, z_nxt) == 1) break;
+      hot_advance(c_far, c_cur, w_cur, c_nxt);
+      wbase += kWave;
+      if (process_window(c_far, w_far, e_cur, z_cur) == 1) break;
+      hot_advance(c_cur, c_nxt, w_nxt, c_far);
+      wbase += kWave;
+    }
+  } else {
+    for (;;) {
+      int st = process_window(c_cur, w_cur, e_cur, z_cur);
+      if (st == 1) break;
+      if (st == 2) continue;
+      load_window(wbase + 2 * kWave, c_cur, w_cur, e_cur, z_cur);
+      wbase += kWave;
+      st = process_window(c_nxt, w_nxt, e_nxt, z_nxt);
+      if (st == 1) break;
+      if (st == 2) continue;
+      load_window(wbase + 2 * kWave, c_nxt, w_nxt, e_nxt, z_nxt);
+      wbase += kWave;
+    }
   }
   // tail: the piece of the unfinished row r1 that falls into this partition
   if (r1 < M && estart < e1) {
@@ -1597,11 +1774,24 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   w.tail_arg = reinterpret_cast<uint32_t *>(minmax ? take(sizeof(uint32_t) * plane) : nullptr);
   w.relabel_mode = 0;
   w.relabel_flag = reinterpret_cast<int *>(take(256));
-  w.xperm = (!relabelled && relabel_possible(dtype, reduce, N, K, E)) ? take(dtype_size(dtype) * (size_t)B * N * K) : nullptr;
+  // hot rows (section 0b): sums of one matrix; the side table shares the copy's region, one row of slack lets it start a
+  // whole number of rows from `mat`
+  const bool hot_scope = !relabelled && relabel_possible(dtype, reduce, N, K, E) && !minmax && B == 1 && N < ((int64_t)1 << 31);
+  w.xperm = (!relabelled && relabel_possible(dtype, reduce, N, K, E))
+                ? take(dtype_size(dtype) * (size_t)B * N * K + (hot_scope ? dtype_size(dtype) * (size_t)K : 0))
+                : nullptr;
   // (carved behind the copy of X: the position of that copy relative to the start of the workspace decides which
   // of its hot rows share a memory channel -- 3-5 % of the north-star kernel either way, measured by padding --
   // and the layout in front of it is the one the round-2/3 numbers were taken with)
   w.head_row = reinterpret_cast<int64_t *>(take(sizeof(int64_t) * P));
+  const int64_t hot_words = ceil_div(N, (int64_t)64);
+  w.hot_flag = hot_scope ? reinterpret_cast<uint8_t *>(take((size_t)N)) : nullptr;
+  w.hot_word = hot_scope ? reinterpret_cast<uint32_t *>(take(16 * (size_t)hot_words)) : nullptr;
+  w.hot_count = hot_scope ? reinterpret_cast<int64_t *>(take(sizeof(int64_t) * (size_t)hot_words)) : nullptr;
+  w.hot_scan = hot_scope ? take(scan_workspace_bytes(hot_words)) : nullptr;
+  w.hot_side = nullptr;
+  w.hot_side_row = 0;
+  w.hot_stride = TSAMD_HOT_STRIDE;
   w.hash_bits = 1;
   while (w.hash_bits < 32 && ((uint64_t)1 << w.hash_bits) < (uint64_t)(N > 1 ? N : 2)) ++w.hash_bits;
   w.hash_mul = 0x9E3779B1u;  // odd (golden-ratio) multiplier
@@ -1636,6 +1826,26 @@ size_t operand_cache_bytes(int dtype, int reduce, int64_t B, int64_t N, int64_t 
   return kOperandCacheHeader + align_up(dtype_size(dtype) * (size_t)B * N * K, 256);
 }
 
+// Hot rows: where the side table of this call starts -- inside the copy's region, a whole number of rows from `mat` (row
+// sizes here are powers of two) -- or false when the call keeps the full copy: out of scope (carve), `mat` not on a
+// 16-byte boundary, or a row index that would not fit a signed 32-bit number next to N.
+bool hot_rows_place(const Workspace &ws, const void *mat, int64_t N, uint64_t row_bytes, void **side, int32_t *side_row) {
+  if (ws.hot_flag == nullptr || ws.xperm == nullptr || ((uintptr_t)mat % 16) != 0) return false;
+  char *xp = reinterpret_cast<char *>(ws.xperm);
+  char *at = xp + (((uintptr_t)mat - (uintptr_t)xp) & (row_bytes - 1));
+  const int64_t rows = ((int64_t)(intptr_t)at - (int64_t)(intptr_t)mat) / (int64_t)row_bytes;
+  const int64_t lim = ((int64_t)1 << 31) - N - 1;
+  if (rows > lim || rows < -lim) return false;
+  *side = at;
+  *side_row = (int32_t)rows;
+  return true;
+}
+
+// `vec` = elements per lane packet, chosen by the caller: the largest power of two <= kMaxVec<T>
+// that divides K and matches the pointers' alignment.
+template <typename T>
+constexpr int kMaxVec = sizeof(T) <= 2 ? 4 : 16 / (int)sizeof(T);
+
 template <typename T, int VEC, int RED>
 int launch_spmm(const SpmmCall &c, Workspace ws) {
   const int64_t *rowptr = c.rowptr, *col = c.col;
@@ -1652,6 +1862,10 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   const uint32_t ktiles = (slots + 63) / 64;
   const unsigned int threads = kWavesPerBlock * kWave;
 
+  // hot rows: floating-point sums with full-width packets (the shapes relabel_possible admits have no others)
+  constexpr bool kHotable = !kPartial && RED == RED_ADD && VEC == kMaxVec<T> &&
+                            (std::is_same<T, float>::value || std::is_same<T, double>::value ||
+                             std::is_same<T, f16_t>::value || std::is_same<T, bf16_t>::value);
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[0], stream));
   {
     int mode = ws.xperm != nullptr && VEC > 1 && !ws.out_relabel ? 2 : 0;
@@ -1660,6 +1874,16 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
     // grad_out rows indexed by the R-MAT ROW ids of the forward, which camp like its column ids)
     if (mode == 2 && ws.wmask != nullptr) mode = 1;
     ws.relabel_mode = mode;
+    // hot rows instead of the full copy: the side table starts in the copy's region, a whole number of rows from `mat`
+    // (row sizes here are powers of two), and every index the merge kernel forms must fit a signed 32-bit row number
+    bool hot = false;
+    if constexpr (kHotable) {
+      // (lgG < 3: the side-by-side short-row kernel knows nothing of the table; rows of >= 256 bytes in full-width
+      // packets never take it, this keeps the two decisions tied together)
+      if (mode == 2 && lgG < 3 && ws.cache_state == 0 && ws.perm == nullptr)
+        hot = hot_rows_place(ws, mat, N, (uint64_t)K * sizeof(T), &ws.hot_side, &ws.hot_side_row);
+    }
+    if (!hot) ws.hot_flag = nullptr;
     const bool cached = ws.cache_state != 0 && mode != 0;
     if (mode == 2 && !(cached && ws.cache_state == 2)) {  // (a reused cache keeps the verdict of its first call)
       TSAMD_HIP_TRY(hipMemsetAsync(ws.relabel_flag, 0, 4 * sizeof(int), stream));
@@ -1667,7 +1891,25 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
                          ws.relabel_flag);
       TSAMD_LAUNCH_CHECK();
     }
-    if (mode != 0) {
+    if (hot) {
+      const int64_t words = ceil_div(N, (int64_t)64);
+      const uint32_t pslots = (uint32_t)(K * sizeof(T) / 16);
+      int lgL = 0;
+      while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
+      TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
+      hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
+      TSAMD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(spmm_hot_bits_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(words, (int64_t)4), kHotBlocks)),
+                         dim3(256), 0, stream, N, ws);
+      TSAMD_LAUNCH_CHECK();
+      // (the scan is not device-gated: on a graph the probe does not flag, its three launches run over counts nobody
+      // wrote or reads -- a few idle microseconds, no effect)
+      const int st = exclusive_scan_i64(ws.hot_count, ws.hot_count, words, nullptr, ws.hot_scan, stream);
+      if (st != TSAMD_OK) return st;
+      hipLaunchKernelGGL(spmm_hot_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, 4 * kHotBlocks)), dim3(256), 0,
+                         stream, reinterpret_cast<const void *>(mat), N, pslots, lgL, ws);
+      TSAMD_LAUNCH_CHECK();
+    } else if (mode != 0) {
       if (cached) {
         hipLaunchKernelGGL(spmm_fingerprint_kernel, dim3(kFingerprintWords), dim3(256), 0, stream,
                            reinterpret_cast<const uint4 *>(mat), (uint64_t)(B * N * K) * sizeof(T) / 16,
@@ -1738,7 +1980,9 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
     return TSAMD_ERR_UNSUPPORTED;
   } else if (lgG >= 3)
     merge(spmm_merge_kernel<T, VEC, RED, true>);
-  else
+  else if (kHotable && ws.hot_flag != nullptr) {
+    if constexpr (kHotable) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, true>);
+  } else
     merge(spmm_merge_kernel<T, VEC, RED, false>);
   TSAMD_LAUNCH_CHECK();
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[2], stream));
@@ -1765,11 +2009,6 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[3], stream));
   return TSAMD_OK;
 }
-
-// `vec` = elements per lane packet, chosen by the caller: the largest power of two <= kMaxVec<T>
-// that divides K and matches the pointers' alignment.
-template <typename T>
-constexpr int kMaxVec = sizeof(T) <= 2 ? 4 : 16 / (int)sizeof(T);
 
 // RED is the family the including unit owns (mean is the run-time flag of RED_ADD)
 template <typename T, int RED>
