@@ -112,6 +112,8 @@ struct PatternCache {
   const void *val_ptr = nullptr;
   uint32_t val_version = 0;
   Tensor value_t;
+  // what the backwards did with the entry (torch.ops.tsamd.pattern_cache_stats; read by the tests only)
+  int64_t row_hits = 0, value_hits = 0, value_fills = 0;
 };
 
 PatternCache &pattern_cache_state() {
@@ -136,6 +138,14 @@ bool pattern_cache_ctl(bool enable) {
   c.row_ptr = nullptr;
   c.val_ptr = nullptr;
   return was;
+}
+
+// torch.ops.tsamd.pattern_cache_stats() -> [enabled, backwards served from the kept row ids, backwards served from the
+// kept value[csr2csc], gathers of value[csr2csc] into the entry]; the counters only grow
+std::vector<int64_t> pattern_cache_stats() {
+  PatternCache &c = pattern_cache_state();
+  std::lock_guard<std::mutex> lock(c.mu);
+  return {c.enabled ? 1 : 0, c.row_hits, c.value_hits, c.value_fills};
 }
 
 // row[csr2csc] from the cache, or an undefined tensor when the caller should read through csr2csc instead
@@ -173,6 +183,7 @@ Tensor cached_csc_rows(const Tensor &row, const Tensor &csr2csc) {
     return Tensor();
   }
   ++pc.seen;
+  ++pc.row_hits;
   if (!pc.row_t.defined()) pc.row_t = row.index_select(0, csr2csc);
   return pc.row_t;
 }
@@ -200,6 +211,9 @@ Tensor csc_values(const Tensor &value, const Tensor &csr2csc) {
     pc.val_storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(vs));
     pc.val_ptr = v.data_ptr();
     pc.val_version = vv;
+    ++pc.value_fills;
+  } else {
+    ++pc.value_hits;
   }
   return pc.value_t;
 }
@@ -927,6 +941,7 @@ static auto registry_spmm = torch::RegisterOperators()
                            .op("tsamd::spmm_mean_owned", &spmm_mean_owned)
                            .op("tsamd::operand_cache", &operand_cache_ctl)
                            .op("tsamd::pattern_cache", &pattern_cache_ctl)
+                           .op("tsamd::pattern_cache_stats", &pattern_cache_stats)
                            .op("tsamd::relabel_ids", &relabel_ids)
                            .op("tsamd::gather_rows", &gather_rows)
                            .op("tsamd::spmm_relabelled", &spmm_relabelled);
