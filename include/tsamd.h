@@ -293,9 +293,17 @@ int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int64_t *col,
  *      per-(entry, feature) predicate:  grad_mat[b, n, k] = sum_{e in column n, bit k set}
  *      round_T(value[e] * grad_out[b, row[e], k]), accumulated in fp32 (fp64 for f64), rounded once.
  * Deterministic (fixed summation order), every element of grad_mat written exactly once (no memset of
- * the result), the device-scope atomics of tsamd_spmm_minmax_bw are gone.  grad_value is computed as
- * in tsamd_spmm_minmax_bw.  Either output may be NULL.  E must be < 2^32.  Replaces the same ATen
- * composition (csrc/spmm.cpp:204-242, 264-302). */
+ * the result), the device-scope atomics of tsamd_spmm_minmax_bw are gone.  grad_value: beside grad_mat, a masked
+ * SDDMM over the same masks when K * element size is a multiple of 16 and mat and grad_out are 16-byte aligned;
+ * otherwise the row-parallel kernel of tsamd_spmm_minmax_bw (no global atomics either).  Either output may be
+ * NULL.  Replaces the same ATen composition (csrc/spmm.cpp:204-242, 264-302).
+ * Status, in this order, before anything is launched (all three _bw_csc* entries; tests/test_cabi_minmax_bw.py):
+ *   INVALID      a negative size; on a non-empty output (B * M * K > 0) a NULL rowptr, col, mat, grad_out or
+ *                arg_out; grad_mat wanted, E > 0 and a NULL colptr, csr2csc or row
+ *   UNSUPPORTED  a dtype that is not f32 / f64 / f16 / bf16; N, M or E >= 2^32 or K >= 2^31 (32-bit ids inside the
+ *                kernels) -- nothing else: this entry serves every combination of outputs and alignments
+ *   WORKSPACE    grad_mat wanted on a non-empty problem and the workspace is NULL, smaller than
+ *                tsamd_spmm_minmax_bw_csc_workspace_bytes() or not 256-byte aligned */
 size_t tsamd_spmm_minmax_bw_csc_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K,
                                                 int64_t E);
 int tsamd_spmm_minmax_bw_csc(int dtype, const int64_t *rowptr, const int64_t *col, const void *value,
@@ -310,9 +318,11 @@ int tsamd_spmm_minmax_bw_csc(int dtype, const int64_t *rowptr, const int64_t *co
  * 1.07 -> 0.54 GB each way).  E < 2^31 ("no winner" = E as in tsamd_spmm).
  *   tsamd_spmm_minmax_arg32: tsamd_spmm / tsamd_spmm_cached (cache == NULL: stateless) for reduce = MIN | MAX with
  *     arg_out32 [B, M, K] int32; workspace = tsamd_spmm_workspace_bytes / tsamd_spmm_cached_workspace_bytes.
- *   tsamd_spmm_minmax_bw_csc_arg32: tsamd_spmm_minmax_bw_csc on those ids; TSAMD_ERR_UNSUPPORTED when grad_value is
- *     wanted and the rows are not 16-byte packets (or grad_mat is NULL): widen the ids and take
- *     tsamd_spmm_minmax_bw / _csc instead. */
+ *   tsamd_spmm_minmax_bw_csc_arg32: tsamd_spmm_minmax_bw_csc on those ids, same workspace.  TSAMD_ERR_UNSUPPORTED,
+ *     besides what that entry returns it for: E >= 2^31 (checked first of all); grad_value wanted and not computable
+ *     as the masked SDDMM, i.e. grad_mat is NULL, K * element size is no multiple of 16, or mat or grad_out is not
+ *     16-byte aligned (the row-parallel kernel reads int64 ids: widen them and take tsamd_spmm_minmax_bw / _csc).
+ *     A NULL arg_out32 on a non-empty output is INVALID before the dtype is looked at. */
 int tsamd_spmm_minmax_arg32(int dtype, int reduce, const int64_t *rowptr, const int64_t *col, const void *value,
                             const void *mat, void *out, int32_t *arg_out32, int64_t B, int64_t M, int64_t N,
                             int64_t K, int64_t E, void *workspace, size_t workspace_bytes, void *cache,
@@ -336,9 +346,14 @@ int tsamd_spmm_minmax_bw_csc_arg32(int dtype, const int64_t *rowptr, const int64
  *   tsamd_spmm_minmax_records_bytes        size of `records` ([B][E] records of 8..  32-bit words, see csrc/spmm_internal.h)
  *   tsamd_spmm_minmax_records              out [B, M, K] and records; row [E] = COO row ids; E < 2^31
  *   tsamd_spmm_minmax_winrec               records from int32 ids (what tsamd_spmm_minmax_bw_csc_arg32 does first)
- *   tsamd_spmm_minmax_bw_csc_records       tsamd_spmm_minmax_bw_csc on such records: grad_mat (required) and grad_value
- *                                          (optional; TSAMD_ERR_UNSUPPORTED unless the rows are 16-byte packets);
- *                                          has_value: the matrix had values (they are in the records) */
+ *   tsamd_spmm_minmax_bw_csc_records       tsamd_spmm_minmax_bw_csc on such records; has_value: the matrix had values
+ *                                          (they are in the records).  TSAMD_ERR_UNSUPPORTED, besides what that entry
+ *                                          returns it for: grad_mat is NULL (checked first of all: grad_value alone
+ *                                          reads ids); E >= 2^31; grad_value wanted and K * element size no multiple
+ *                                          of 16, or mat or grad_out not 16-byte aligned -- there is no id to fall back
+ *                                          on.  NULL records with E > 0 on a non-empty output: INVALID, checked second.
+ *                                          Workspace: tsamd_spmm_minmax_bw_csc_records_workspace_bytes(), which is the
+ *                                          _csc figure less tsamd_spmm_minmax_records_bytes() */
 int tsamd_spmm_minmax_records_in_forward(int dtype, int64_t B, int64_t M, int64_t K, int64_t E); /* 1: the merge kernel writes them */
 size_t tsamd_spmm_minmax_records_bytes(int64_t B, int64_t K, int64_t E);
 size_t tsamd_spmm_minmax_records_workspace_bytes(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K,

@@ -29,12 +29,35 @@ bool stream_is_capturing(void *stream) {
          cs != hipStreamCaptureStatusNone;
 }
 
+// "The same tensor contents as last time", as far as torch can tell: the same storage object (held weakly: while it is
+// alive its address cannot be handed to another tensor), the same data pointer and the same version counter.
+// Inference tensors have no version counter: no cache below ever keeps or matches one (their callers turn them away).
+struct TensorIdentity {
+  c10::weak_intrusive_ptr<c10::StorageImpl> storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
+      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
+  const void *ptr = nullptr;
+  uint32_t version = 0;
+
+  static uint32_t version_of(const Tensor &t) { return t.unsafeGetTensorImpl()->version_counter().current_version(); }
+  bool matches(const Tensor &t) const {
+    if (ptr != t.data_ptr() || version != version_of(t)) return false;
+    auto alive = storage.lock();
+    return alive && alive.get() == t.storage().unsafeGetStorageImpl();
+  }
+  void rearm(const Tensor &t) {
+    storage = c10::weak_intrusive_ptr<c10::StorageImpl>(
+        c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(t.storage().unsafeGetStorageImpl()));
+    ptr = t.data_ptr();
+    version = version_of(t);
+  }
+  void forget() { ptr = nullptr; }
+};
+
 // ---- operand cache (include/tsamd.h: tsamd_spmm_cached) ------------------------------------------------
 // One entry: the relabelled copy of the last dense operand that needed one.  A call may reuse it when the
-// operand is provably the same tensor contents as far as torch can tell -- same storage object (held weakly:
-// while it is alive its address cannot be handed to another tensor), same data pointer, same version
-// counter, same shape / dtype / device / stream, same sparse pattern (col pointer and length) and reduction
-// class -- and the kernel side re-checks a sampled fingerprint on the device.
+// operand is provably the same tensor contents as far as torch can tell (TensorIdentity), with the same shape /
+// dtype / device / stream, same sparse pattern (col pointer, version and length) and reduction class -- and the
+// kernel side re-checks a sampled fingerprint on the device.
 //
 // OPT-IN (off by default): the reference boundary keeps no state between calls (csrc/cuda/spmm_cuda.cu:102,134
 // allocate fresh outputs, nothing else survives), and neither the version counter nor a SAMPLED fingerprint can
@@ -45,13 +68,10 @@ bool stream_is_capturing(void *stream) {
 struct OperandCache {
   std::mutex mu;
   bool enabled = false;
-  c10::weak_intrusive_ptr<c10::StorageImpl> storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
-      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
-  const void *ptr = nullptr, *col_ptr = nullptr;
-  uint32_t version = 0, col_version = 0;
-  std::vector<int64_t> sizes;
-  int dtype = -1, red_class = -1, device = -1;
-  int64_t E = -1;
+  TensorIdentity mat;
+  // the rest of the key: dtype, reduction class, device, col pointer / version / length, sizes of mat
+  using Key = std::tuple<int, int, int, const void *, uint32_t, int64_t, std::vector<int64_t>>;
+  Key key;
   void *stream = nullptr;
   Tensor buf;
   int64_t hits = 0, fills = 0;
@@ -75,7 +95,7 @@ std::vector<int64_t> operand_cache_ctl(bool enable) {
   std::vector<int64_t> r = {c.enabled ? 1 : 0, c.hits, c.fills};
   c.enabled = enable;
   c.buf = Tensor();
-  c.ptr = nullptr;
+  c.mat.forget();
   return r;
 }
 
@@ -83,7 +103,7 @@ std::vector<int64_t> operand_cache_ctl(bool enable) {
 // grad_mat = A^T * grad_out multiplies by the CSC view (colptr, row[csr2csc], value[csr2csc]).  The reference
 // gathers row[csr2csc] and value[csr2csc] anew in every backward (spmm.cpp:104-106).  The row ids of the CSC
 // order only depend on the PATTERN, which a training loop does not change: they are gathered once and kept
-// (one entry; key = storage objects, data pointers and version counters of `row` and `csr2csc`), so that every
+// (one entry; key = the identities of `row` and `csr2csc`), so that every
 // later backward reads them sequentially; the stream is part of the key (a backward on another stream starts a
 // new entry instead of reading arrays whose producer it is not ordered after).  TSAMD_PATTERN_CACHE=0 turns it off (then, and for a pattern seen
 // for the first time in a no-reuse setting, the kernel reads (row, value) through csr2csc -- tsamd_spmm_permuted).
@@ -95,22 +115,14 @@ std::vector<int64_t> operand_cache_ctl(bool enable) {
 struct PatternCache {
   std::mutex mu;
   bool enabled = true;
-  c10::weak_intrusive_ptr<c10::StorageImpl> row_storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
-      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
-  c10::weak_intrusive_ptr<c10::StorageImpl> perm_storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
-      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
-  const void *row_ptr = nullptr, *perm_ptr = nullptr;
-  uint32_t row_version = 0, perm_version = 0;
+  TensorIdentity row, perm;
   int64_t E = -1;
   void *stream = nullptr;  // the gathered arrays are produced and consumed on one stream only (no cross-stream events)
   int seen = 0;  // calls with this key so far
   Tensor row_t;
   // value[csr2csc] of FIXED edge weights (a value tensor that does not require grad, e.g. GCN's normalised
-  // adjacency): valid while the pattern entry is and the value tensor keeps its storage / pointer / version
-  c10::weak_intrusive_ptr<c10::StorageImpl> val_storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
-      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
-  const void *val_ptr = nullptr;
-  uint32_t val_version = 0;
+  // adjacency): valid while the pattern entry is and the value tensor keeps its identity
+  TensorIdentity val;
   Tensor value_t;
   // what the backwards did with the entry (torch.ops.tsamd.pattern_cache_stats; read by the tests only)
   int64_t row_hits = 0, value_hits = 0, value_fills = 0;
@@ -135,8 +147,8 @@ bool pattern_cache_ctl(bool enable) {
   c.enabled = enable;
   c.row_t = Tensor();
   c.value_t = Tensor();
-  c.row_ptr = nullptr;
-  c.val_ptr = nullptr;
+  c.row.forget();
+  c.val.forget();
   return was;
 }
 
@@ -156,30 +168,17 @@ Tensor cached_csc_rows(const Tensor &row, const Tensor &csr2csc) {
   if (!pc.enabled || row.is_inference() || csr2csc.is_inference() || !row.is_contiguous() || !csr2csc.is_contiguous() ||
       !row.device().is_cuda() || stream_is_capturing(current_stream(row)))
     return Tensor();
-  c10::StorageImpl *rs = row.storage().unsafeGetStorageImpl(), *ps = csr2csc.storage().unsafeGetStorageImpl();
-  const uint32_t rv = row.unsafeGetTensorImpl()->version_counter().current_version();
-  const uint32_t pv = csr2csc.unsafeGetTensorImpl()->version_counter().current_version();
   void *stream = current_stream(row);
   std::lock_guard<std::mutex> lock(pc.mu);
-  bool same = pc.row_ptr == row.data_ptr() && pc.perm_ptr == csr2csc.data_ptr() && pc.E == row.numel() &&
-              pc.row_version == rv && pc.perm_version == pv && pc.stream == stream;
-  if (same) {
-    auto a = pc.row_storage.lock(), b = pc.perm_storage.lock();
-    same = a && b && a.get() == rs && b.get() == ps;
-  }
-  if (!same) {
-    pc.row_storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(rs));
-    pc.perm_storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(ps));
-    pc.row_ptr = row.data_ptr();
-    pc.perm_ptr = csr2csc.data_ptr();
-    pc.row_version = rv;
-    pc.perm_version = pv;
+  if (!(pc.E == row.numel() && pc.stream == stream && pc.row.matches(row) && pc.perm.matches(csr2csc))) {
+    pc.row.rearm(row);
+    pc.perm.rearm(csr2csc);
     pc.E = row.numel();
     pc.stream = stream;
     pc.seen = 1;
     pc.row_t = Tensor();
     pc.value_t = Tensor();
-    pc.val_ptr = nullptr;
+    pc.val.forget();
     return Tensor();
   }
   ++pc.seen;
@@ -195,42 +194,38 @@ Tensor csc_values(const Tensor &value, const Tensor &csr2csc) {
   PatternCache &pc = pattern_cache_state();
   if (needs_grad(value) || v.is_inference() || !v.is_contiguous() || stream_is_capturing(current_stream(v)))
     return v.index_select(0, csr2csc);
-  c10::StorageImpl *vs = v.storage().unsafeGetStorageImpl();
-  const uint32_t vv = v.unsafeGetTensorImpl()->version_counter().current_version();
   std::lock_guard<std::mutex> lock(pc.mu);
-  if (!pc.enabled || pc.perm_ptr != csr2csc.data_ptr() || !pc.row_t.defined() || pc.stream != current_stream(v))
+  if (!pc.enabled || pc.perm.ptr != csr2csc.data_ptr() || !pc.row_t.defined() || pc.stream != current_stream(v))
     return v.index_select(0, csr2csc);
-  bool same = pc.value_t.defined() && pc.val_ptr == v.data_ptr() && pc.val_version == vv &&
-              pc.value_t.scalar_type() == v.scalar_type() && pc.value_t.numel() == v.numel();
-  if (same) {
-    auto a = pc.val_storage.lock();
-    same = a && a.get() == vs;
-  }
-  if (!same) {
-    pc.value_t = v.index_select(0, csr2csc);
-    pc.val_storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(vs));
-    pc.val_ptr = v.data_ptr();
-    pc.val_version = vv;
-    ++pc.value_fills;
-  } else {
+  if (pc.value_t.defined() && pc.value_t.scalar_type() == v.scalar_type() && pc.value_t.numel() == v.numel() &&
+      pc.val.matches(v)) {
     ++pc.value_hits;
+  } else {
+    pc.value_t = v.index_select(0, csr2csc);
+    pc.val.rearm(v);
+    ++pc.value_fills;
   }
   return pc.value_t;
 }
 
-// Forward launch: mirrors the argument checks of spmm_cpu.cpp:12-24 / spmm_cuda.cu:96-109.
-// arg32: min / max winners as int32 ids (callers that keep them for their own backward only, tsamd.h)
-std::tuple<Tensor, OptTensor> spmm_fw(const Tensor &rowptr, const Tensor &col,
-                                      const OptTensor &opt_value, Tensor mat,
-                                      const std::string &reduce, const OptTensor &opt_perm = std::nullopt,
-                                      bool arg32 = false) {
+// ---- the forward's arguments, once ----------------------------------------------------------------------
+// B, M, N, K, E of a product; mat.dim() >= 2
+struct SpmmDims {
+  int64_t B, M, N, K, E;
+};
+SpmmDims spmm_dims(const Tensor &rowptr, const Tensor &col, const Tensor &mat) {
+  const int64_t N = mat.size(-2), K = mat.size(-1);
+  return {(N * K) > 0 ? mat.numel() / (N * K) : 1, rowptr.numel() - 1, N, K, col.numel()};
+}
+
+// The argument checks of spmm_cpu.cpp:12-24 / spmm_cuda.cu:96-109, in the reference's order.
+void check_spmm_args(const Tensor &rowptr, const Tensor &col, const OptTensor &opt_value, const Tensor &mat) {
   check_gpu(rowptr, "rowptr");
   check_gpu(col, "col");
   if (opt_value.has_value()) check_gpu(opt_value.value(), "value");
   check_gpu(mat, "mat");
   TORCH_CHECK(rowptr.dim() == 1 && col.dim() == 1, "Input mismatch");
-  TORCH_CHECK(rowptr.scalar_type() == at::kLong && col.scalar_type() == at::kLong,
-              "rowptr and col must be int64");
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong && col.scalar_type() == at::kLong, "rowptr and col must be int64");
   if (opt_value.has_value()) {
     TORCH_CHECK(opt_value.value().dim() == 1, "Input mismatch");
     TORCH_CHECK(opt_value.value().size(0) == col.size(0), "Input mismatch");
@@ -238,53 +233,89 @@ std::tuple<Tensor, OptTensor> spmm_fw(const Tensor &rowptr, const Tensor &col,
                 mat.scalar_type(), " but found ", opt_value.value().scalar_type());
   }
   TORCH_CHECK(mat.dim() >= 2, "Input mismatch");
-  c10::hip::HIPGuard guard(rowptr.get_device());
+}
 
-  mat = mat.contiguous();
-  Tensor rp = rowptr.contiguous(), c = col.contiguous();
-  OptTensor value = opt_value.has_value() ? OptTensor(opt_value.value().contiguous()) : std::nullopt;
-  auto sizes = mat.sizes().vec();
-  const int64_t M = rp.numel() - 1, E = c.numel();
-  const int64_t N = mat.size(-2), K = mat.size(-1);
-  const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
-  sizes[mat.dim() - 2] = M;
-  Tensor out = torch::empty(sizes, mat.options().requires_grad(false));
-  const int red = reduce_code(reduce);
-  OptTensor arg_out = std::nullopt;
-  int64_t *arg_ptr = nullptr;
-  arg32 = arg32 && (red == TSAMD_MIN || red == TSAMD_MAX) && E < ((int64_t)1 << 31) && !opt_perm.has_value();
-  if (arg32) {
-    arg_out = torch::empty(sizes, rp.options().dtype(at::kInt));
-  } else if (red == TSAMD_MIN || red == TSAMD_MAX) {
-    arg_out = torch::empty(sizes, rp.options());
-    arg_ptr = arg_out.value().data_ptr<int64_t>();
-  }
-  const int dt = dtype_code(mat);
-  const size_t need = tsamd_spmm_workspace_bytes(dt, red, B, M, N, K, E);
-  Tensor ws = workspace(need, mat);
-  if (arg32) {
-    check_status(tsamd_spmm_minmax_arg32(dt, red, rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(), ptr_or_null(value),
-                                         mat.data_ptr(), out.data_ptr(), arg_out.value().data_ptr<int32_t>(), B, M, N,
-                                         K, E, ws.data_ptr(), (size_t)ws.numel(), nullptr, 0, 0, current_stream(mat)),
+// What a forward hands to the C-ABI, from checked arguments: the contiguous operands, the sizes, the codes, and the
+// outputs.  Winners of min / max: int64 ids (the API's arg_out), int32 ids where the caller keeps them for its own
+// backward only and they fit, or none (the caller brings records).
+enum class ArgIds { Wide, NarrowIfFits, None };
+struct SpmmShape : SpmmDims {
+  Tensor rowptr, col, mat;
+  OptTensor value;
+  int dt, red;
+  Tensor out;
+  OptTensor arg_out;
+  bool arg32 = false;
+  const int64_t *rp() const { return rowptr.data_ptr<int64_t>(); }
+  const int64_t *cp() const { return col.data_ptr<int64_t>(); }
+  int64_t *arg64() const { return arg_out.has_value() && !arg32 ? arg_out.value().data_ptr<int64_t>() : nullptr; }
+};
+SpmmShape spmm_shape(const Tensor &rowptr, const Tensor &col, const OptTensor &opt_value, const Tensor &mat, int red,
+                     ArgIds ids) {
+  SpmmShape s;
+  s.mat = mat.contiguous();
+  s.rowptr = rowptr.contiguous();
+  s.col = col.contiguous();
+  if (opt_value.has_value()) s.value = opt_value.value().contiguous();
+  static_cast<SpmmDims &>(s) = spmm_dims(s.rowptr, s.col, s.mat);
+  auto sizes = s.mat.sizes().vec();
+  sizes[s.mat.dim() - 2] = s.M;
+  s.out = torch::empty(sizes, s.mat.options().requires_grad(false));
+  s.red = red;
+  const bool minmax = red == TSAMD_MIN || red == TSAMD_MAX;
+  s.arg32 = minmax && ids == ArgIds::NarrowIfFits && s.E < ((int64_t)1 << 31);
+  if (minmax && ids != ArgIds::None)
+    s.arg_out = torch::empty(sizes, s.arg32 ? s.rowptr.options().dtype(at::kInt) : s.rowptr.options());
+  s.dt = dtype_code(s.mat);
+  return s;
+}
+
+// One forward on checked arguments: exactly one C-ABI call.
+// arg32: min / max winners as int32 ids (callers that keep them for their own backward only, tsamd.h)
+// opt_perm: entries through a permutation (the CSC view in the backward)
+// copy: the operand cache's buffer (spmm_fw_cached); copy_valid: it holds this operand's copy already
+std::tuple<Tensor, OptTensor> spmm_run(const Tensor &rowptr, const Tensor &col, const OptTensor &opt_value,
+                                       const Tensor &mat, int red, const OptTensor &opt_perm, bool arg32,
+                                       const Tensor &copy = Tensor(), bool copy_valid = false) {
+  c10::hip::HIPGuard guard(rowptr.get_device());
+  const ArgIds ids = arg32 && !opt_perm.has_value() ? ArgIds::NarrowIfFits : ArgIds::Wide;
+  const SpmmShape s = spmm_shape(rowptr, col, opt_value, mat, red, ids);
+  void *stream = current_stream(s.mat);
+  Tensor ws = workspace(copy.defined() ? tsamd_spmm_cached_workspace_bytes(s.dt, red, s.B, s.M, s.N, s.K, s.E)
+                                       : tsamd_spmm_workspace_bytes(s.dt, red, s.B, s.M, s.N, s.K, s.E),
+                        s.mat);
+  void *w = ws.data_ptr(), *cbuf = copy.defined() ? copy.data_ptr() : nullptr;
+  const size_t wb = (size_t)ws.numel(), cbytes = copy.defined() ? (size_t)copy.numel() : 0;
+  if (s.arg32) {
+    check_status(tsamd_spmm_minmax_arg32(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(),
+                                         s.out.data_ptr(), s.arg_out.value().data_ptr<int32_t>(), s.B, s.M, s.N, s.K, s.E,
+                                         w, wb, cbuf, cbytes, copy_valid ? 1 : 0, stream),
                  "tsamd_spmm_minmax_arg32");
-    return std::make_tuple(out, arg_out);
-  }
-  if (opt_perm.has_value()) {  // entries through a permutation (the CSC view in the backward)
+  } else if (opt_perm.has_value()) {
     check_index(opt_perm.value(), "perm");
-    TORCH_CHECK(opt_perm.value().numel() == E, "Input mismatch");
+    TORCH_CHECK(opt_perm.value().numel() == s.E, "Input mismatch");
     Tensor perm = opt_perm.value().contiguous();
-    check_status(tsamd_spmm_permuted(dt, red, rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(),
-                                     ptr_or_null(value), perm.data_ptr<int64_t>(), mat.data_ptr(),
-                                     out.data_ptr(), arg_ptr, B, M, N, K, E, ws.data_ptr(),
-                                     (size_t)ws.numel(), current_stream(mat)),
+    check_status(tsamd_spmm_permuted(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), perm.data_ptr<int64_t>(),
+                                     s.mat.data_ptr(), s.out.data_ptr(), s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb,
+                                     stream),
                  "tsamd_spmm_permuted");
-    return std::make_tuple(out, arg_out);
+  } else if (copy.defined()) {
+    check_status(tsamd_spmm_cached(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
+                                   s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, cbuf, cbytes, copy_valid ? 1 : 0, stream),
+                 "tsamd_spmm_cached");
+  } else {
+    check_status(tsamd_spmm(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
+                            s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, stream),
+                 "tsamd_spmm");
   }
-  check_status(tsamd_spmm(dt, red, rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(),
-                          ptr_or_null(value), mat.data_ptr(), out.data_ptr(), arg_ptr, B, M, N, K,
-                          E, ws.data_ptr(), (size_t)ws.numel(), current_stream(mat)),
-               "tsamd_spmm");
-  return std::make_tuple(out, arg_out);
+  return std::make_tuple(s.out, s.arg_out);
+}
+
+std::tuple<Tensor, OptTensor> spmm_fw(const Tensor &rowptr, const Tensor &col, const OptTensor &opt_value,
+                                      const Tensor &mat, const std::string &reduce,
+                                      const OptTensor &opt_perm = std::nullopt, bool arg32 = false) {
+  check_spmm_args(rowptr, col, opt_value, mat);
+  return spmm_run(rowptr, col, opt_value, mat, reduce_code(reduce), opt_perm, arg32);
 }
 
 // the forward of the registered ops: tsamd_spmm, or tsamd_spmm_cached when this product copies its operand
@@ -296,67 +327,32 @@ std::tuple<Tensor, OptTensor> spmm_fw_cached(const Tensor &rowptr, const Tensor 
                   mat_in.is_contiguous() && !mat_in.is_inference() && rowptr.device().is_cuda() &&
                   rowptr.dim() == 1 && col.dim() == 1 && col.is_contiguous() && rowptr.is_contiguous() &&
                   (reinterpret_cast<uintptr_t>(mat_in.data_ptr()) % 16) == 0;
+  if (eligible) {
+    const at::ScalarType t = mat_in.scalar_type();
+    eligible = t == at::kFloat || t == at::kDouble || t == at::kHalf || t == at::kBFloat16 || t == at::kInt || t == at::kLong;
+  }
   size_t cache_bytes = 0;
-  int64_t B = 1, M = 0, N = 0, K = 0, E = 0;
+  int64_t E = 0;
   int dt = -1;
   if (eligible) {
-    switch (mat_in.scalar_type()) {
-      case at::kFloat: case at::kDouble: case at::kHalf: case at::kBFloat16: case at::kInt: case at::kLong:
-        dt = dtype_code(mat_in);
-        break;
-      default: eligible = false;
-    }
-  }
-  if (eligible) {
-    M = rowptr.numel() - 1;
-    E = col.numel();
-    N = mat_in.size(-2);
-    K = mat_in.size(-1);
-    B = (N * K) > 0 ? mat_in.numel() / (N * K) : 1;
-    cache_bytes = tsamd_spmm_operand_cache_bytes(dt, red, B, M, N, K, E);
+    const SpmmDims d = spmm_dims(rowptr, col, mat_in);
+    E = d.E;
+    dt = dtype_code(mat_in);
+    cache_bytes = tsamd_spmm_operand_cache_bytes(dt, red, d.B, d.M, d.N, d.K, d.E);
   }
   if (!eligible || cache_bytes == 0 || stream_is_capturing(current_stream(mat_in)))
     return spmm_fw(rowptr, col, opt_value, mat_in, reduce, std::nullopt, arg32);
 
-  // same checks as spmm_fw
-  check_gpu(col, "col");
-  if (opt_value.has_value()) check_gpu(opt_value.value(), "value");
-  TORCH_CHECK(rowptr.scalar_type() == at::kLong && col.scalar_type() == at::kLong, "rowptr and col must be int64");
-  if (opt_value.has_value()) {
-    TORCH_CHECK(opt_value.value().dim() == 1, "Input mismatch");
-    TORCH_CHECK(opt_value.value().size(0) == col.size(0), "Input mismatch");
-    TORCH_CHECK(opt_value.value().scalar_type() == mat_in.scalar_type(), "expected scalar type ",
-                mat_in.scalar_type(), " but found ", opt_value.value().scalar_type());
-  }
+  check_spmm_args(rowptr, col, opt_value, mat_in);  // (before the entry is re-armed: a refused call leaves it alone)
   c10::hip::HIPGuard guard(rowptr.get_device());
-  OptTensor value = opt_value.has_value() ? OptTensor(opt_value.value().contiguous()) : std::nullopt;
-  auto sizes = mat_in.sizes().vec();
-  sizes[mat_in.dim() - 2] = M;
-  Tensor out = torch::empty(sizes, mat_in.options().requires_grad(false));
-  OptTensor arg_out = std::nullopt;
-  int64_t *arg_ptr = nullptr;
-  arg32 = arg32 && (red == TSAMD_MIN || red == TSAMD_MAX) && E < ((int64_t)1 << 31);
-  if (arg32) {
-    arg_out = torch::empty(sizes, rowptr.options().dtype(at::kInt));
-  } else if (red == TSAMD_MIN || red == TSAMD_MAX) {
-    arg_out = torch::empty(sizes, rowptr.options());
-    arg_ptr = arg_out.value().data_ptr<int64_t>();
-  }
   void *stream = current_stream(mat_in);
-  c10::StorageImpl *simpl = mat_in.storage().unsafeGetStorageImpl();
-  const uint32_t version = mat_in.unsafeGetTensorImpl()->version_counter().current_version();
-  const uint32_t col_version = col.is_inference() ? 0u : col.unsafeGetTensorImpl()->version_counter().current_version();
-  const int red_class = (red == TSAMD_MIN || red == TSAMD_MAX) ? 1 : 0;
+  const uint32_t col_version = col.is_inference() ? 0u : TensorIdentity::version_of(col);
+  const OperandCache::Key key{dt, (red == TSAMD_MIN || red == TSAMD_MAX) ? 1 : 0, (int)mat_in.get_device(), col.data_ptr(),
+                              col_version, E, mat_in.sizes().vec()};
 
   std::lock_guard<std::mutex> lock(oc.mu);
-  bool valid = false;
-  if (oc.buf.defined() && oc.ptr == mat_in.data_ptr() && oc.version == version && oc.dtype == dt &&
-      oc.red_class == red_class && oc.device == mat_in.get_device() && oc.stream == stream &&
-      oc.col_ptr == col.data_ptr() && oc.col_version == col_version && oc.E == E && oc.sizes == mat_in.sizes().vec() &&
-      (size_t)oc.buf.numel() >= cache_bytes) {
-    auto locked = oc.storage.lock();  // the storage the copy was made from is still alive and is this one
-    valid = locked && locked.get() == simpl;
-  }
+  const bool valid = oc.buf.defined() && oc.key == key && oc.stream == stream && (size_t)oc.buf.numel() >= cache_bytes &&
+                     oc.mat.matches(mat_in);
   if (!valid) {
     // a buffer is only ever touched on the stream it was allocated under (the caching allocator's reuse is
     // stream-ordered on that stream): another stream gets a fresh one instead of racing with pending work
@@ -365,37 +361,12 @@ std::tuple<Tensor, OptTensor> spmm_fw_cached(const Tensor &rowptr, const Tensor 
       oc.buf = Tensor();  // release before the new allocation
       oc.buf = workspace(cache_bytes, mat_in);
     }
-    oc.storage = c10::weak_intrusive_ptr<c10::StorageImpl>(
-        c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(simpl));
-    oc.ptr = mat_in.data_ptr();
-    oc.version = version;
-    oc.dtype = dt;
-    oc.red_class = red_class;
-    oc.device = mat_in.get_device();
+    oc.mat.rearm(mat_in);
+    oc.key = key;
     oc.stream = stream;
-    oc.col_ptr = col.data_ptr();
-    oc.col_version = col_version;
-    oc.E = E;
-    oc.sizes = mat_in.sizes().vec();
-    ++oc.fills;
-  } else {
-    ++oc.hits;
   }
-  Tensor ws = workspace(tsamd_spmm_cached_workspace_bytes(dt, red, B, M, N, K, E), mat_in);
-  if (arg32) {
-    check_status(tsamd_spmm_minmax_arg32(dt, red, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                         ptr_or_null(value), mat_in.data_ptr(), out.data_ptr(),
-                                         arg_out.value().data_ptr<int32_t>(), B, M, N, K, E, ws.data_ptr(),
-                                         (size_t)ws.numel(), oc.buf.data_ptr(), (size_t)oc.buf.numel(), valid ? 1 : 0,
-                                         stream),
-                 "tsamd_spmm_minmax_arg32");
-    return std::make_tuple(out, arg_out);
-  }
-  check_status(tsamd_spmm_cached(dt, red, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), ptr_or_null(value),
-                                 mat_in.data_ptr(), out.data_ptr(), arg_ptr, B, M, N, K, E, ws.data_ptr(),
-                                 (size_t)ws.numel(), oc.buf.data_ptr(), (size_t)oc.buf.numel(), valid ? 1 : 0, stream),
-               "tsamd_spmm_cached");
-  return std::make_tuple(out, arg_out);
+  ++(valid ? oc.hits : oc.fills);
+  return spmm_run(rowptr, col, opt_value, mat_in, red, std::nullopt, arg32, oc.buf, valid);
 }
 
 Tensor spmm_value_bw(const Tensor &row, const Tensor &rowptr, const Tensor &col, Tensor mat,
@@ -514,12 +485,11 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
         (mat.scalar_type() == at::kFloat || mat.scalar_type() == at::kHalf || mat.scalar_type() == at::kBFloat16) &&
         (!has_value || value.scalar_type() == mat.scalar_type()) && opt_row.value().numel() == col.numel() &&
         !stream_is_capturing(current_stream(mat))) {
-      const int64_t M = rowptr.numel() - 1, E = col.numel(), N = mat.size(-2), K = mat.size(-1);
-      const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
-      const int dt = dtype_code(mat);
-      const bool value_grad_ok = !(has_value && needs_grad(value)) || (K * (int64_t)mat.element_size()) % 16 == 0;
-      use_records = M > 0 && E > 0 && value_grad_ok && tsamd_spmm_minmax_records_in_forward(dt, B, M, K, E) == 1 &&
-                    tsamd_spmm_minmax_records_bytes(B, K, E) <= (size_t)(3 * 4 * B * M * K);
+      const SpmmDims d = spmm_dims(rowptr, col, mat);
+      const bool value_grad_ok = !(has_value && needs_grad(value)) || (d.K * (int64_t)mat.element_size()) % 16 == 0;
+      use_records = d.M > 0 && d.E > 0 && value_grad_ok &&
+                    tsamd_spmm_minmax_records_in_forward(dtype_code(mat), d.B, d.M, d.K, d.E) == 1 &&
+                    tsamd_spmm_minmax_records_bytes(d.B, d.K, d.E) <= (size_t)(3 * 4 * d.B * d.M * d.K);
     }
     Tensor out, arg_out;
     if (use_records) {
@@ -527,21 +497,17 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
       check_index(col, "col");
       check_index(opt_row.value(), "row");
       c10::hip::HIPGuard guard(mat.get_device());
-      Tensor m = mat.contiguous(), rp = rowptr.contiguous(), c = col.contiguous(), r = opt_row.value().contiguous();
-      OptTensor vc = has_value ? OptTensor(value.contiguous()) : std::nullopt;
-      const int64_t M = rp.numel() - 1, E = c.numel(), N = m.size(-2), K = m.size(-1);
-      const int64_t B = (N * K) > 0 ? m.numel() / (N * K) : 1;
-      const int dt = dtype_code(m), red = is_max ? TSAMD_MAX : TSAMD_MIN;
-      if (has_value) TORCH_CHECK(value.dim() == 1 && value.size(0) == E, "Input mismatch");
-      auto sizes = m.sizes().vec();
-      sizes[m.dim() - 2] = M;
-      out = torch::empty(sizes, m.options().requires_grad(false));
-      records = torch::empty({(int64_t)(tsamd_spmm_minmax_records_bytes(B, K, E) / 4)}, rp.options().dtype(at::kInt));
-      Tensor ws = workspace(tsamd_spmm_minmax_records_workspace_bytes(dt, red, B, M, N, K, E), m);
-      check_status(tsamd_spmm_minmax_records(dt, red, rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(), ptr_or_null(vc),
-                                             m.data_ptr(), out.data_ptr(), r.data_ptr<int64_t>(),
-                                             reinterpret_cast<uint32_t *>(records.data_ptr<int32_t>()), B, M, N, K, E,
-                                             ws.data_ptr(), (size_t)ws.numel(), current_stream(m)),
+      const SpmmShape s = spmm_shape(rowptr, col, v, mat, is_max ? TSAMD_MAX : TSAMD_MIN, ArgIds::None);
+      Tensor r = opt_row.value().contiguous();
+      if (has_value) TORCH_CHECK(value.dim() == 1 && value.size(0) == s.E, "Input mismatch");
+      out = s.out;
+      records = torch::empty({(int64_t)(tsamd_spmm_minmax_records_bytes(s.B, s.K, s.E) / 4)},
+                             s.rowptr.options().dtype(at::kInt));
+      Tensor ws = workspace(tsamd_spmm_minmax_records_workspace_bytes(s.dt, s.red, s.B, s.M, s.N, s.K, s.E), s.mat);
+      check_status(tsamd_spmm_minmax_records(s.dt, s.red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(),
+                                             out.data_ptr(), r.data_ptr<int64_t>(),
+                                             reinterpret_cast<uint32_t *>(records.data_ptr<int32_t>()), s.B, s.M, s.N, s.K,
+                                             s.E, ws.data_ptr(), (size_t)ws.numel(), current_stream(s.mat)),
                    "tsamd_spmm_minmax_records");
       arg_out = records;  // (what this mode returns in the ids' place: the caller asked not to see them)
     } else {
@@ -568,6 +534,10 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
     return {out, arg_out};
   }
 
+  // Which C-ABI entry a backward calls.  Only Scatter uses atomics (its grad_mat depends on their order); the three
+  // pulls are deterministic.
+  enum class Route { Records, PullIds32, PullIds64, Scatter };
+
   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
     const bool has_value = ctx->saved_data["has_value"].toBool();
     const bool has_csc = ctx->saved_data["has_csc"].toBool();
@@ -578,71 +548,74 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
     const bool want_value = has_value && needs_grad(value);
     const bool want_mat = needs_grad(mat);
     Tensor grad_value, grad_mat;
-    if (want_value || want_mat) {
-      c10::hip::HIPGuard guard(mat.get_device());
-      const int64_t N = mat.size(-2), K = mat.size(-1), M = grad_out.size(-2), E = col.numel();
-      const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
-      if (want_value) grad_value = torch::empty({E}, mat.options().requires_grad(false));
-      if (want_mat) grad_mat = torch::empty_like(mat, mat.options().requires_grad(false));
-      const int dt = dtype_code(mat);
-      int st = TSAMD_ERR_UNSUPPORTED;
-      // The pull is deterministic and faster for grad_mat alone (configs[2]: 1.36 vs 2.47 ms).  With grad_value as
-      // well it pays a masked SDDMM where the scatter kernel gets the value gradient fused: WHICH of the two wins
-      // depends on the row size, and the front-end decides that BEFORE the forward -- it hands the CSC arrays over
-      // exactly when it wants the pull (pytorch_sparse_amd/tensor.py: storage_spmm; until round 5 this line asked
-      // for deterministic algorithms again and sent the with-values case down the scatter route although the
-      // front-end had built the CSC arrays for it).
-      const bool pull = has_csc && want_mat;
-      if (ctx->saved_data["records"].toBool()) {  // the forward left the pull's winner records (see forward)
-        Tensor colptr = s[5].contiguous(), csr2csc = s[6].contiguous(), row = s[7].contiguous();
-        if (!want_mat) grad_mat = torch::empty_like(mat, mat.options().requires_grad(false));  // (the entry needs it)
-        Tensor ws = workspace(tsamd_spmm_minmax_bw_csc_records_workspace_bytes(dt, B, M, N, K, E), mat);
-        check_status(tsamd_spmm_minmax_bw_csc_records(
-                         dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), has_value ? 1 : 0, mat.data_ptr(),
-                         grad_out.data_ptr(), reinterpret_cast<const uint32_t *>(arg_out.data_ptr<int32_t>()),
-                         colptr.data_ptr<int64_t>(), csr2csc.data_ptr<int64_t>(), row.data_ptr<int64_t>(),
-                         want_value ? grad_value.data_ptr() : nullptr, grad_mat.data_ptr(), B, M, N, K, E, ws.data_ptr(),
-                         (size_t)ws.numel(), current_stream(mat)),
+    if (!want_value && !want_mat)
+      return {Tensor(), Tensor(), grad_value, grad_mat, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    c10::hip::HIPGuard guard(mat.get_device());
+    const int64_t N = mat.size(-2), K = mat.size(-1), M = grad_out.size(-2), E = col.numel();
+    const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
+    const int dt = dtype_code(mat);
+    // The pull is deterministic and faster for grad_mat alone (configs[2]: 1.36 vs 2.47 ms).  With grad_value as
+    // well it pays a masked SDDMM where the scatter kernel gets the value gradient fused: WHICH of the two wins
+    // depends on the row size, and the front-end decides that BEFORE the forward -- it hands the CSC arrays over
+    // exactly when it wants the pull (pytorch_sparse_amd/tensor.py: storage_spmm).
+    // The route, from what the C-ABI decides on (csrc/spmm_bw.hip: plan_minmax_csc, table in
+    // docs/design/spmm_backward.md): the pull kernels hold 32-bit ids; int32 winners give grad_value only as the masked
+    // SDDMM (16-byte packets), otherwise they are widened for the row-parallel kernel, which reads int64 ids.
+    const bool records = ctx->saved_data["records"].toBool();  // the forward left the pull's winner records (see forward)
+    Tensor colptr, csr2csc, row;
+    if (records || (has_csc && want_mat)) {
+      colptr = s[5].contiguous();
+      csr2csc = s[6].contiguous();
+      row = s[7].contiguous();
+    }
+    const bool narrow = arg_out.scalar_type() == at::kInt;
+    const bool fits32 = N < ((int64_t)1 << 32) && M < ((int64_t)1 << 32) && E < ((int64_t)1 << 32) && K < ((int64_t)1 << 31);
+    const bool packets16 = row.defined() && row.data_ptr() != nullptr && (K * (int64_t)mat.element_size()) % 16 == 0 &&
+                           (uintptr_t)mat.data_ptr() % 16 == 0 && (uintptr_t)grad_out.data_ptr() % 16 == 0;
+    Route route = Route::Scatter;  // no CSC arrays (the bare op), or sizes beyond the pull kernels' 32-bit ids
+    if (records)
+      route = Route::Records;
+    else if (has_csc && want_mat && fits32)
+      route = narrow && E < ((int64_t)1 << 31) && (!want_value || packets16) ? Route::PullIds32 : Route::PullIds64;
+
+    if (want_value) grad_value = torch::empty({E}, mat.options().requires_grad(false));
+    if (want_mat || route == Route::Records)  // (the records entry always writes grad_mat)
+      grad_mat = torch::empty_like(mat, mat.options().requires_grad(false));
+    if (narrow && (route == Route::PullIds64 || route == Route::Scatter)) arg_out = arg_out.to(at::kLong);
+    Tensor ws = workspace(route == Route::Records   ? tsamd_spmm_minmax_bw_csc_records_workspace_bytes(dt, B, M, N, K, E)
+                          : route == Route::Scatter ? tsamd_spmm_minmax_bw_workspace_bytes(dt, B, N, K, E)
+                                                    : tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, B, M, N, K, E),
+                          mat);
+    auto ids = [](const Tensor &t) { return t.defined() ? t.data_ptr<int64_t>() : nullptr; };
+    const int64_t *rp = ids(rowptr), *cp = ids(col), *ccp = ids(colptr), *perm = ids(csr2csc), *rw = ids(row);
+    const void *vp = has_value ? value.data_ptr() : nullptr, *x = mat.data_ptr(), *g = grad_out.data_ptr();
+    void *gv = want_value ? grad_value.data_ptr() : nullptr, *gm = grad_mat.defined() ? grad_mat.data_ptr() : nullptr;
+    void *w = ws.data_ptr(), *stream = current_stream(mat);
+    const size_t wb = (size_t)ws.numel();
+    // an UNSUPPORTED from the chosen entry means the rule above and plan_minmax_csc disagree: an error like any other
+    switch (route) {
+      case Route::Records:
+        check_status(tsamd_spmm_minmax_bw_csc_records(dt, rp, cp, has_value ? 1 : 0, x, g,
+                                                      reinterpret_cast<const uint32_t *>(arg_out.data_ptr<int32_t>()), ccp,
+                                                      perm, rw, gv, gm, B, M, N, K, E, w, wb, stream),
                      "tsamd_spmm_minmax_bw_csc_records");
         if (!want_mat) grad_mat = Tensor();
-        return {Tensor(), Tensor(), grad_value, grad_mat, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-      }
-      if (pull && arg_out.scalar_type() == at::kInt) {  // the winners were kept as 32-bit ids (forward, arg32)
-        Tensor colptr = s[5].contiguous(), csr2csc = s[6].contiguous(), row = s[7].contiguous();
-        Tensor ws = workspace(tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, B, M, N, K, E), mat);
-        st = tsamd_spmm_minmax_bw_csc_arg32(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                            has_value ? value.data_ptr() : nullptr, mat.data_ptr(),
-                                            grad_out.data_ptr(), arg_out.data_ptr<int32_t>(),
-                                            colptr.data_ptr<int64_t>(), csr2csc.data_ptr<int64_t>(),
-                                            row.data_ptr<int64_t>(), want_value ? grad_value.data_ptr() : nullptr,
-                                            grad_mat.data_ptr(), B, M, N, K, E, ws.data_ptr(), (size_t)ws.numel(),
-                                            current_stream(mat));
-        if (st != TSAMD_ERR_UNSUPPORTED) check_status(st, "tsamd_spmm_minmax_bw_csc_arg32");
-      }
-      if (arg_out.scalar_type() == at::kInt && st == TSAMD_ERR_UNSUPPORTED) arg_out = arg_out.to(at::kLong);
-      if (pull && st == TSAMD_ERR_UNSUPPORTED) {
-        Tensor colptr = s[5].contiguous(), csr2csc = s[6].contiguous(), row = s[7].contiguous();
-        Tensor ws = workspace(tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, B, M, N, K, E), mat);
-        st = tsamd_spmm_minmax_bw_csc(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                      has_value ? value.data_ptr() : nullptr, mat.data_ptr(),
-                                      grad_out.data_ptr(), arg_out.data_ptr<int64_t>(),
-                                      colptr.data_ptr<int64_t>(), csr2csc.data_ptr<int64_t>(),
-                                      row.data_ptr<int64_t>(), want_value ? grad_value.data_ptr() : nullptr,
-                                      grad_mat.data_ptr(), B, M, N, K, E, ws.data_ptr(), (size_t)ws.numel(),
-                                      current_stream(mat));
-        if (st != TSAMD_ERR_UNSUPPORTED) check_status(st, "tsamd_spmm_minmax_bw_csc");
-      }
-      if (st == TSAMD_ERR_UNSUPPORTED) {  // no CSC arrays (bare op), or sizes beyond the pull kernel's 32-bit ids
-        Tensor ws = workspace(tsamd_spmm_minmax_bw_workspace_bytes(dt, B, N, K, E), mat);
-        check_status(
-            tsamd_spmm_minmax_bw(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                 has_value ? value.data_ptr() : nullptr,
-                                 mat.data_ptr(), grad_out.data_ptr(), arg_out.data_ptr<int64_t>(),
-                                 want_value ? grad_value.data_ptr() : nullptr,
-                                 want_mat ? grad_mat.data_ptr() : nullptr, B, M, N, K, E,
-                                 ws.data_ptr(), (size_t)ws.numel(), current_stream(mat)),
-            "tsamd_spmm_minmax_bw");
-      }
+        break;
+      case Route::PullIds32:
+        check_status(tsamd_spmm_minmax_bw_csc_arg32(dt, rp, cp, vp, x, g, arg_out.data_ptr<int32_t>(), ccp, perm, rw, gv, gm,
+                                                    B, M, N, K, E, w, wb, stream),
+                     "tsamd_spmm_minmax_bw_csc_arg32");
+        break;
+      case Route::PullIds64:
+        check_status(tsamd_spmm_minmax_bw_csc(dt, rp, cp, vp, x, g, arg_out.data_ptr<int64_t>(), ccp, perm, rw, gv, gm, B, M,
+                                              N, K, E, w, wb, stream),
+                     "tsamd_spmm_minmax_bw_csc");
+        break;
+      case Route::Scatter:
+        check_status(tsamd_spmm_minmax_bw(dt, rp, cp, vp, x, g, arg_out.data_ptr<int64_t>(), gv, gm, B, M, N, K, E, w, wb,
+                                          stream),
+                     "tsamd_spmm_minmax_bw");
+        break;
     }
     return {Tensor(), Tensor(), grad_value, grad_mat, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
@@ -668,7 +641,7 @@ Tensor relabel_ids(OptTensor ids, int64_t n, Tensor like) {
 }
 
 std::tuple<Tensor, OptTensor> spmm_relabelled_fw(const Tensor &rowptr, const Tensor &col_h,
-                                                 const OptTensor &opt_value, Tensor mat_h,
+                                                 const OptTensor &opt_value, const Tensor &mat_h,
                                                  const std::string &reduce) {
   check_index(rowptr, "rowptr");
   check_index(col_h, "col_h");
@@ -681,29 +654,13 @@ std::tuple<Tensor, OptTensor> spmm_relabelled_fw(const Tensor &rowptr, const Ten
                 mat_h.scalar_type(), " but found ", opt_value.value().scalar_type());
   }
   c10::hip::HIPGuard guard(rowptr.get_device());
-  mat_h = mat_h.contiguous();
-  Tensor rp = rowptr.contiguous(), c = col_h.contiguous();
-  OptTensor value = opt_value.has_value() ? OptTensor(opt_value.value().contiguous()) : std::nullopt;
-  auto sizes = mat_h.sizes().vec();
-  const int64_t M = rp.numel() - 1, E = c.numel();
-  const int64_t N = mat_h.size(-2), K = mat_h.size(-1);
-  const int64_t B = (N * K) > 0 ? mat_h.numel() / (N * K) : 1;
-  sizes[mat_h.dim() - 2] = M;
-  Tensor out = torch::empty(sizes, mat_h.options().requires_grad(false));
-  const int red = reduce_code(reduce);
-  OptTensor arg_out = std::nullopt;
-  int64_t *arg_ptr = nullptr;
-  if (red == TSAMD_MIN || red == TSAMD_MAX) {
-    arg_out = torch::empty(sizes, rp.options());
-    arg_ptr = arg_out.value().data_ptr<int64_t>();
-  }
-  const int dt = dtype_code(mat_h);
-  Tensor ws = workspace(tsamd_spmm_relabelled_workspace_bytes(dt, red, B, M, N, K, E), mat_h);
-  check_status(tsamd_spmm_relabelled(dt, red, rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(),
-                                     ptr_or_null(value), mat_h.data_ptr(), out.data_ptr(), arg_ptr, B, M,
-                                     N, K, E, ws.data_ptr(), (size_t)ws.numel(), current_stream(mat_h)),
+  const SpmmShape s = spmm_shape(rowptr, col_h, opt_value, mat_h, reduce_code(reduce), ArgIds::Wide);
+  Tensor ws = workspace(tsamd_spmm_relabelled_workspace_bytes(s.dt, s.red, s.B, s.M, s.N, s.K, s.E), s.mat);
+  check_status(tsamd_spmm_relabelled(s.dt, s.red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
+                                     s.arg64(), s.B, s.M, s.N, s.K, s.E, ws.data_ptr(), (size_t)ws.numel(),
+                                     current_stream(s.mat)),
                "tsamd_spmm_relabelled");
-  return std::make_tuple(out, arg_out);
+  return std::make_tuple(s.out, s.arg_out);
 }
 
 // sum / mean in the relabelled layout with both gradients; the backward works in the same layout
@@ -799,46 +756,33 @@ Tensor gather_rows(Tensor src, Tensor idx) {
 }
 
 // ---- registered entry points (reference signatures) -----------------------------------------
+// owned: the index arrays belong to a SparseStorage (SparseTensor.matmul): the backward may keep row[csr2csc] (and
+// value[csr2csc] of non-trainable weights) across calls -- see PatternCache
+Tensor spmm_add(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value, OptTensor opt_rowcount,
+                OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat, bool mean, bool owned) {
+  Tensor value = opt_value.value_or(col);
+  return SpmmAddFunction::apply(opt_row, rowptr, col, value, opt_rowcount, opt_colptr, opt_csr2csc, mat,
+                                opt_value.has_value(), mean, owned)[0];
+}
+
 Tensor spmm_sum(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value,
                 OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat) {
-  Tensor value = opt_value.value_or(col);
-  return SpmmAddFunction::apply(opt_row, rowptr, col, value, std::nullopt, opt_colptr, opt_csr2csc,
-                                mat, opt_value.has_value(), false, false)[0];
+  return spmm_add(opt_row, rowptr, col, opt_value, std::nullopt, opt_colptr, opt_csr2csc, mat, false, false);
 }
 
 Tensor spmm_mean(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value,
                  OptTensor opt_rowcount, OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat) {
-  Tensor value = opt_value.value_or(col);
-  return SpmmAddFunction::apply(opt_row, rowptr, col, value, opt_rowcount, opt_colptr, opt_csr2csc,
-                                mat, opt_value.has_value(), true, false)[0];
+  return spmm_add(opt_row, rowptr, col, opt_value, opt_rowcount, opt_colptr, opt_csr2csc, mat, true, false);
 }
 
-// The same two ops for callers whose index arrays belong to a SparseStorage (SparseTensor.matmul): the backward
-// may keep row[csr2csc] (and value[csr2csc] of non-trainable weights) across calls -- see PatternCache.
 Tensor spmm_sum_owned(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value,
                       OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat) {
-  Tensor value = opt_value.value_or(col);
-  return SpmmAddFunction::apply(opt_row, rowptr, col, value, std::nullopt, opt_colptr, opt_csr2csc,
-                                mat, opt_value.has_value(), false, true)[0];
+  return spmm_add(opt_row, rowptr, col, opt_value, std::nullopt, opt_colptr, opt_csr2csc, mat, false, true);
 }
 
 Tensor spmm_mean_owned(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value,
                        OptTensor opt_rowcount, OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat) {
-  Tensor value = opt_value.value_or(col);
-  return SpmmAddFunction::apply(opt_row, rowptr, col, value, opt_rowcount, opt_colptr, opt_csr2csc,
-                                mat, opt_value.has_value(), true, true)[0];
-}
-
-std::tuple<Tensor, Tensor> spmm_min(Tensor rowptr, Tensor col, OptTensor opt_value, Tensor mat) {
-  auto r = SpmmMinMaxFunction::apply(rowptr, col, opt_value.value_or(col), mat,
-                                     opt_value.has_value(), false, std::nullopt, std::nullopt, std::nullopt, false);
-  return std::make_tuple(r[0], r[1]);
-}
-
-std::tuple<Tensor, Tensor> spmm_max(Tensor rowptr, Tensor col, OptTensor opt_value, Tensor mat) {
-  auto r = SpmmMinMaxFunction::apply(rowptr, col, opt_value.value_or(col), mat,
-                                     opt_value.has_value(), true, std::nullopt, std::nullopt, std::nullopt, false);
-  return std::make_tuple(r[0], r[1]);
+  return spmm_add(opt_row, rowptr, col, opt_value, opt_rowcount, opt_colptr, opt_csr2csc, mat, true, true);
 }
 
 // tsamd::spmm_minmax(Tensor rowptr, Tensor col, Tensor? value, Tensor? colptr, Tensor? csr2csc, Tensor? row,
@@ -851,6 +795,14 @@ std::tuple<Tensor, Tensor> spmm_minmax(Tensor rowptr, Tensor col, OptTensor opt_
   auto r = SpmmMinMaxFunction::apply(rowptr, col, opt_value.value_or(col), mat, opt_value.has_value(), is_max,
                                      opt_colptr, opt_csr2csc, opt_row, arg32);
   return std::make_tuple(r[0], r[1]);
+}
+
+std::tuple<Tensor, Tensor> spmm_min(Tensor rowptr, Tensor col, OptTensor opt_value, Tensor mat) {
+  return spmm_minmax(rowptr, col, opt_value, std::nullopt, std::nullopt, std::nullopt, mat, false, false);
+}
+
+std::tuple<Tensor, Tensor> spmm_max(Tensor rowptr, Tensor col, OptTensor opt_value, Tensor mat) {
+  return spmm_minmax(rowptr, col, opt_value, std::nullopt, std::nullopt, std::nullopt, mat, true, false);
 }
 
 Tensor ind2ptr(Tensor ind, int64_t M) {

@@ -690,15 +690,22 @@ int ilog2_ceil(uint32_t x) {
   return l;
 }
 
+// `slots` lanes (rounded up to a power of two, 64 at the most) work side by side on one item: log2 of the number
+// of such groups in a wave
+int lg_groups(uint32_t slots) {
+  const uint32_t lpr = slots >= 64 ? 64u : (1u << ilog2_ceil(slots));
+  return 6 - ilog2_ceil(lpr);
+}
+
+// blocks of the entry-parallel kernels: a wave owns 64 consecutive entries
+unsigned int entry_blocks(int64_t E) { return (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock); }
+
 template <typename T, int VEC>
 int launch_value_bw(const int64_t *row, const int64_t *rowptr, const int64_t *col, const T *mat,
                     const T *grad, T *out, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                     bool mean, hipStream_t stream) {
-  const uint32_t slots = (uint32_t)((K + VEC - 1) / VEC);
-  const uint32_t lpr = slots >= 64 ? 64u : (1u << ilog2_ceil(slots));
-  const int lgG = 6 - ilog2_ceil(lpr);
-  const unsigned int blocks = (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock);
-  hipLaunchKernelGGL((spmm_value_bw_kernel<T, VEC>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0,
+  const int lgG = lg_groups((uint32_t)((K + VEC - 1) / VEC));
+  hipLaunchKernelGGL((spmm_value_bw_kernel<T, VEC>), dim3(entry_blocks(E)), dim3(kWavesPerBlock * kWave), 0,
                      stream, row, rowptr, col, mat, grad, out, B, M, N, (uint32_t)K, E, lgG, mean);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
@@ -711,9 +718,8 @@ int launch_value_bw_masked(const int64_t *row, const int64_t *rowptr, const int6
                            int64_t M, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
   constexpr int VEC = 16 / (int)sizeof(T);
   const uint32_t slots = (uint32_t)(K / VEC);
-  const uint32_t lpr = slots >= 64 ? 64u : (1u << ilog2_ceil(slots));
-  const int lgG = 6 - ilog2_ceil(lpr);
-  const unsigned int blocks = (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock);
+  const int lgG = lg_groups(slots);
+  const unsigned int blocks = entry_blocks(E);
   if (slots <= 64u && K % VEC == 0 && (uint64_t)kWave * rec_stride < (1ull << 32)) {
     hipLaunchKernelGGL((spmm_value_bw_masked_kernel<T>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream, row,
                        rowptr, col, mat, grad, out, B, M, N, (uint32_t)K, E, lgG, rec, rec_stride);
@@ -726,16 +732,48 @@ int launch_value_bw_masked(const int64_t *row, const int64_t *rowptr, const int6
   return TSAMD_OK;
 }
 
-template <typename T>
-int dispatch_value_bw(bool vec_ok, const int64_t *row, const int64_t *rowptr, const int64_t *col,
-                      const void *mat, const void *grad, void *out, int64_t B, int64_t M,
-                      int64_t N, int64_t K, int64_t E, bool mean, hipStream_t stream) {
-  constexpr int kVec = 16 / (int)sizeof(T);
-  const T *x = reinterpret_cast<const T *>(mat);
-  const T *g = reinterpret_cast<const T *>(grad);
-  T *o = reinterpret_cast<T *>(out);
-  if (vec_ok) return launch_value_bw<T, kVec>(row, rowptr, col, x, g, o, B, M, N, K, E, mean, stream);
-  return launch_value_bw<T, 1>(row, rowptr, col, x, g, o, B, M, N, K, E, mean, stream);
+// f(T{}) for the floating type behind `dtype`; integer dtypes have no gradient
+template <typename F>
+int dispatch_float(int dtype, F &&f) {
+  switch (dtype) {
+    case TSAMD_F32: return f(float{});
+    case TSAMD_F64: return f(double{});
+    case TSAMD_F16: return f(f16_t{});
+    case TSAMD_BF16: return f(bf16_t{});
+    default: return TSAMD_ERR_UNSUPPORTED;
+  }
+}
+
+// What the pull backward is given in place of arg_out: the winners as ids of either width, or as the records the forward
+// left (spmm_internal.h).  An accessor answers NULL for every kind but its own, so no route can read one as another.
+struct Winners {
+  enum Kind { Ids64, Ids32, Records } kind;
+  const void *ptr;
+  const int64_t *ids64() const { return kind == Ids64 ? static_cast<const int64_t *>(ptr) : nullptr; }
+  const int32_t *ids32() const { return kind == Ids32 ? static_cast<const int32_t *>(ptr) : nullptr; }
+  const uint32_t *records() const { return kind == Records ? static_cast<const uint32_t *>(ptr) : nullptr; }
+};
+
+// The one launch of the record writer.
+template <typename T, typename ARG>
+int launch_winrec(const int64_t *row, const void *value, const ARG *ids, uint32_t *rec, int64_t B, int64_t M,
+                  int64_t K, int64_t E, hipStream_t stream) {
+  const uint32_t W = (uint32_t)ceil_div(K, 32), S = win_record_stride(K);
+  hipLaunchKernelGGL((minmax_winrec_kernel<T, ARG>), dim3(entry_blocks(E)), dim3(kWavesPerBlock * kWave), 0, stream, row,
+                     static_cast<const T *>(value), ids, rec, B, M, (uint32_t)K, E, W, S);
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+// records of `ids` (Ids64 or Ids32) -> rec; a non-empty problem with non-null arrays (the callers check)
+int write_winrec(int dtype, const int64_t *row, const void *value, const Winners &ids, uint32_t *rec, int64_t B,
+                 int64_t M, int64_t K, int64_t E, hipStream_t stream) {
+  return dispatch_float(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (ids.kind == Winners::Ids32) return launch_winrec<T>(row, value, ids.ids32(), rec, B, M, K, E, stream);
+    if (ids.kind == Winners::Ids64) return launch_winrec<T>(row, value, ids.ids64(), rec, B, M, K, E, stream);
+    return (int)TSAMD_ERR_INVALID;
+  });
 }
 
 template <typename T, typename TM>
@@ -743,8 +781,7 @@ int launch_minmax_bw(const int64_t *rowptr, const int64_t *col, const void *valu
                      const void *grad_out, const int64_t *arg_out, void *gval, TM *gmat, int64_t B,
                      int64_t M, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
   if (B * M * K == 0) return TSAMD_OK;
-  const uint32_t lpr = K >= 64 ? 64u : (1u << ilog2_ceil((uint32_t)K));
-  const int lgG = 6 - ilog2_ceil(lpr);
+  const int lgG = lg_groups((uint32_t)K);
   const int64_t rows_per_wave = (int64_t)kBwRows << lgG;
   const unsigned int blocks = (unsigned int)ceil_div(ceil_div(M, rows_per_wave), kWavesPerBlock);
   const T *v = reinterpret_cast<const T *>(value), *x = reinterpret_cast<const T *>(mat),
@@ -793,13 +830,12 @@ extern "C" int tsamd_spmm_value_bw(int dtype, int reduce, const int64_t *row,
   const bool vec_ok = K > 0 && (K * es) % 16 == 0 && ((uintptr_t)mat % 16 == 0) &&
                       ((uintptr_t)grad % 16 == 0);
   const bool mean = reduce == TSAMD_MEAN;
-  return TSAMD_DISPATCH_DTYPE(dtype, [&]() -> int {
-    if constexpr (std::is_integral<scalar_t>::value) {
-      return (int)TSAMD_ERR_UNSUPPORTED;
-    } else {
-      return dispatch_value_bw<scalar_t>(vec_ok, row, rowptr, col, mat, grad, out, B, M, N, K, E,
-                                         mean, stream);
-    }
+  return dispatch_float(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    const T *x = static_cast<const T *>(mat), *g = static_cast<const T *>(grad);
+    T *o = static_cast<T *>(out);
+    if (vec_ok) return launch_value_bw<T, 16 / (int)sizeof(T)>(row, rowptr, col, x, g, o, B, M, N, K, E, mean, stream);
+    return launch_value_bw<T, 1>(row, rowptr, col, x, g, o, B, M, N, K, E, mean, stream);
   });
 }
 
@@ -814,22 +850,6 @@ extern "C" size_t tsamd_spmm_minmax_bw_workspace_bytes(int dtype, int64_t B, int
     return align_up(sizeof(float) * (size_t)(B * N * K), 256);
   return 0;
 }
-
-namespace {
-template <typename T>
-int run_minmax_bw(const int64_t *rowptr, const int64_t *col, const void *value, const void *mat,
-                  const void *grad_out, const int64_t *arg_out, void *grad_value, void *grad_mat,
-                  float *shadow_mat, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
-                  hipStream_t stream) {
-  if constexpr (Traits<T>::kNarrow) {
-    if (shadow_mat != nullptr || grad_mat == nullptr)
-      return launch_minmax_bw<T, float>(rowptr, col, value, mat, grad_out, arg_out, grad_value,
-                                        shadow_mat, B, M, N, K, E, stream);
-  }
-  return launch_minmax_bw<T, T>(rowptr, col, value, mat, grad_out, arg_out, grad_value,
-                                reinterpret_cast<T *>(grad_mat), B, M, N, K, E, stream);
-}
-}  // namespace
 
 extern "C" int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int64_t *col,
                                     const void *value, const void *mat, const void *grad_out,
@@ -862,13 +882,15 @@ extern "C" int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int6
     if (grad_value && E > 0) TSAMD_HIP_TRY(hipMemsetAsync(grad_value, 0, es * (size_t)E, stream));
     return TSAMD_OK;
   }
-  int st = TSAMD_DISPATCH_DTYPE(dtype, [&]() -> int {
-    if constexpr (std::is_integral<scalar_t>::value) {
-      return (int)TSAMD_ERR_UNSUPPORTED;
-    } else {
-      return run_minmax_bw<scalar_t>(rowptr, col, value, mat, grad_out, arg_out, grad_value, grad_mat,
-                                     shadow_mat, B, M, N, K, E, stream);
+  int st = dispatch_float(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if constexpr (Traits<T>::kNarrow) {
+      if (shadow_mat != nullptr || grad_mat == nullptr)
+        return launch_minmax_bw<T, float>(rowptr, col, value, mat, grad_out, arg_out, grad_value, shadow_mat, B, M, N, K, E,
+                                          stream);
     }
+    return launch_minmax_bw<T, T>(rowptr, col, value, mat, grad_out, arg_out, grad_value, static_cast<T *>(grad_mat), B, M,
+                                  N, K, E, stream);
   });
   if (st != TSAMD_OK) return st;
   if (shadow_mat) {
@@ -880,135 +902,180 @@ extern "C" int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int6
 
 // ---------------------------------------------------------------------------
 // min/max backward, pull formulation over the transposed pattern (see include/tsamd.h)
+//   grad_mat   = masked (A^T) * grad_out over the winner records: rows of A^T = columns of A, entries through csr2csc.
+//                Compacted winner lists per entry were measured slower (instruction-bound: 2.08 vs 1.78 ms at
+//                configs[2], profiles/r04_minmax_bw_routes.md).
+//   grad_value = a masked SDDMM over the same records where 16-byte packets allow it; else the row-parallel kernel.
+// The three entries differ in the winners they are given.  plan_minmax_csc() decides what a call answers and does from
+// its arguments alone, run_minmax_csc() carries that out; the table is in docs/design/spmm_backward.md.
 // ---------------------------------------------------------------------------
-static size_t winrec_bytes(int64_t B, int64_t K, int64_t E) {
-  return align_up(sizeof(uint32_t) * (size_t)(B * E) * win_record_stride(K), 256);
-}
+namespace tsamd {
+namespace {
 
-// grad_mat route of the pull: winner bit masks + the masked merge-path SpMM.  Compacted winner lists per entry were
-// measured slower (instruction-bound: 2.08 vs 1.78 ms at configs[2], profiles/r04_minmax_bw_routes.md).
-extern "C" size_t tsamd_spmm_minmax_bw_csc_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N,
-                                                           int64_t K, int64_t E) {
+struct MinMaxCscCall {
+  int dtype;
+  const int64_t *rowptr, *col;
+  const void *value;  // ids only (the record writer reads it); records carry the values
+  bool has_value;
+  const void *mat, *grad_out;
+  Winners winners;
+  const int64_t *colptr, *csr2csc, *row;
+  void *grad_value, *grad_mat;
+  int64_t B, M, N, K, E;
+  void *workspace;
+  size_t workspace_bytes;
+  void *stream;
+};
+
+// the workspace of a pull: [records, unless the caller brought them | masked sum on the transposed matrix (N rows)];
+// -> its size, *sum_off = where the second part starts
+size_t minmax_csc_workspace(Winners::Kind kind, int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                            size_t *sum_off = nullptr) {
   if (dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
-  // the masked sum runs on the transposed matrix: N rows, M columns
-  return winrec_bytes(B, K, E) + spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
+  const size_t rec = kind == Winners::Records ? 0 : align_up(sizeof(uint32_t) * (size_t)(B * E) * win_record_stride(K), 256);
+  if (sum_off != nullptr) *sum_off = rec;
+  return rec + spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
 }
 
-// arg32: arg_any holds int32 ids (tsamd_spmm_minmax_arg32); only the record route reads them in that width
-// records_in: the winner records are there already (tsamd_spmm_minmax_records wrote them in the forward): no ids, the
-// whole workspace belongs to the masked sum; `value` is then only asked for presence
-static int minmax_bw_csc_impl(int dtype, const int64_t *rowptr, const int64_t *col, const void *value,
-                              const void *mat, const void *grad_out, const void *arg_any, bool arg32,
-                              const int64_t *colptr, const int64_t *csr2csc, const int64_t *row, void *grad_value,
-                              void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, void *workspace,
-                              size_t workspace_bytes, void *stream_, const uint32_t *records_in = nullptr) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (records_in != nullptr) {
-    arg_any = records_in;  // (never dereferenced as ids: every id-reading route below returns UNSUPPORTED first)
-    arg32 = true;
+struct MinMaxCscPlan {
+  int status = TSAMD_OK;  // anything else is the call's answer and nothing runs
+  enum Value { NoValue, ZeroValue, MaskedSddmm, RowParallel } value = NoValue;  // how grad_value is made
+  enum Mat { NoMat, ZeroMat, Pull } mat = NoMat;                                // how grad_mat is made
+  bool write_records = false;         // Pull: the records are written first, from ids of the winners' width
+  size_t rec_off = 0, sum_off = 0;    // Pull: where the written records and the masked sum's scratch start in the workspace
+};
+
+// No HIP call in here.  The ORDER of the checks is part of the C-ABI (tests/test_cabi_minmax_bw.py pins it).
+MinMaxCscPlan plan_minmax_csc(const MinMaxCscCall &c) {
+  MinMaxCscPlan p;
+  auto answer = [&p](int status) { return p.status = status, p; };
+  const Winners::Kind kind = c.winners.kind;
+  const bool want_value = c.grad_value != nullptr, want_mat = c.grad_mat != nullptr;
+  const int64_t B = c.B, M = c.M, N = c.N, K = c.K, E = c.E, total = B * M * K;
+  if (kind == Winners::Records) {
+    if (!want_mat) return answer(TSAMD_ERR_UNSUPPORTED);  // (grad_value alone reads ids: tsamd_spmm_minmax_bw)
+    // an empty pattern needs no records (though with no `mat` either the call is INVALID before its dtype is looked at)
+    if (total > 0 && !c.winners.ptr && (E > 0 || !c.mat)) return answer(TSAMD_ERR_INVALID);
   }
-  const int64_t *arg_out = arg32 ? nullptr : reinterpret_cast<const int64_t *>(arg_any);
-  if (arg32 && arg_any == nullptr && B * M * K > 0) return TSAMD_ERR_INVALID;
-  if (arg32) arg_out = reinterpret_cast<const int64_t *>(arg_any);  // (never dereferenced at this width below)
-  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16)
-    return TSAMD_ERR_UNSUPPORTED;
+  if (kind != Winners::Ids64 && E >= (int64_t)1 << 31) return answer(TSAMD_ERR_UNSUPPORTED);
+  if (kind == Winners::Ids32 && total > 0 && !c.winners.ptr) return answer(TSAMD_ERR_INVALID);
+  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return answer(TSAMD_ERR_INVALID);
+  if (c.dtype != TSAMD_F32 && c.dtype != TSAMD_F64 && c.dtype != TSAMD_F16 && c.dtype != TSAMD_BF16)
+    return answer(TSAMD_ERR_UNSUPPORTED);
   if (N >= (int64_t)1 << 32 || M >= (int64_t)1 << 32 || E >= (int64_t)1 << 32 || K >= (int64_t)1 << 31)
-    return TSAMD_ERR_UNSUPPORTED;
-  const int64_t total = B * M * K;
-  if (total > 0 && (!rowptr || !col || !mat || !grad_out || !arg_out)) return TSAMD_ERR_INVALID;
-  if (grad_mat && E > 0 && (!colptr || !csr2csc || !row)) return TSAMD_ERR_INVALID;
-  const size_t es = dtype_size(dtype);
-  // grad_value as a masked SDDMM over the records needs 16-byte packets; else the row-parallel LDS kernel
-  const bool sddmm_ok = grad_value && row && (K * (int64_t)es) % 16 == 0 && ((uintptr_t)mat % 16) == 0 &&
-                        ((uintptr_t)grad_out % 16) == 0;
-  if (grad_value && !(sddmm_ok && grad_mat)) {
-    if (arg32) return TSAMD_ERR_UNSUPPORTED;  // the row-parallel kernel reads int64 ids: the caller widens them
-    int st = tsamd_spmm_minmax_bw(dtype, rowptr, col, value, mat, grad_out, arg_out, grad_value, nullptr, B, M, N,
-                                  K, E, nullptr, 0, stream_);
+    return answer(TSAMD_ERR_UNSUPPORTED);
+  if (total > 0 && (!c.rowptr || !c.col || !c.mat || !c.grad_out || (kind != Winners::Records && !c.winners.ptr)))
+    return answer(TSAMD_ERR_INVALID);
+  if (want_mat && E > 0 && (!c.colptr || !c.csr2csc || !c.row)) return answer(TSAMD_ERR_INVALID);
+  // grad_value as a masked SDDMM over the records needs 16-byte packets, and the records: it only runs beside grad_mat
+  const bool sddmm = want_value && want_mat && c.row && (K * (int64_t)dtype_size(c.dtype)) % 16 == 0 &&
+                     ((uintptr_t)c.mat % 16) == 0 && ((uintptr_t)c.grad_out % 16) == 0;
+  if (want_value && !sddmm) {
+    if (kind != Winners::Ids64) return answer(TSAMD_ERR_UNSUPPORTED);  // the row-parallel kernel reads int64 ids: the caller widens them
+    if (E > 0 && !c.rowptr) return answer(TSAMD_ERR_INVALID);          // grad_value is laid out by rows
+    p.value = MinMaxCscPlan::RowParallel;
+  }
+  if (!want_mat || B * N * K == 0) return p;
+  if (total == 0 || E == 0) {
+    p.mat = MinMaxCscPlan::ZeroMat;
+    if (sddmm && E > 0) p.value = MinMaxCscPlan::ZeroValue;
+    return p;
+  }
+  const size_t need = minmax_csc_workspace(kind, c.dtype, B, M, N, K, E, &p.sum_off);
+  if (!c.workspace || c.workspace_bytes < need || (uintptr_t)c.workspace % 256 != 0) return answer(TSAMD_ERR_WORKSPACE);
+  p.mat = MinMaxCscPlan::Pull;
+  if (sddmm) p.value = MinMaxCscPlan::MaskedSddmm;
+  p.write_records = kind != Winners::Records;
+  return p;
+}
+
+int run_minmax_csc(const MinMaxCscCall &c, const MinMaxCscPlan &p) {
+  if (p.status != TSAMD_OK) return p.status;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
+  const size_t es = dtype_size(c.dtype);
+  if (p.value == MinMaxCscPlan::RowParallel) {
+    int st = tsamd_spmm_minmax_bw(c.dtype, c.rowptr, c.col, c.value, c.mat, c.grad_out, c.winners.ids64(), c.grad_value,
+                                  nullptr, c.B, c.M, c.N, c.K, c.E, nullptr, 0, c.stream);
     if (st != TSAMD_OK) return st;
   }
-  if (!grad_mat || B * N * K == 0) return TSAMD_OK;
-  if (total == 0 || E == 0) {
-    TSAMD_HIP_TRY(hipMemsetAsync(grad_mat, 0, es * (size_t)(B * N * K), stream));
-    if (grad_value && sddmm_ok && E > 0) TSAMD_HIP_TRY(hipMemsetAsync(grad_value, 0, es * (size_t)E, stream));
+  if (p.mat == MinMaxCscPlan::NoMat) return TSAMD_OK;
+  if (p.mat == MinMaxCscPlan::ZeroMat) {
+    TSAMD_HIP_TRY(hipMemsetAsync(c.grad_mat, 0, es * (size_t)(c.B * c.N * c.K), stream));
+    if (p.value == MinMaxCscPlan::ZeroValue) TSAMD_HIP_TRY(hipMemsetAsync(c.grad_value, 0, es * (size_t)c.E, stream));
     return TSAMD_OK;
   }
-  const size_t rec_b = records_in != nullptr ? 0 : winrec_bytes(B, K, E);
-  const size_t spmm_b = spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
-  if (!workspace || workspace_bytes < rec_b + spmm_b || (uintptr_t)workspace % 256 != 0)
-    return TSAMD_ERR_WORKSPACE;
-  uint32_t *rec = records_in != nullptr ? const_cast<uint32_t *>(records_in) : reinterpret_cast<uint32_t *>(workspace);
-  const uint32_t W = (uint32_t)ceil_div(K, 32), S = win_record_stride(K);
-  const unsigned int blocks = (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock);
-  int st = TSAMD_DISPATCH_DTYPE(dtype, [&]() -> int {
-    if constexpr (std::is_integral<scalar_t>::value) {
-      return (int)TSAMD_ERR_UNSUPPORTED;
-    } else {
-      if (records_in != nullptr) {
-      } else if (arg32)
-        hipLaunchKernelGGL((minmax_winrec_kernel<scalar_t, int32_t>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0,
-                           stream, row, reinterpret_cast<const scalar_t *>(value),
-                           reinterpret_cast<const int32_t *>(arg_any), rec, B, M, (uint32_t)K, E, W, S);
-      else
-        hipLaunchKernelGGL((minmax_winrec_kernel<scalar_t, int64_t>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0,
-                           stream, row, reinterpret_cast<const scalar_t *>(value), arg_out, rec, B, M, (uint32_t)K, E,
-                           W, S);
-      TSAMD_LAUNCH_CHECK();
-      if (grad_value && sddmm_ok)
-        return launch_value_bw_masked<scalar_t>(row, rowptr, col, reinterpret_cast<const scalar_t *>(mat),
-                                                reinterpret_cast<const scalar_t *>(grad_out),
-                                                reinterpret_cast<scalar_t *>(grad_value), rec, S, B, M, N, K, E, stream);
-      return (int)TSAMD_OK;
-    }
-  });
-  if (st != TSAMD_OK) return st;
-  // grad_mat = masked (A^T) * grad_out: rows of A^T = columns of A, entries through csr2csc
-  return spmm_masked_sum(dtype, colptr, value != nullptr, csr2csc, rec, grad_out, grad_mat, B, N, M, K, E,
-                         reinterpret_cast<char *>(workspace) + rec_b, workspace_bytes - rec_b, stream);
+  char *ws = reinterpret_cast<char *>(c.workspace);
+  const uint32_t *rec = c.winners.records();
+  if (p.write_records) {
+    uint32_t *written = reinterpret_cast<uint32_t *>(ws + p.rec_off);
+    int st = write_winrec(c.dtype, c.row, c.value, c.winners, written, c.B, c.M, c.K, c.E, stream);
+    if (st != TSAMD_OK) return st;
+    rec = written;
+  }
+  if (p.value == MinMaxCscPlan::MaskedSddmm) {
+    int st = dispatch_float(c.dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      return launch_value_bw_masked<T>(c.row, c.rowptr, c.col, static_cast<const T *>(c.mat),
+                                       static_cast<const T *>(c.grad_out), static_cast<T *>(c.grad_value), rec,
+                                       win_record_stride(c.K), c.B, c.M, c.N, c.K, c.E, stream);
+    });
+    if (st != TSAMD_OK) return st;
+  }
+  return spmm_masked_sum(c.dtype, c.colptr, c.has_value, c.csr2csc, rec, c.grad_out, c.grad_mat, c.B, c.N, c.M, c.K, c.E,
+                         ws + p.sum_off, c.workspace_bytes - p.sum_off, stream);
 }
 
-extern "C" int tsamd_spmm_minmax_bw_csc(int dtype, const int64_t *rowptr, const int64_t *col,
-                                        const void *value, const void *mat, const void *grad_out,
-                                        const int64_t *arg_out, const int64_t *colptr,
-                                        const int64_t *csr2csc, const int64_t *row, void *grad_value,
-                                        void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K,
-                                        int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
-  return minmax_bw_csc_impl(dtype, rowptr, col, value, mat, grad_out, arg_out, false, colptr, csr2csc, row,
-                            grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_);
-}
+}  // namespace
 
-extern "C" int tsamd_spmm_minmax_bw_csc_arg32(int dtype, const int64_t *rowptr, const int64_t *col,
-                                              const void *value, const void *mat, const void *grad_out,
-                                              const int32_t *arg_out32, const int64_t *colptr,
-                                              const int64_t *csr2csc, const int64_t *row, void *grad_value,
-                                              void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K,
-                                              int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
-  if (E >= (int64_t)1 << 31) return TSAMD_ERR_UNSUPPORTED;
-  return minmax_bw_csc_impl(dtype, rowptr, col, value, mat, grad_out, arg_out32, true, colptr, csr2csc, row,
-                            grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_);
-}
-
-// ---- the pull backward on records the forward left (tsamd_spmm_minmax_records, include/tsamd.h) ------------------
-namespace tsamd {
+// Winner records from int32 ids, for the forward that leaves records (csrc/spmm.hip)
 int minmax_winrec_from_ids(int dtype, const int64_t *row, const void *value, const int32_t *arg32, uint32_t *records,
                            int64_t B, int64_t M, int64_t K, int64_t E, hipStream_t stream) {
   if (E == 0 || B * M * K == 0) return TSAMD_OK;
   if (!row || !arg32 || !records) return TSAMD_ERR_INVALID;
-  const uint32_t W = (uint32_t)ceil_div(K, 32), S = win_record_stride(K);
-  const unsigned int blocks = (unsigned int)ceil_div(ceil_div(E, kWave), kWavesPerBlock);
-  return TSAMD_DISPATCH_DTYPE(dtype, [&]() -> int {
-    if constexpr (std::is_integral<scalar_t>::value) {
-      return (int)TSAMD_ERR_UNSUPPORTED;
-    } else {
-      hipLaunchKernelGGL((minmax_winrec_kernel<scalar_t, int32_t>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
-                         row, reinterpret_cast<const scalar_t *>(value), arg32, records, B, M, (uint32_t)K, E, W, S);
-      TSAMD_LAUNCH_CHECK();
-      return (int)TSAMD_OK;
-    }
-  });
+  return write_winrec(dtype, row, value, Winners{Winners::Ids32, arg32}, records, B, M, K, E, stream);
 }
 }  // namespace tsamd
+
+extern "C" size_t tsamd_spmm_minmax_bw_csc_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E) {
+  return minmax_csc_workspace(Winners::Ids64, dtype, B, M, N, K, E);  // (Ids32: the same)
+}
+
+extern "C" size_t tsamd_spmm_minmax_bw_csc_records_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K,
+                                                                   int64_t E) {
+  return minmax_csc_workspace(Winners::Records, dtype, B, M, N, K, E);
+}
+
+extern "C" int tsamd_spmm_minmax_bw_csc(int dtype, const int64_t *rowptr, const int64_t *col, const void *value,
+                                        const void *mat, const void *grad_out, const int64_t *arg_out,
+                                        const int64_t *colptr, const int64_t *csr2csc, const int64_t *row, void *grad_value,
+                                        void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                        void *workspace, size_t workspace_bytes, void *stream_) {
+  const MinMaxCscCall c{dtype, rowptr, col, value, value != nullptr, mat, grad_out, Winners{Winners::Ids64, arg_out},
+                        colptr, csr2csc, row, grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_};
+  return run_minmax_csc(c, plan_minmax_csc(c));
+}
+
+extern "C" int tsamd_spmm_minmax_bw_csc_arg32(int dtype, const int64_t *rowptr, const int64_t *col, const void *value,
+                                              const void *mat, const void *grad_out, const int32_t *arg_out32,
+                                              const int64_t *colptr, const int64_t *csr2csc, const int64_t *row,
+                                              void *grad_value, void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K,
+                                              int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
+  const MinMaxCscCall c{dtype, rowptr, col, value, value != nullptr, mat, grad_out, Winners{Winners::Ids32, arg_out32},
+                        colptr, csr2csc, row, grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_};
+  return run_minmax_csc(c, plan_minmax_csc(c));
+}
+
+// the pull backward on records the forward left (tsamd_spmm_minmax_records, include/tsamd.h)
+extern "C" int tsamd_spmm_minmax_bw_csc_records(int dtype, const int64_t *rowptr, const int64_t *col, int has_value,
+                                                const void *mat, const void *grad_out, const uint32_t *records,
+                                                const int64_t *colptr, const int64_t *csr2csc, const int64_t *row,
+                                                void *grad_value, void *grad_mat, int64_t B, int64_t M, int64_t N,
+                                                int64_t K, int64_t E, void *workspace, size_t workspace_bytes,
+                                                void *stream_) {
+  const MinMaxCscCall c{dtype, rowptr, col, nullptr, has_value != 0, mat, grad_out, Winners{Winners::Records, records},
+                        colptr, csr2csc, row, grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_};
+  return run_minmax_csc(c, plan_minmax_csc(c));
+}
 
 extern "C" int tsamd_spmm_minmax_winrec(int dtype, const int64_t *row, const void *value, const int32_t *arg_out32,
                                         uint32_t *records, int64_t B, int64_t M, int64_t K, int64_t E, void *stream_) {
@@ -1016,25 +1083,4 @@ extern "C" int tsamd_spmm_minmax_winrec(int dtype, const int64_t *row, const voi
   if (E >= (int64_t)1 << 31 || M >= (int64_t)1 << 32) return TSAMD_ERR_UNSUPPORTED;
   return tsamd::minmax_winrec_from_ids(dtype, row, value, arg_out32, records, B, M, K, E,
                                        reinterpret_cast<hipStream_t>(stream_));
-}
-
-extern "C" size_t tsamd_spmm_minmax_bw_csc_records_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K,
-                                                                   int64_t E) {
-  if (dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
-  return spmm_masked_sum_workspace_bytes(dtype, B, N, M, K, E);
-}
-
-extern "C" int tsamd_spmm_minmax_bw_csc_records(int dtype, const int64_t *rowptr, const int64_t *col, int has_value,
-                                                const void *mat, const void *grad_out, const uint32_t *records,
-                                                const int64_t *colptr, const int64_t *csr2csc, const int64_t *row,
-                                                void *grad_value, void *grad_mat, int64_t B, int64_t M, int64_t N,
-                                                int64_t K, int64_t E, void *workspace, size_t workspace_bytes,
-                                                void *stream_) {
-  if (!grad_mat) return TSAMD_ERR_UNSUPPORTED;  // (grad_value alone reads ids: tsamd_spmm_minmax_bw)
-  if (E > 0 && B * M * K > 0 && !records) return TSAMD_ERR_INVALID;
-  if (E >= (int64_t)1 << 31) return TSAMD_ERR_UNSUPPORTED;
-  // `value` is only tested for presence on this route (the records carry the values): any non-null pointer will do
-  return minmax_bw_csc_impl(dtype, rowptr, col, has_value ? mat : nullptr, mat, grad_out, records, true, colptr, csr2csc,
-                            row, grad_value, grad_mat, B, M, N, K, E, workspace, workspace_bytes, stream_,
-                            records ? records : reinterpret_cast<const uint32_t *>(mat));
 }

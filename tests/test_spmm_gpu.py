@@ -426,6 +426,27 @@ def test_masked_sddmm_non_winners_contribute_nothing(dev, dtype):
     assert not torch.isfinite(gv[1])  # entry 1 did win the Inf / NaN features
 
 
+def assert_within_scatter_bound(c, v, x, gout, arg, grad_mat, grad_value, tag):
+    """The min / max backward against the fp64 formulas, within the scatter kernel's bound: every contribution to an
+    element of grad_mat is rounded once and accumulated in any order (cnt of them, l1 their absolute sum).  c, v, x,
+    gout: CPU tensors of one matrix; arg: the winners [n, K]; grad_mat / grad_value: None when not asked for."""
+    dtype, K = x.dtype, x.size(-1)
+    egv, egm = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().numpy(), x.double().numpy(), gout.double().numpy(),
+                                 arg.cpu().numpy(), want_value=True)
+    _, l1 = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().abs().numpy(), x.double().numpy(),
+                              gout.double().abs().numpy(), arg.cpu().numpy(), want_value=False)
+    _, cnt = oc.spmm_minmax_bw(oc.F64, c.numpy(), None, x.double().numpy(), np.ones_like(gout.double().numpy()),
+                               arg.cpu().numpy(), want_value=False)
+    u = 2.0 ** -24 if dtype == torch.float32 else 2.0 ** -8
+    bound = (cnt + 2) * u * l1 * 1.01 + 1e-30
+    if grad_mat is not None:
+        err = np.abs(grad_mat.cpu().double().numpy() - egm)
+        assert (err <= bound).all(), (tag, float((err / bound).max()))
+    if grad_value is not None:
+        tol = 1e-5 if dtype == torch.float32 else 3e-2
+        assert np.allclose(grad_value.cpu().double().numpy(), egv, rtol=tol, atol=tol * max(1.0, float(np.abs(egv).max())))
+
+
 def test_minmax_backward_route_rule(dev):
     """Which backward SparseTensor.matmul(x, 'max') prepares (pytorch_sparse_amd/tensor.py: storage_spmm, table in
     profiles/r05_minmax_bw_route_rule.md): the pull needs the CSC arrays, so a storage that has them after the forward
@@ -454,19 +475,7 @@ def test_minmax_backward_route_rule(dev):
         finally:
             torch.use_deterministic_algorithms(False)
         arg = nat.spmm(rp.to(dev), c.to(dev), v.to(dev), x.to(dev), 'max')[1]
-        egv, egm = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().numpy(), x.double().numpy(), gout.double().numpy(),
-                                     arg.cpu().numpy(), want_value=True)
-        _, l1 = oc.spmm_minmax_bw(oc.F64, c.numpy(), v.double().abs().numpy(), x.double().numpy(),
-                                  gout.double().abs().numpy(), arg.cpu().numpy(), want_value=False)
-        _, cnt = oc.spmm_minmax_bw(oc.F64, c.numpy(), None, x.double().numpy(), np.ones_like(gout.double().numpy()),
-                                   arg.cpu().numpy(), want_value=False)
-        u = 2.0 ** -24 if dtype == torch.float32 else 2.0 ** -8
-        bound = (cnt + 2) * u * l1 * 1.01 + 1e-30
-        err = np.abs(xr.grad.cpu().double().numpy() - egm)
-        assert (err <= bound).all(), (dtype, K, float((err / bound).max()))
-        if with_value:
-            tol = 1e-5 if dtype == torch.float32 else 3e-2
-            assert np.allclose(vr.grad.cpu().double().numpy(), egv, rtol=tol, atol=tol * max(1.0, float(np.abs(egv).max())))
+        assert_within_scatter_bound(c, v, x, gout, arg, xr.grad, vr.grad if with_value else None, (dtype, K))
 
 
 def test_minmax_bw_csc_no_winner_and_empty(dev):
