@@ -17,6 +17,15 @@
 //
 // Deterministic (fixed combine tree), no atomics.  Empty segments give 0 (torch_scatter's
 // convention); mean divides by the segment length (floor division for integers).
+//
+// Min / max of floating types give the bits of the sequential loop (segment_reduce_kernel in
+// coalesce.hip: acc = first value, then `v < acc ? v : acc`): a NaN is the result exactly when it is
+// the segment's first entry, a later NaN is skipped, and of two equal candidates (+0.0 / -0.0) the
+// earlier entry wins.  That loop is not a tree, so: a NaN that is not its segment's first entry is
+// replaced on load by the reducer's identity (+inf / -inf), after which `b < a ? b : a` with a = the
+// EARLIER piece is associative (a NaN can only head the earliest piece, and stays); and every combine
+// -- scan, carry, fix-up -- takes its operands in entry order.  The fix-up therefore gives each lane a
+// contiguous run of tail records and reduces across lanes towards lane 0 (kSrOrdered).
 #include "common.h"
 #include "expand.h"
 
@@ -37,6 +46,10 @@ __device__ __forceinline__ A sr_combine(A a, A b) {
   else if constexpr (RED == SR_MIN) return b < a ? b : a;
   else return b > a ? b : a;
 }
+
+// min / max of a floating accumulator: the NaN and tie rule of the sequential loop (file header)
+template <typename A, int RED>
+constexpr bool kSrOrdered = RED != SR_ADD && std::is_floating_point<A>::value;
 
 template <typename T, typename A>
 __device__ __forceinline__ void sr_write(T *__restrict__ out, A v, int64_t cnt, bool mean) {
@@ -105,6 +118,10 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
         send = ptr[seg + 1];
       }
       v = Traits<T>::to_acc(value[(perm ? perm[e] : e) * D + d]);
+      if constexpr (kSrOrdered<A, RED>) {  // a NaN after the segment's first entry never wins
+        if (v != v && e != sstart)
+          v = RED == SR_MIN ? std::numeric_limits<A>::infinity() : -std::numeric_limits<A>::infinity();
+      }
     }
     // segmented inclusive scan: segments are contiguous runs, so "lane - off has my segment"
     // implies every lane in between has it too
@@ -169,16 +186,36 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_fixup_kernel(
   const A *tv = tail_val + d * nchunks;
   W acc = W(0);
   bool have = false;
-  for (int64_t i = lane; i < run; i += kWave) {
-    const W v = (W)tv[b - 1 - i];
-    acc = have ? sr_combine<W, RED>(acc, v) : v;
-    have = true;
-  }
-  for (int off = 32; off > 0; off >>= 1) {  // lanes without a record must not contribute
-    const W ov = lane_xor(acc, off);
-    const bool oh = lane_xor((int32_t)have, off) != 0;
-    if (oh) acc = have ? sr_combine<W, RED>(acc, ov) : ov;
-    have = have || oh;
+  if constexpr (kSrOrdered<A, RED>) {
+    // entry order: lane l folds records [l * per, (l + 1) * per) counted from the segment's first chunk,
+    // then lane l takes the piece of lane l + off behind its own
+    const int64_t per = (run + kWave - 1) / kWave;
+    const int64_t first = b - run;
+    const int64_t r0 = lane * per, r1 = r0 + per < run ? r0 + per : run;
+    for (int64_t i = r0; i < r1; ++i) {
+      const W v = (W)tv[first + i];
+      acc = have ? sr_combine<W, RED>(acc, v) : v;
+      have = true;
+    }
+    for (int off = 1; off < kWave; off <<= 1) {
+      const int src = lane + off < kWave ? lane + off : lane;
+      const W ov = lane_read(acc, src);
+      const bool oh = lane_read((int32_t)have, src) != 0;
+      if (lane + off < kWave && oh) acc = have ? sr_combine<W, RED>(acc, ov) : ov;
+      have = have || (lane + off < kWave && oh);
+    }
+  } else {
+    for (int64_t i = lane; i < run; i += kWave) {
+      const W v = (W)tv[b - 1 - i];
+      acc = have ? sr_combine<W, RED>(acc, v) : v;
+      have = true;
+    }
+    for (int off = 32; off > 0; off >>= 1) {  // lanes without a record must not contribute
+      const W ov = lane_xor(acc, off);
+      const bool oh = lane_xor((int32_t)have, off) != 0;
+      if (oh) acc = have ? sr_combine<W, RED>(acc, ov) : ov;
+      have = have || oh;
+    }
   }
   if (lane == 0) {
     const W hv = (W)head_val[d * nchunks + b];
