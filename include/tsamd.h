@@ -588,6 +588,54 @@ int tsamd_spspmm_numeric(int dtype, const int64_t *rowptrA, const int64_t *colA,
                          void *valC, int values_binned, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ------------------------------------------------------------------------ *
+ * SpSpMM value gradients (csrc/spspmm_bw.hip).  Serves the autograd node of tsamd::spspmm
+ * (csrc/ops_storage.cpp), i.e. SparseTensor @ SparseTensor (pytorch_sparse_amd/matmul.py) and the
+ * functional spspmm (pytorch_sparse_amd/spspmm.py); the reference's torch.sparse.mm is differentiable
+ * in both value tensors but torch_sparse/matmul.py:102 drops the graph at C._values().
+ * With C = A * B as tsamd_spspmm_numeric leaves it (structural pattern, rows sorted by column, explicit
+ * zeros kept), gC the gradient of valC and pos(i, j) the index of (i, j) in C:
+ *
+ *   gA[e] = sum_{p in row k of B}    vB[p] * gC[pos(i, colB[p])]      e = (i, k) of A
+ *   gB[p] = sum_{e in column k of A} vA[e] * gC[pos(row(e), j)]       p = (k, j) of B
+ *
+ * Both are one computation -- a SEGMENT (entry of A | entry of B) owns a LIST (row k of B | column k of A),
+ * one of (row, col) of the looked-up entry of C is fixed per segment, the other comes from the list -- so
+ * the entries take the operands in that generic form (a deviation from one signature per side):
+ *
+ *              segptr[nrows + 1]  segind[nseg]  listptr          list_ind             list_val
+ *   side 0 gA  rowptrA, M         colA, nnzA    rowptrB [K + 1]  colB                 valB | NULL
+ *   side 1 gB  rowptrB, K         colB, nnzB    colptrA [K + 1]  rowA in column order valA in column order | NULL
+ *
+ * list_val NULL = all ones.  fp32 / fp64 only (TSAMD_ERR_UNSUPPORTED otherwise).  Work is balanced by
+ * products: tiles of out[0] consecutive products, sums in a fixed order, no atomics -- two calls return the
+ * same bits.  No buffer proportional to the number of products P beyond two carry records per tile.
+ *
+ *   tsamd_spspmm_bw_route   host arithmetic only.  out[0] = products per tile; out[1] = the largest number
+ *        of segments a tile may intersect and still stage their pointers in LDS (a tile over more segments
+ *        -- long runs of segments with empty lists -- searches global memory: the one further route);
+ *        out[2] = products per wave; out[3] = carry records per tile; the rest 0.
+ *   tsamd_spspmm_bw_plan    ptr[nseg + 1] = exclusive scan of the list lengths; stats (DEVICE int64[2]):
+ *        [0] = bytes of workspace tsamd_spspmm_value_bw needs, [1] = P.  P does not depend on the side.
+ *        workspace: tsamd_spspmm_bw_plan_workspace_bytes(nseg).
+ *        --> host reads stats (the one sync: the grid and the carry records are sized by P).
+ *   tsamd_spspmm_value_bw   grad[nseg], every element written (zeroed inside the call, segments with an
+ *        empty list stay 0).  workspace: tsamd_spspmm_bw_workspace_bytes(dtype, P) = stats[0].
+ *        nseg = 0 or P = 0: TSAMD_OK, zeros written.  An entry of the product pattern that is missing
+ *        in C contributes 0 (never an out-of-range read).
+ * ------------------------------------------------------------------------ */
+int tsamd_spspmm_bw_route(int dtype, int64_t out[8]);
+size_t tsamd_spspmm_bw_plan_workspace_bytes(int64_t nseg);
+size_t tsamd_spspmm_bw_workspace_bytes(int dtype, int64_t P);
+int tsamd_spspmm_bw_plan(int dtype, int side, const int64_t *segptr, int64_t nrows, const int64_t *segind,
+                         int64_t nseg, const int64_t *listptr, int64_t *ptr, int64_t *stats, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int tsamd_spspmm_value_bw(int dtype, int side, const int64_t *ptr, int64_t P, const int64_t *segptr,
+                          int64_t nrows, const int64_t *segind, int64_t nseg, const int64_t *listptr,
+                          const int64_t *list_ind, const void *list_val, const int64_t *rowptrC,
+                          const int64_t *colC, const void *gC, void *grad, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * Sub-matrix extraction (the callers either side of the sharded
  * SpMM path).  Pure index work on a sorted pattern; order preserving.

@@ -32,6 +32,7 @@ SYMBOLS = [
     'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
     'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
+    'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
     'tsamd_select_workspace_bytes', 'tsamd_select_plan', 'tsamd_select_fill',
     'tsamd_filter_workspace_bytes', 'tsamd_filter_plan', 'tsamd_filter_apply',
     'tsamd_filter_tiles_workspace_bytes', 'tsamd_filter_count', 'tsamd_filter_write',
@@ -82,6 +83,8 @@ def lib():
         L.tsamd_status_string.restype = ctypes.c_char_p
         L.tsamd_spmm_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spspmm_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_spspmm_bw_plan_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_spspmm_bw_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_exclusive_scan_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_partial_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_workspace_bytes.restype = ctypes.c_size_t
@@ -219,6 +222,50 @@ def spmm_value_bw(row, rowptr, col, mat, grad, reduce):
                                        _i64(E), stream_ptr(mat.device))
     check(st, 'tsamd_spmm_value_bw')
     return out
+
+
+def spspmm_bw_route(dtype):
+    """C-ABI ``tsamd_spspmm_bw_route`` (host arithmetic, no device): the eight route words for a value dtype."""
+    out = (ctypes.c_int64 * 8)()
+    check(lib().tsamd_spspmm_bw_route(dtype_code(dtype), out), 'tsamd_spspmm_bw_route')
+    return [int(x) for x in out]
+
+
+def spspmm_value_bw(side, segptr, segind, listptr, list_ind, list_val, rowptrC, colC, gC, grad=None):
+    """C-ABI ``tsamd_spspmm_bw_plan`` + ``tsamd_spspmm_value_bw``: the gradient of one value tensor of C = A * B.
+    side 0 (gA): (rowptrA, colA, rowptrB, colB, valB or None); side 1 (gB): (rowptrB, colB, colptrA, rowA and valA
+    in column order, or None).  grad: an optional contiguous [nseg] buffer to write into.  Returns (grad [nseg], P); one
+    host sync (the plan's stats)."""
+    require_gpu(segptr, segind, listptr, list_ind, list_val, rowptrC, colC, gC)
+    if list_val is not None and list_val.dtype != gC.dtype:
+        raise TsamdError('expected scalar type %s but found %s' % (gC.dtype, list_val.dtype))
+    if not gC.is_contiguous() or (list_val is not None and not list_val.is_contiguous()):
+        raise TsamdError('tsamd_spspmm_value_bw: gC / list_val must be contiguous')
+    dev = gC.device
+    dt = dtype_code(gC.dtype)
+    nrows, nseg = segptr.numel() - 1, segind.numel()
+    L = lib()
+    ptr = torch.empty(nseg + 1, dtype=torch.int64, device=dev)
+    stats = torch.empty(2, dtype=torch.int64, device=dev)
+    if grad is None:
+        grad = torch.empty(nseg, dtype=gC.dtype, device=dev)
+    elif grad.dtype != gC.dtype or grad.numel() != nseg or not grad.is_contiguous() or grad.device != dev:
+        raise TsamdError('tsamd_spspmm_value_bw: grad must be a contiguous [nseg] tensor of the type of gC')
+    ws0 = workspace(L.tsamd_spspmm_bw_plan_workspace_bytes(_i64(nseg)), dev)
+    with torch.cuda.device(dev):
+        st = L.tsamd_spspmm_bw_plan(dt, ctypes.c_int(side), _ptr(segptr), _i64(nrows), _ptr(segind), _i64(nseg),
+                                    _ptr(listptr), _ptr(ptr), _ptr(stats), _ptr(ws0), ctypes.c_size_t(ws0.numel()),
+                                    stream_ptr(dev))
+        check(st, 'tsamd_spspmm_bw_plan')
+        nbytes, P = (int(x) for x in stats.cpu())
+        assert nbytes == L.tsamd_spspmm_bw_workspace_bytes(dt, _i64(P))
+        ws = workspace(nbytes, dev)
+        st = L.tsamd_spspmm_value_bw(dt, ctypes.c_int(side), _ptr(ptr), _i64(P), _ptr(segptr), _i64(nrows),
+                                     _ptr(segind), _i64(nseg), _ptr(listptr), _ptr(list_ind), _ptr(list_val),
+                                     _ptr(rowptrC), _ptr(colC), _ptr(gC), _ptr(grad), _ptr(ws),
+                                     ctypes.c_size_t(ws.numel()), stream_ptr(dev))
+    check(st, 'tsamd_spspmm_value_bw')
+    return grad, P
 
 
 def spmm_minmax_bw(rowptr, col, value, mat, grad_out, arg_out, want_value=True, want_mat=True):

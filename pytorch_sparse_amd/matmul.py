@@ -49,12 +49,11 @@ def spspmm_sum(src: SparseTensor, other: SparseTensor) -> SparseTensor:
     if valueA is not None and valueB is not None and valueA.dtype != valueB.dtype:
         dtype = torch.promote_types(valueA.dtype, valueB.dtype)
         valueA, valueB = valueA.to(dtype), valueB.to(dtype)
-    if valueA is not None:
-        valueA = valueA.detach()
-    if valueB is not None:
-        valueB = valueB.detach()
+    # differentiable in both value tensors (the reference drops this gradient at C._values(), matmul.py:102);
+    # the cached column view of A saves the backward a sort when valueB wants a gradient
     rowptrC, colC, valueC = torch.ops.tsamd.spspmm(rowptrA, colA, valueA, rowptrB, colB, valueB,
-                                                   other.sparse_size(1), with_value)
+                                                   other.sparse_size(1), with_value, src.storage._colptr,
+                                                   src.storage._csr2csc)
     value: Optional[Tensor] = None
     if with_value:
         value = valueC
