@@ -98,6 +98,17 @@ size_t tsamd_spmm_workspace_bytes(int dtype, int reduce, int64_t B, int64_t M,
 int tsamd_spmm_hot_rows_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                                const void *mat, const void *out, void *workspace, int64_t *layout);
 
+/* Hot blocks (inspection and tests; no device work): the same scope from N = 65536 on, where the unit of the side table
+ * is the block of 64 consecutive ids (a call takes one of the two routes, never both: for these shapes
+ * tsamd_spmm_hot_rows_layout returns 0, for smaller N this function does).  A block is selected when at least
+ * tsamd_spmm_hot_block_min() of its ids are flagged.  Returns 1 and fills layout[0..3]: byte offsets in `workspace` of
+ * the N flag bytes, of the block words (uint32 per block: rank + 1 among the selected blocks in block order, 0 = not
+ * selected) and of the table, and the table's distance from `mat` in rows.  Id i of the block of rank r sits in table
+ * row r * 64 + ((i + rot(r)) & 63), rot(r) = ((uint32_t)(r * 0x9E3779B1u)) >> 26; rows of ids >= N are not written. */
+int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                 const void *mat, const void *out, void *workspace, int64_t *layout);
+int tsamd_spmm_hot_block_min(void);
+
 int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const int64_t *col,
                const void *value, const void *mat, void *out, int64_t *arg_out,
                int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,

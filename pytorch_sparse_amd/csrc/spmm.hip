@@ -28,27 +28,41 @@ extern "C" int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const in
                            workspace_bytes_given, reinterpret_cast<hipStream_t>(stream_)});
 }
 
-// hot rows (include/tsamd.h): the host-side half of launch_spmm's decision, for callers that look into the workspace
-extern "C" int tsamd_spmm_hot_rows_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
-                                          const void *mat, const void *out, void *workspace, int64_t *layout) {
+// hot rows / hot blocks (include/tsamd.h): the host-side half of launch_spmm's decision, for callers that look into the
+// workspace.  `blocks` says which of the two routes is asked about; a call takes at most one of them.
+static int hot_layout(bool blocks, int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                      const void *mat, const void *out, void *workspace, int64_t *layout) {
   if (!layout || !workspace || !mat || dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
   if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return 0;
   if (spmm_reference_order_on() || (uintptr_t)workspace % 256 != 0) return 0;
   Workspace ws;
   carve(workspace, dtype, reduce, B, M, N, K, E, &ws);
+  if ((ws.blk_word != nullptr) != blocks) return 0;
   const size_t es = dtype_size(dtype);
   const size_t packet = (es <= 2 ? 4 : 16 / es) * es;  // full-width packets (spmm_entry)
   if ((K * es) % packet != 0 || (uintptr_t)mat % packet != 0 || (uintptr_t)out % packet != 0) return 0;
   void *side = nullptr;
   int32_t side_row = 0;
-  if (!hot_rows_place(ws, mat, N, (uint64_t)K * es, &side, &side_row)) return 0;
+  if (!hot_rows_place(ws, mat, blocks ? N + 64 : N, (uint64_t)K * es, &side, &side_row)) return 0;
   const char *base = reinterpret_cast<const char *>(workspace);
   layout[0] = reinterpret_cast<const char *>(ws.hot_flag) - base;
-  layout[1] = reinterpret_cast<const char *>(ws.hot_word) - base;
+  layout[1] = reinterpret_cast<const char *>(blocks ? ws.blk_word : ws.hot_word) - base;
   layout[2] = reinterpret_cast<const char *>(side) - base;
   layout[3] = side_row;
   return 1;
 }
+
+extern "C" int tsamd_spmm_hot_rows_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                          const void *mat, const void *out, void *workspace, int64_t *layout) {
+  return hot_layout(false, dtype, reduce, B, M, N, K, E, mat, out, workspace, layout);
+}
+
+extern "C" int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                            const void *mat, const void *out, void *workspace, int64_t *layout) {
+  return hot_layout(true, dtype, reduce, B, M, N, K, E, mat, out, workspace, layout);
+}
+
+extern "C" int tsamd_spmm_hot_block_min(void) { return kHotBlockMin; }
 
 // ---------------------------------------------------------------------------
 // operand cache: see include/tsamd.h

@@ -134,6 +134,12 @@ struct Workspace {
   void *hot_side;          // the table; (hot_side - mat) is a whole number of rows
   int32_t hot_side_row;    // (hot_side - mat) / row bytes: a gathered index stays `mat`-relative and signed
   int64_t hot_stride;      // every hot_stride-th entry of `col` is sampled
+  // hot blocks (see "hot blocks" below; N >= kHotBlockMinN): the unit of the table is the block of 64 consecutive ids.
+  // The three arrays share the storage of hot_word / hot_count, which this route does not use.
+  uint32_t *blk_word;   // [ceil(N / 64)] rank + 1 of a selected block, 0 otherwise; nullptr = the per-id route
+  uint32_t *blk_list;   // [ceil(N / 64)] indices of the selected blocks, compacted within every chunk of blk_chunk blocks
+  uint32_t *blk_total;  // [kHotChunks] selected blocks per chunk
+  uint32_t blk_chunk;   // blocks per chunk, a multiple of 256
 };
 
 // One SpMM call: the operands of tsamd_spmm (include/tsamd.h), then the optional modes (see Workspace), off unless set.
@@ -393,6 +399,135 @@ __global__ __launch_bounds__(256) void spmm_hot_copy_kernel(const void *__restri
 #pragma unroll
         for (int t = 0; t < kRows; ++t)
           if (on[t]) dst[to[t] + sl] = v[t];
+      }
+    }
+  }
+}
+
+// Hot blocks: from N = kHotBlockMinN on, the unit of the table is the block of 64 consecutive ids instead of the id.
+// (Smaller N keeps the per-id route above exactly as it is: its workspace layout is pinned by a test.  That is the only
+// reason two routes exist.)  A block is selected when at least kHotBlockMin of its ids are flagged; its rank among the
+// selected blocks is its place in the table, and id i of the block of rank r sits in slot
+// r * 64 + ((i + hot_block_rot(r)) & 63).  Both sides of the copy are then one contiguous span of 64 rows, whose source
+// rows take every value of the low six id bits -- the per-id copy read the popular low-bit patterns only and camped like
+// the gathers it replaced -- and the lookup is one 4-byte word per block: rank + 1, or 0.  The rotation keeps the
+// popular low-bit patterns of consecutive selected blocks from landing on the same table offsets.
+// Ranks without a scan launch and without waiting: spmm_hot_block_bits_kernel compacts the selected blocks of each of
+// kHotChunks chunks and leaves the chunk's total; every workgroup of the copy kernel adds the totals up for itself.
+// (threshold: -DTSAMD_HOT_BLOCK_MIN=8 / 16 / 32 measured as built code, docs/design/spmm_forward.md "Hot blocks": 32 has the
+// shortest call on all three bench shapes -- the smallest table, and a merge kernel no slower than with 16)
+#ifndef TSAMD_HOT_BLOCK_MIN
+#define TSAMD_HOT_BLOCK_MIN 32
+#endif
+constexpr int kHotBlockMin = TSAMD_HOT_BLOCK_MIN;
+constexpr int64_t kHotBlockMinN = 65536;
+constexpr int kHotChunks = 128;
+
+__device__ __forceinline__ uint32_t hot_block_rot(uint32_t rank) { return (rank * 0x9E3779B1u) >> 26; }
+
+// a workgroup per chunk, a thread per block: 64 flag bytes -> selected or not; unselected blocks get their word (0),
+// selected ones their place in the chunk's list (their word comes from the copy kernel, which knows the rank)
+__global__ __launch_bounds__(256) void spmm_hot_block_bits_kernel(int64_t N, Workspace ws) {
+  if (!use_relabel(ws.relabel_mode, ws.relabel_flag)) return;
+  __shared__ uint32_t wave_sum[4];
+  const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
+  const int64_t words = (N + 63) >> 6;
+  const int64_t first = (int64_t)blockIdx.x * ws.blk_chunk;
+  const uint4 *flag16 = reinterpret_cast<const uint4 *>(ws.hot_flag);  // (256-byte aligned, padded to 256: carve)
+  auto count4 = [&](uint32_t f, int64_t i0) -> int {  // flags of ids i0 .. i0 + 3, those >= N left out
+    const int64_t v = N - i0;
+    const uint32_t mk = v >= 4 ? 0xFFFFFFFFu : (v <= 0 ? 0u : ((1u << (8 * (int)v)) - 1u));
+    return __popc(f & mk & 0x01010101u);
+  };
+  uint32_t run = 0;  // selected blocks of the chunk so far
+  for (int64_t t = 0; t < (int64_t)ws.blk_chunk && first + t < words; t += 256) {  // (uniform bounds)
+    const int64_t w = first + t + threadIdx.x;
+    bool sel = false;
+    if (w < words) {
+      int cnt = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint4 f = flag16[w * 4 + q];
+        const int64_t i0 = w * 64 + q * 16;
+        cnt += count4(f.x, i0) + count4(f.y, i0 + 4) + count4(f.z, i0 + 8) + count4(f.w, i0 + 12);
+      }
+      sel = cnt >= kHotBlockMin;
+    }
+    const unsigned long long m = __ballot(sel);
+    if (lane == 0) wave_sum[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = run + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (int i = 0; i < wv; ++i) before += wave_sum[i];
+    run += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+    if (w < words) {
+      if (sel) ws.blk_list[first + before] = (uint32_t)w;
+      else ws.blk_word[w] = 0u;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) ws.blk_total[blockIdx.x] = run;
+}
+
+// A 256-thread block per selected block of 64 ids and iteration: 64 x slots 16-byte packets, contiguous on both sides
+// (the rotation permutes whole rows inside the span), four packets per lane in flight.  `lgS` = log2(slots): row sizes
+// here are powers of two.  The workgroup that copies the block of rank r also enters r + 1 into the block's word.
+__global__ __launch_bounds__(256) void spmm_hot_block_copy_kernel(const void *__restrict__ mat, int64_t N, int lgS,
+                                                                 Workspace ws) {
+  if (!use_relabel(ws.relabel_mode, ws.relabel_flag)) return;
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  __shared__ uint32_t start[kHotChunks + 1];  // exclusive prefix sums of the chunks' totals
+  __shared__ uint32_t half_sum;
+  static_assert(kHotChunks == 128, "two waves scan the totals");
+  {
+    const int lane = (int)(threadIdx.x & 63);
+    const uint32_t v = threadIdx.x < (unsigned)kHotChunks ? ws.blk_total[threadIdx.x] : 0u;
+    uint32_t inc = v;
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t u = lane_read_u32(inc, lane >= off ? lane - off : lane);
+      if (lane >= off) inc += u;
+    }
+    if (threadIdx.x == 63) half_sum = inc;
+    __syncthreads();
+    const uint32_t add = threadIdx.x >= 64 ? half_sum : 0u;
+    if (threadIdx.x < (unsigned)kHotChunks) start[threadIdx.x] = inc - v + add;
+    if (threadIdx.x == (unsigned)kHotChunks - 1) start[kHotChunks] = inc + add;
+    __syncthreads();
+  }
+  const uint32_t selected = start[kHotChunks];
+  auto block_of = [&](uint32_t r) -> uint32_t {  // the r-th selected block: its chunk from the prefix sums, then the list
+    if (r >= selected) return 0u;
+    int g = 0;
+    for (int step = kHotChunks / 2; step > 0; step >>= 1)
+      if (start[g + step] <= r) g += step;  // the last chunk that starts at or before r (empty chunks in front of it tie)
+    return ws.blk_list[(uint64_t)g * ws.blk_chunk + (r - start[g])];
+  };
+  const u32x4 *src = reinterpret_cast<const u32x4 *>(mat);
+  u32x4 *dst = reinterpret_cast<u32x4 *>(ws.hot_side);
+  const uint32_t slots = 1u << lgS;
+  const uint32_t packets = 64u << lgS;  // of one block: a multiple of 4 x 256 (rows of >= 256 bytes)
+  constexpr int kInFlight = 4;
+  uint32_t w_next = block_of(blockIdx.x);
+  for (uint32_t r = blockIdx.x; r < selected; r += gridDim.x) {
+    const uint32_t w = w_next;
+    w_next = block_of(r + gridDim.x);  // the next list entry is on its way while this block moves
+    if (threadIdx.x == 0) ws.blk_word[w] = r + 1u;
+    const uint32_t rot = hot_block_rot(r);
+    const int64_t id0 = (int64_t)w * 64;
+    const uint64_t from = (uint64_t)id0 << lgS, to = ((uint64_t)r * 64u) << lgS;
+    for (uint32_t p0 = threadIdx.x; p0 < packets; p0 += kInFlight * 256) {
+      u32x4 v[kInFlight];
+      bool on[kInFlight];
+#pragma unroll
+      for (int t = 0; t < kInFlight; ++t) {
+        const uint32_t p = p0 + t * 256;
+        on[t] = id0 + (int64_t)(p >> lgS) < N;  // the last block of N is partial
+        if (on[t]) v[t] = __builtin_nontemporal_load(src + from + p);  // streamed once, as in the full copy
+      }
+#pragma unroll
+      for (int t = 0; t < kInFlight; ++t) {
+        const uint32_t p = p0 + t * 256;
+        const uint32_t row = ((p >> lgS) + rot) & 63u;
+        if (on[t]) dst[to + ((uint64_t)row << lgS) + (p & (slots - 1u))] = v[t];
       }
     }
   }
@@ -922,8 +1057,9 @@ constexpr int kMinWavesPerEU = kPartial ? ((RED == RED_ADD && !SHORT && !MASKED)
 // HOT: the sum kernel of the hot-row side table (section 0b).  It never gathers from the hashed copy: when the probe
 // flagged the graph, a column id becomes a signed row index relative to `mat` -- the id itself, or the id's slot in the
 // side table -- through one 8-byte lookup per entry, which runs as a third window stage: raw ids of window k + 2 and the
-// lookup of window k + 1 are in flight while window k is consumed.
-template <typename T, int VEC, int RED, bool SHORT, bool MASKED = false, bool A32 = false, int REC = 0, bool HOT = false>
+// lookup of window k + 1 are in flight while window k is consumed.  HOT = 1: the per-id table (8-byte half words);
+// HOT = 2: the block table (one 4-byte word per 64 ids: rank + 1 of the id's block, or 0).
+template <typename T, int VEC, int RED, bool SHORT, bool MASKED = false, bool A32 = false, int REC = 0, int HOT = 0>
 __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, MASKED, REC>)) void spmm_merge_kernel(
     const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col,
     const T *__restrict__ value, const T *__restrict__ mat, T *__restrict__ out,
@@ -952,7 +1088,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
   const int kl = lane & (lpr - 1);
   const uint32_t k0 = (kt * 64u + (uint32_t)kl) * VEC;
   const bool kok = k0 < K;
-  static_assert(!HOT || (RED == RED_ADD && !SHORT && !MASKED && !A32 && REC == 0 && !kPartial), "hot rows: plain sums only");
+  static_assert(HOT == 0 || (RED == RED_ADD && !SHORT && !MASKED && !A32 && REC == 0 && !kPartial), "hot rows: plain sums only");
   const bool flagged = use_relabel(ws.relabel_mode, ws.relabel_flag);  // wave-uniform
   const bool relabel = HOT ? false : flagged;
   const bool hot = HOT ? flagged : false;
@@ -1038,12 +1174,21 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
   };
   auto hot_lookup = [&](uint32_t c) {  // (lanes past e1 hold id 0: word 0 exists)
     if (!hot) return;
-    const uint2 wd = *reinterpret_cast<const uint2 *>(ws.hot_word + (uint64_t)(c >> 5) * 2u);  // the id's half word
-    hw0 = wd.x;
-    hw1 = wd.y;
+    if constexpr (HOT == 2) {
+      hw0 = ws.blk_word[c >> 6];  // the word of the id's block
+    } else {
+      const uint2 wd = *reinterpret_cast<const uint2 *>(ws.hot_word + (uint64_t)(c >> 5) * 2u);  // the id's half word
+      hw0 = wd.x;
+      hw1 = wd.y;
+    }
   };
   auto hot_resolve = [&](uint32_t c) -> uint32_t {
     if (!hot) return c;
+    if constexpr (HOT == 2) {
+      const uint32_t r = hw0 - 1u;
+      const uint32_t slot = (uint32_t)ws.hot_side_row + r * 64u + ((c + hot_block_rot(r)) & 63u);
+      return hw0 != 0u ? slot : c;
+    }
     const uint32_t b = c & 31u;
     const uint32_t slot = (uint32_t)ws.hot_side_row + hw1 + (uint32_t)__popc(hw0 & ((1u << b) - 1u));
     return ((hw0 >> b) & 1u) != 0 ? slot : c;
@@ -1056,7 +1201,8 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
     // the registers about to be reloaded count as read HERE, where everything in flight is a window old: a window that
     // consumed nothing (an empty tail) would otherwise leave their old loads "pending", and the compiler would drain
     // the queue -- the lookup just requested included -- in front of the overwrite
-    asm volatile("" : : "v"(w_look), "v"(c_free), "v"(hw0), "v"(hw1));
+    if constexpr (HOT == 2) asm volatile("" : : "v"(w_look), "v"(c_free), "v"(hw0));
+    else asm volatile("" : : "v"(w_look), "v"(c_free), "v"(hw0), "v"(hw1));
     c_res = hot_resolve(c_res);
     hot_lookup(c_look);
     w_look = hot_weights(wbase + 2 * kWave);
@@ -1274,7 +1420,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
       }
       const int64_t stop = rend < wend ? rend : wend;
       if (e < stop) {
-        accumulate_window<T, VEC, RED, MASKED, HOT>((int)(e - wbase), (int)(stop - wbase), (uint32_t)(wbase - e0),
+        accumulate_window<T, VEC, RED, MASKED, HOT != 0>((int)(e - wbase), (int)(stop - wbase), (uint32_t)(wbase - e0),
                                                c_w, w_w, has_value, matk, K, lgG, g, val, arg, e_w, maskk,
                                                ws.rec_stride, mask_shift, z_w, mask_seg);
         e = stop;
@@ -1777,8 +1923,10 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   // hot rows (section 0b): sums of one matrix; the side table shares the copy's region, one row of slack lets it start a
   // whole number of rows from `mat`
   const bool hot_scope = !relabelled && relabel_possible(dtype, reduce, N, K, E) && !minmax && B == 1 && N < ((int64_t)1 << 31);
+  // hot blocks: the same scope from N = kHotBlockMinN on; 64 more rows, for a table of every block whose last one is partial
+  const bool blk_scope = hot_scope && N >= kHotBlockMinN;
   w.xperm = (!relabelled && relabel_possible(dtype, reduce, N, K, E))
-                ? take(dtype_size(dtype) * (size_t)B * N * K + (hot_scope ? dtype_size(dtype) * (size_t)K : 0))
+                ? take(dtype_size(dtype) * (size_t)B * N * K + (hot_scope ? dtype_size(dtype) * (size_t)K * (blk_scope ? 65 : 1) : 0))
                 : nullptr;
   // (carved behind the copy of X: the position of that copy relative to the start of the workspace decides which
   // of its hot rows share a memory channel -- 3-5 % of the north-star kernel either way, measured by padding --
@@ -1792,6 +1940,10 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   w.hot_side = nullptr;
   w.hot_side_row = 0;
   w.hot_stride = TSAMD_HOT_STRIDE;
+  w.blk_word = blk_scope ? w.hot_word : nullptr;
+  w.blk_list = blk_scope ? w.hot_word + hot_words : nullptr;
+  w.blk_total = blk_scope ? reinterpret_cast<uint32_t *>(w.hot_count) : nullptr;  // (8 * hot_words >= 4 * kHotChunks bytes)
+  w.blk_chunk = (uint32_t)(ceil_div(ceil_div(hot_words, (int64_t)kHotChunks), (int64_t)256) * 256);
   w.hash_bits = 1;
   while (w.hash_bits < 32 && ((uint64_t)1 << w.hash_bits) < (uint64_t)(N > 1 ? N : 2)) ++w.hash_bits;
   w.hash_mul = 0x9E3779B1u;  // odd (golden-ratio) multiplier
@@ -1881,7 +2033,8 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
       // (lgG < 3: the side-by-side short-row kernel knows nothing of the table; rows of >= 256 bytes in full-width
       // packets never take it, this keeps the two decisions tied together)
       if (mode == 2 && lgG < 3 && ws.cache_state == 0 && ws.perm == nullptr)
-        hot = hot_rows_place(ws, mat, N, (uint64_t)K * sizeof(T), &ws.hot_side, &ws.hot_side_row);
+        hot = hot_rows_place(ws, mat, ws.blk_word != nullptr ? N + 64 : N, (uint64_t)K * sizeof(T), &ws.hot_side,
+                             &ws.hot_side_row);  // (the block table ends at most 64 rows further from `mat`)
     }
     if (!hot) ws.hot_flag = nullptr;
     const bool cached = ws.cache_state != 0 && mode != 0;
@@ -1899,16 +2052,25 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
       TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
       hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
       TSAMD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(spmm_hot_bits_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(words, (int64_t)4), kHotBlocks)),
-                         dim3(256), 0, stream, N, ws);
-      TSAMD_LAUNCH_CHECK();
-      // (the scan is not device-gated: on a graph the probe does not flag, its three launches run over counts nobody
-      // wrote or reads -- a few idle microseconds, no effect)
-      const int st = exclusive_scan_i64(ws.hot_count, ws.hot_count, words, nullptr, ws.hot_scan, stream);
-      if (st != TSAMD_OK) return st;
-      hipLaunchKernelGGL(spmm_hot_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, 4 * kHotBlocks)), dim3(256), 0,
-                         stream, reinterpret_cast<const void *>(mat), N, pslots, lgL, ws);
-      TSAMD_LAUNCH_CHECK();
+      if (ws.blk_word != nullptr) {  // hot blocks: select and compact, then copy; no scan launches
+        const int lgS = ilog2_ceil(pslots);  // (exact: the rows that relabel_possible admits are powers of two)
+        hipLaunchKernelGGL(spmm_hot_block_bits_kernel, dim3(kHotChunks), dim3(256), 0, stream, N, ws);
+        TSAMD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(spmm_hot_block_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, kHotBlocks)), dim3(256), 0,
+                           stream, reinterpret_cast<const void *>(mat), N, lgS, ws);
+        TSAMD_LAUNCH_CHECK();
+      } else {
+        hipLaunchKernelGGL(spmm_hot_bits_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(words, (int64_t)4), kHotBlocks)),
+                           dim3(256), 0, stream, N, ws);
+        TSAMD_LAUNCH_CHECK();
+        // (the scan is not device-gated: on a graph the probe does not flag, its three launches run over counts nobody
+        // wrote or reads -- a few idle microseconds, no effect)
+        const int st = exclusive_scan_i64(ws.hot_count, ws.hot_count, words, nullptr, ws.hot_scan, stream);
+        if (st != TSAMD_OK) return st;
+        hipLaunchKernelGGL(spmm_hot_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, 4 * kHotBlocks)), dim3(256), 0,
+                           stream, reinterpret_cast<const void *>(mat), N, pslots, lgL, ws);
+        TSAMD_LAUNCH_CHECK();
+      }
     } else if (mode != 0) {
       if (cached) {
         hipLaunchKernelGGL(spmm_fingerprint_kernel, dim3(kFingerprintWords), dim3(256), 0, stream,
@@ -1981,7 +2143,10 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   } else if (lgG >= 3)
     merge(spmm_merge_kernel<T, VEC, RED, true>);
   else if (kHotable && ws.hot_flag != nullptr) {
-    if constexpr (kHotable) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, true>);
+    if constexpr (kHotable) {
+      if (ws.blk_word != nullptr) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 2>);
+      else merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 1>);
+    }
   } else
     merge(spmm_merge_kernel<T, VEC, RED, false>);
   TSAMD_LAUNCH_CHECK();
