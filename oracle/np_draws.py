@@ -6,7 +6,7 @@ redraw -- so it can be restated bit for bit:
   philox / fmix32 / umul64hi / permute_index     the primitives (csrc/philox.h, csrc/sample.hip)
   sample_draw / ego_draw / temporal_redraw       what tsamd_sample_plan + _draw, tsamd_ego_plan + _draw and
                                                  tsamd_temporal_redraw write
-  host_seed, neighbor_seed, ego_seed,            how the operators (csrc/ops_sample.cpp) derive the seed of a draw from
+  host_seed, neighbor_seed, ego_seed,            how the operators (csrc/ops_sample.h) derive the seed of a draw from
   hetero_seed, redraw_seed                       torch's CPU generator
   sample_adj_draws / neighbor_draws /            the draw sources the sequential restatements take as `draws=`
   ego_draws / HeteroDraws                        (oracle/np_oracle.py, tests/ego_reference.py)

@@ -1,4 +1,4 @@
-// Shared helpers of the torch operator glue (ops_spmm.cpp, ops_storage.cpp, ops_sample.cpp): argument
+// Shared helpers of the torch operator glue (ops_spmm.cpp, ops_storage.cpp, ops_sample*.cpp): argument
 // checks, dtype / reduce codes, workspaces, the current HIP stream.  Host-only C++ (g++), links torch.
 #pragma once
 

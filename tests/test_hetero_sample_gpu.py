@@ -1,4 +1,4 @@
-"""torch_sparse::hetero_neighbor_sample / hetero_temporal_neighbor_sample on the GPU (csrc/ops_sample.cpp) against the
+"""torch_sparse::hetero_neighbor_sample / hetero_temporal_neighbor_sample on the GPU (csrc/ops_sample_hetero.cpp) against the
 reference's CPU samplers (csrc/cpu/neighbor_sample_cpu.cpp:135-507):
   * tests/golden/py8_hetero_*.npz -- outputs of the COMPILED REFERENCE (make_golden.py part 8) for every deterministic
     case (take all neighbours, or more draws than neighbours): every node list, row / col / edge list bit for bit;
@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from tests.util import _count_syncs
 
 pytestmark = pytest.mark.gpu
 
@@ -179,33 +181,6 @@ def test_temporal_constraint_holds_on_every_drawn_edge(ops):
                 cnt = torch.bincount(c, minlength=roots.numel())
                 assert torch.equal(cnt, torch.where(valid > 0, torch.full_like(valid, 5), torch.zeros_like(valid)))
         assert seen > 0
-
-
-def _count_syncs(fn):
-    """Number of synchronising device -> host operations `fn` performs: torch's sync debug mode warns on each -- as a
-    Python warning when the operation is called from Python, on the process's stderr from inside a C++ operator (file
-    descriptor 2 is captured around the call)."""
-    import sys
-    import tempfile
-    import warnings
-    torch.cuda.synchronize()
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode='w+b') as tmp, warnings.catch_warnings(record=True) as caught:
-        warnings.simplefilter('always')
-        os.dup2(tmp.fileno(), 2)
-        torch.cuda.set_sync_debug_mode('warn')
-        try:
-            out = fn()
-        finally:
-            torch.cuda.set_sync_debug_mode('default')
-            sys.stderr.flush()
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        text = tmp.read().decode(errors='replace')
-        n_py = sum('synchronizing' in str(w.message) for w in caught)
-    return out, text.count('synchronizing') + n_py
 
 
 @pytest.mark.parametrize('temporal', [False, True])

@@ -16,7 +16,7 @@ import torch
 import pytorch_sparse_amd  # noqa: F401  (registers the torch_sparse:: ops)
 from tests.hgt_reference import (LAW_BUDGETS, LAW_K, LAW_R, MAX_NEIGHBORS, hgt_assemble, hgt_budget, hgt_expand_det,
                                  inclusion_probabilities, law_bound, split)
-from tests.test_hetero_sample_gpu import _count_syncs
+from tests.util import _count_syncs
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,9 @@
 """Shared helpers for the parity tests: torch <-> oracle (numpy) plumbing and tolerances."""
+import os
+import sys
+import tempfile
+import warnings
+
 import numpy as np
 import torch
 
@@ -134,3 +139,27 @@ def ref_minmax_bw(rowptr, col, value, mat, grad, arg, want_value):
     gv, gm = oc.spmm_minmax_bw(CODE[mat.dtype], tonp(col), tonp(value), tonp(mat), tonp(grad), tonp(arg),
                                want_value=want_value and value is not None, want_mat=True)
     return (None if gv is None else fromnp(gv, mat.dtype)), fromnp(gm, mat.dtype)
+
+
+def _count_syncs(fn):
+    """Number of synchronising device -> host operations `fn` performs: torch's sync debug mode warns on each -- as a
+    Python warning when the operation is called from Python, on the process's stderr from inside a C++ operator (file
+    descriptor 2 is captured around the call)."""
+    torch.cuda.synchronize()
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode='w+b') as tmp, warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter('always')
+        os.dup2(tmp.fileno(), 2)
+        torch.cuda.set_sync_debug_mode('warn')
+        try:
+            out = fn()
+        finally:
+            torch.cuda.set_sync_debug_mode('default')
+            sys.stderr.flush()
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors='replace')
+        n_py = sum('synchronizing' in str(w.message) for w in caught)
+    return out, text.count('synchronizing') + n_py
