@@ -406,8 +406,38 @@ int tsamd_segment_reduce_balanced(int dtype, int reduce, const void *value, cons
                                   const int64_t *seg_ptr, int64_t nseg, int64_t E, int64_t D,
                                   void *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Entry-balanced segmented softmax and its backward (csrc/softmax.hip): SparseTensor.softmax(dim), the
+ * normalisation of attention layers over the stored entries of every row (perm = NULL, seg_ptr = rowptr) or
+ * column (perm = csr2csc, seg_ptr = colptr).  Entry i of the segmented order is element perm ? perm[i] : i of
+ * value / y / grad / out / grad_value, each [E, D] contiguous; the output is written in the input's own order.
+ *   forward   out = exp(value - m) / s, m and s the maximum and the sum of exp(value - m) of the entry's segment
+ *             and head (column of D); a segment alone behaves as torch.softmax does on it: -inf gives 0, a
+ *             segment of -inf only, or one that holds +inf or a NaN, is all NaN; other segments and heads are
+ *             not touched by it.  Empty segments write nothing.
+ *   backward  grad_value = y * (grad - sum over the segment of grad * y), from the forward's output y.
+ * float32 / float16 / bfloat16 accumulate in fp32, float64 in fp64; one rounding on the store.  Work is split by
+ * entries; deterministic, no atomics, no host sync.  Needs seg_ptr[0] = 0 and seg_ptr[nseg] = E.
+ * Status, in this order: a negative size TSAMD_ERR_INVALID; a non-floating dtype or D > 65535
+ * TSAMD_ERR_UNSUPPORTED; E == 0 or D == 0 TSAMD_OK without a launch; a null pointer (or nseg == 0)
+ * TSAMD_ERR_INVALID; a missing or short workspace TSAMD_ERR_WORKSPACE.
+ *   tsamd_segment_softmax_route (host arithmetic only): out[0] entries per wave chunk, out[1] entries per
+ *   workgroup tile, out[2] the largest number of segments a tile stages in LDS, out[3] tail records one fix-up
+ *   round folds per wave, out[4..7] = 0.
+ *   workspace = 3 * align256(2 * acc * D * nchunks) + 2 * align256(8 * nchunks), nchunks = ceil(E / out[0]),
+ *   acc = 8 for float64, else 4 (0 for a dtype that is not supported).
+ * ------------------------------------------------------------------------ */
+int tsamd_segment_softmax_route(int64_t out[8]);
+size_t tsamd_segment_softmax_workspace_bytes(int dtype, int64_t E, int64_t D);
+int tsamd_segment_softmax(int dtype, const void *value, const int64_t *perm, const int64_t *seg_ptr,
+                          int64_t nseg, int64_t E, int64_t D, void *out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int tsamd_segment_softmax_bw(int dtype, const void *y, const void *grad, const int64_t *perm,
+                             const int64_t *seg_ptr, int64_t nseg, int64_t E, int64_t D, void *grad_value,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ *
- * COO ordering / sorting / coalescing.  Replace the Python + ATen +
+ * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):
  *
  *   tsamd_coo_order      the `(idx[1:] < idx[:-1]).any()` / `mask.all()` probes

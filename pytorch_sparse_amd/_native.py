@@ -30,6 +30,7 @@ SYMBOLS = [
     'tsamd_coo_order', 'tsamd_coo_check', 'tsamd_sort_rank_mode', 'tsamd_sort_route', 'tsamd_sort_coalesce_workspace_bytes', 'tsamd_sort_coalesce', 'tsamd_sort_coalesce_reduce', 'tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo', 'tsamd_sort_coo_auto', 'tsamd_sort_coo_probed', 'tsamd_sort_coo_values',
     'tsamd_coalesce_workspace_bytes', 'tsamd_coalesce_index', 'tsamd_segment_reduce',
     'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
+    'tsamd_segment_softmax_route', 'tsamd_segment_softmax_workspace_bytes', 'tsamd_segment_softmax', 'tsamd_segment_softmax_bw',
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
     'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
     'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
@@ -92,6 +93,7 @@ def lib():
         L.tsamd_spmm_minmax_records_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_records_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_segment_softmax_workspace_bytes.restype = ctypes.c_size_t
         _lib = L
     return _lib
 

@@ -305,6 +305,56 @@ Tensor segment_reduce(Tensor value, OptTensor perm, Tensor seg_ptr, int64_t nseg
   return out;
 }
 
+// Segmented softmax (csrc/softmax.hip) and its backward; `second` is the gradient of the backward call.
+// -> a tensor of the shape of `first`, in its own order (entry i of the segmented order is element perm[i]).
+Tensor segment_softmax_call(bool backward, Tensor first, OptTensor second, OptTensor perm, Tensor seg_ptr,
+                            int64_t nseg) {
+  const char *what = backward ? "tsamd_segment_softmax_bw" : "tsamd_segment_softmax";
+  check_gpu(first, backward ? "y" : "value");
+  check_index(seg_ptr, "seg_ptr");
+  if (perm.has_value()) check_index(perm.value(), "perm");
+  TORCH_CHECK(first.dim() >= 1, "value must have at least one dimension");
+  TORCH_CHECK(at::isFloatingType(first.scalar_type()), what,
+              ": float32, float64, float16 or bfloat16 values expected, got ", first.scalar_type());
+  TORCH_CHECK(nseg >= 0 && seg_ptr.numel() >= nseg + 1, "seg_ptr shorter than nseg + 1");
+  TORCH_CHECK(!perm.has_value() || perm.value().numel() == first.size(0), "perm and value differ in length");
+  c10::hip::HIPGuard guard(first.get_device());
+  first = first.contiguous();
+  seg_ptr = seg_ptr.contiguous();
+  Tensor grad;
+  if (backward) {
+    grad = second.value();
+    check_gpu(grad, "grad");
+    TORCH_CHECK(grad.sizes() == first.sizes() && grad.scalar_type() == first.scalar_type(),
+                "grad must have the shape and type of y");
+    grad = grad.contiguous();
+  }
+  const int64_t E = first.size(0);
+  const int64_t D = E > 0 ? first.numel() / E : 1;
+  Tensor out = torch::empty(first.sizes(), first.options().requires_grad(false));
+  if (E == 0 || D == 0) return out;
+  Tensor p = perm.has_value() ? perm.value().contiguous() : Tensor();
+  const int64_t *pp = perm.has_value() ? p.data_ptr<int64_t>() : nullptr;
+  const int dt = dtype_code(first);
+  Tensor ws = workspace(tsamd_segment_softmax_workspace_bytes(dt, E, D), first);
+  const int st =
+      backward ? tsamd_segment_softmax_bw(dt, first.data_ptr(), grad.data_ptr(), pp, seg_ptr.data_ptr<int64_t>(),
+                                          nseg, E, D, out.data_ptr(), ws.data_ptr(), (size_t)ws.numel(),
+                                          current_stream(first))
+               : tsamd_segment_softmax(dt, first.data_ptr(), pp, seg_ptr.data_ptr<int64_t>(), nseg, E, D,
+                                       out.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), current_stream(first));
+  check_status(st, what);
+  return out;
+}
+
+Tensor segment_softmax(Tensor value, OptTensor perm, Tensor seg_ptr, int64_t nseg) {
+  return segment_softmax_call(false, value, OptTensor(), perm, seg_ptr, nseg);
+}
+
+Tensor segment_softmax_bw(Tensor y, Tensor grad, OptTensor perm, Tensor seg_ptr, int64_t nseg) {
+  return segment_softmax_call(true, y, grad, perm, seg_ptr, nseg);
+}
+
 // C = A * B on CSR operands -> (rowptrC, colC, valueC); valueC is empty unless with_value.
 // Count first, write once (csrc/spspmm.hip); two host syncs (size classes, nnz(C)) because the
 // scratch of oversized rows and the output size are data dependent.
@@ -718,6 +768,11 @@ static auto registry_storage = torch::RegisterOperators()
                            .op("tsamd::sort_coalesce", &sort_coalesce)
                            .op("tsamd::sort_coalesce_reduce", &sort_coalesce_reduce)
                            .op("tsamd::segment_reduce", &segment_reduce)
+                           .op("tsamd::segment_softmax(Tensor value, Tensor? perm, Tensor seg_ptr, int nseg) -> Tensor",
+                               &segment_softmax)
+                           .op("tsamd::segment_softmax_bw(Tensor y, Tensor grad, Tensor? perm, Tensor seg_ptr, "
+                               "int nseg) -> Tensor",
+                               &segment_softmax_bw)
                            .op("tsamd::spspmm(Tensor rowptrA, Tensor colA, Tensor? valA, Tensor rowptrB, Tensor colB, "
                                "Tensor? valB, int N, bool with_value, Tensor? colptrA=None, "
                                "Tensor? csr2cscA=None) -> (Tensor, Tensor, Tensor)",

@@ -59,6 +59,35 @@ class _SegmentReduce(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class _SegmentSoftmax(torch.autograd.Function):
+    """y = tsamd::segment_softmax(value); backward from the saved y in one call of tsamd::segment_softmax_bw:
+    grad_value = y * (grad - sum over the segment of grad * y)."""
+
+    @staticmethod
+    def forward(ctx, value: Tensor, perm: Optional[Tensor], seg_ptr: Tensor, nseg: int):
+        y = torch.ops.tsamd.segment_softmax(value.detach(), perm, seg_ptr, nseg)
+        ctx.nseg = nseg
+        ctx.has_perm = perm is not None
+        ctx.save_for_backward(*([y, seg_ptr] + ([perm] if perm is not None else [])))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        y, seg_ptr = ctx.saved_tensors[:2]
+        perm = ctx.saved_tensors[2] if ctx.has_perm else None
+        g = torch.ops.tsamd.segment_softmax_bw(y, grad_out.contiguous(), perm, seg_ptr, ctx.nseg)
+        return g, None, None, None
+
+
+def segment_softmax(value: Tensor, perm: Optional[Tensor], seg_ptr: Tensor, nseg: int) -> Tensor:
+    """softmax over value[perm][seg_ptr[j]:seg_ptr[j+1]] for j < nseg, every trailing element of value on its own;
+    the result has the shape and the order of value.  Differentiable (once) w.r.t. value."""
+    if value.requires_grad and torch.is_grad_enabled():
+        return _SegmentSoftmax.apply(value, perm, seg_ptr, nseg)
+    return torch.ops.tsamd.segment_softmax(value, perm, seg_ptr, nseg)
+
+
 def segment_reduce(value: Tensor, perm: Optional[Tensor], seg_ptr: Tensor, nseg: int, reduce: str,
                    balanced: bool = False) -> Tensor:
     """REDUCE over value[perm][seg_ptr[j]:seg_ptr[j+1]] for j < nseg; differentiable w.r.t. value.
