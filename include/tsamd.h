@@ -109,6 +109,32 @@ int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, int64_t M, in
                                  const void *mat, const void *out, void *workspace, int64_t *layout);
 int tsamd_spmm_hot_block_min(void);
 
+/* tsamd_spmm_route (inspection and tests): what tsamd_spmm -- with arg32 != 0: tsamd_spmm_minmax_arg32 -- decides for
+ * these operands before it launches anything.  Host arithmetic only -- no HIP call, no device -- through the very
+ * functions the driver plans with.  Pointers count for their alignment and for the offsets only; mat / out / arg_out ==
+ * NULL mean "aligned", workspace == NULL leaves the four offsets 0.
+ *   route[0] family   merge instantiation: 0 nothing is launched (B * M * K == 0), 1 short rows side by side (lgG >= 3),
+ *                     2 cooperative, 3 cooperative over the hot-row table, 4 over the hot-block table, 5 / 6 = 1 / 2 with
+ *                     int32 winner ids, 7 the reference-order mode (tsamd_spmm_reference_order; nothing else is filled)
+ *   route[1] vec      elements per lane packet; route[2] slots = ceil(K / vec) packets per row; route[3] lpr lanes per
+ *                     row (a power of two <= 64); route[4] lgG (2^lgG rows side by side); route[5] ktiles (feature
+ *                     tiles of 64 packets; gridDim.y = route[17] = B * ktiles)
+ *   route[6] P, route[7] items   partitions and (row end + entry) items per partition; route[8] snap: min / max
+ *                     boundaries that fall into the first `snap` entries of a row move back to its start (0: sums)
+ *   route[9] relabel  0 no copy of mat, 2 decided on the device by the probe of `col` (1: never for this entry)
+ *   route[10] copy    what a flagged call copies: 0 nothing, 1 all of mat, 2 the hot-row table, 3 the hot-block table
+ *   route[11] fixup   1 when the fix-up kernel launches (P > 1)
+ *   route[12..15]     byte offsets in `workspace` of table ([P + 1] {row, entry}), tail_row [P], head_row [P] (int64)
+ *                     and of the probe's four int counters {-, ids with 3 low zero bits, with 6, samples}
+ *   route[16] records arg32 only: the record-writing instantiation tsamd_spmm_minmax_records takes for this shape
+ *                     (1: 97..128 features, 2: the others), 0 when its records come from the ids
+ *   route[18]         tsamd_spmm_workspace_bytes of the shape; route[19..23] are 0.
+ * TSAMD_ERR_INVALID for a negative size or route == NULL; TSAMD_ERR_UNSUPPORTED where the entry point refuses (dtype,
+ * reduce, N >= 2^32, K >= 2^31, B * ceil(K / 64) >= 65536; arg32 for sum / mean, integer types or E >= 2^31);
+ * TSAMD_ERR_WORKSPACE for a workspace off a 256-byte boundary. */
+int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, const void *mat,
+                     const void *out, const void *arg_out, int arg32, void *workspace, int64_t route[24]);
+
 int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const int64_t *col,
                const void *value, const void *mat, void *out, int64_t *arg_out,
                int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,

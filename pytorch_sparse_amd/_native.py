@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('TSAMD_LIB') or os.path.join(_HERE, 'lib', 'libtsamd.s
 # Every symbol include/tsamd.h declares (tests check that all of them resolve).
 SYMBOLS = [
     'tsamd_hip_version', 'tsamd_build_flags', 'tsamd_last_hip_error', 'tsamd_status_string',
-    'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
+    'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm_route', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
     'tsamd_spmm_partial_workspace_bytes', 'tsamd_spmm_partial',
     'tsamd_spmm_operand_cache_bytes', 'tsamd_spmm_cached_workspace_bytes', 'tsamd_spmm_cached',
     'tsamd_spmm_minmax_arg32', 'tsamd_spmm_minmax_bw_csc_arg32',
@@ -174,6 +174,28 @@ def spmm(rowptr, col, value, mat, reduce, out=None, profile=None):
             profile[:] = [float(ms[0]), float(ms[1]), float(ms[2])]
     check(st, 'tsamd_spmm')
     return out, arg
+
+
+SPMM_ROUTE_FIELDS = ('family', 'vec', 'slots', 'lpr', 'lgG', 'ktiles', 'P', 'items', 'snap', 'relabel', 'copy', 'fixup',
+                     'table_off', 'tail_row_off', 'head_row_off', 'relabel_flag_off', 'records', 'grid_y',
+                     'workspace_bytes')
+SPMM_FAMILIES = ('none', 'short', 'cooperative', 'hot_rows', 'hot_blocks', 'arg32_short', 'arg32_cooperative',
+                 'reference_order')
+
+
+def spmm_route(dtype, reduce, B, M, N, K, E, mat=0, out=0, arg_out=0, arg32=False, workspace=0):
+    """C-ABI ``tsamd_spmm_route`` (host arithmetic, no device): what the forward decides for these operands, as a dict of
+    SPMM_ROUTE_FIELDS (``family`` as one of SPMM_FAMILIES).  mat / out / arg_out / workspace: tensors or plain addresses
+    (they count for their alignment and the offsets only; 0 = aligned / no workspace).  A refusal raises TsamdError."""
+    def addr(p):
+        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
+    words = (ctypes.c_int64 * 24)()
+    st = lib().tsamd_spmm_route(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), addr(mat),
+                                addr(out), addr(arg_out), ctypes.c_int(1 if arg32 else 0), addr(workspace), words)
+    check(st, 'tsamd_spmm_route')
+    r = dict(zip(SPMM_ROUTE_FIELDS, (int(x) for x in words)))
+    r['family'] = SPMM_FAMILIES[r['family']]
+    return r
 
 
 def spmm_partial(rowptr, col, value, mat, reduce, out, arg_out=None, arg_map=None, arg_none=0, accumulate=True,

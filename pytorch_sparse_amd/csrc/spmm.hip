@@ -64,6 +64,78 @@ extern "C" int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, in
 
 extern "C" int tsamd_spmm_hot_block_min(void) { return kHotBlockMin; }
 
+// min / max with int32 ids: which record-writing instantiation tsamd_spmm_minmax_records takes for these operands
+// (0 = none: the records come from the ids)
+static bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64_t E, const void *mat, const void *out);
+
+// What a forward call decides before it launches (include/tsamd.h): spmm_entry's checks in their order, then the
+// planning functions of spmm_kernels.h and the instantiation chain of launch_spmm restated on the host.
+extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                const void *mat, const void *out, const void *arg_out, int arg32, void *workspace,
+                                int64_t route[24]) {
+  if (!route || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
+  for (int i = 0; i < 24; ++i) route[i] = 0;
+  if (reduce < TSAMD_SUM || reduce > TSAMD_MAX) return TSAMD_ERR_UNSUPPORTED;
+  if (dtype_size(dtype) == 0) return TSAMD_ERR_UNSUPPORTED;
+  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31 || B >= 65536) return TSAMD_ERR_UNSUPPORTED;
+  if (B * ceil_div(K, 64) >= 65536) return TSAMD_ERR_UNSUPPORTED;
+  const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
+  const bool floating = dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
+  if (arg32 && !minmax) return TSAMD_ERR_UNSUPPORTED;  // (tsamd_spmm_minmax_arg32)
+  if (B * M * K == 0) return TSAMD_OK;                 // family 0: nothing is launched
+  if (spmm_reference_order_on()) {
+    route[0] = 7;
+    return TSAMD_OK;
+  }
+  if ((uintptr_t)workspace % 256 != 0) return TSAMD_ERR_WORKSPACE;
+  if (arg32 && (E >= (int64_t)1 << 31 || !floating)) return TSAMD_ERR_UNSUPPORTED;
+  // pointers count for their alignment and their distances only; without a workspace the layout is that of one that
+  // starts at the first 256-byte boundary behind `mat`
+  char *base = reinterpret_cast<char *>(workspace);
+  if (!base) base = reinterpret_cast<char *>(align_up((size_t)(uintptr_t)mat + 1, 4096));
+  if (!mat) mat = base;
+  Workspace ws;
+  route[18] = (int64_t)carve(base, dtype, reduce, B, M, N, K, E, &ws);
+  const int vec = packet_width(dtype, minmax, arg32 != 0, K, mat, out, arg_out);
+  const LaneLayout lay = lane_layout(K, vec);
+  const size_t es = dtype_size(dtype);
+  const int max_vec = es <= 2 ? 4 : (int)(16 / es);
+  const int mode = ws.xperm != nullptr && vec > 1 ? 2 : 0;
+  int copy = mode != 0 ? 1 : 0;
+  if (mode == 2 && floating && !minmax && vec == max_vec && lay.lgG < 3) {  // kHotable, and launch_spmm's condition
+    void *side = nullptr;
+    int32_t side_row = 0;
+    if (hot_rows_place(ws, mat, ws.blk_word != nullptr ? N + 64 : N, (uint64_t)K * es, &side, &side_row))
+      copy = ws.blk_word != nullptr ? 3 : 2;
+  }
+  int family;
+  if (arg32) family = lay.lgG >= 3 ? 5 : 6;
+  else if (lay.lgG >= 3) family = 1;
+  else family = copy == 2 ? 3 : (copy == 3 ? 4 : 2);
+  route[0] = family;
+  route[1] = vec;
+  route[2] = lay.slots;
+  route[3] = lay.lpr;
+  route[4] = lay.lgG;
+  route[5] = lay.ktiles;
+  route[6] = ws.P;
+  route[7] = ws.items;
+  route[8] = minmax ? snap_items(ws.items) : 0;
+  route[9] = mode;
+  route[10] = copy;
+  route[11] = ws.P > 1 ? 1 : 0;
+  if (workspace) {
+    route[12] = reinterpret_cast<char *>(ws.table) - base;
+    route[13] = reinterpret_cast<char *>(ws.tail_row) - base;
+    route[14] = reinterpret_cast<char *>(ws.head_row) - base;
+    route[15] = reinterpret_cast<char *>(ws.relabel_flag) - base;
+  }
+  if (arg32 && E > 0 && vec == 4 && spmm_emits_records(dtype, B, M, K, E, mat, out))
+    route[16] = ceil_div(K, 32) == 4 && win_record_stride(K) == 8u ? 1 : 2;
+  route[17] = B * (int64_t)lay.ktiles;
+  return TSAMD_OK;
+}
+
 // ---------------------------------------------------------------------------
 // operand cache: see include/tsamd.h
 // ---------------------------------------------------------------------------

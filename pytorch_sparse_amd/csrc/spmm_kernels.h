@@ -1998,6 +1998,39 @@ bool hot_rows_place(const Workspace &ws, const void *mat, int64_t N, uint64_t ro
 template <typename T>
 constexpr int kMaxVec = sizeof(T) <= 2 ? 4 : 16 / (int)sizeof(T);
 
+// How the 64 lanes of a wave share a row of K features in packets of `vec` elements: `slots` packets per row, groups of
+// `lpr` lanes (a power of two, 64 at most) -> 2^lgG rows side by side, `ktiles` feature tiles of 64 packets on gridDim.y.
+// launch_spmm and tsamd_spmm_route (csrc/spmm.hip) both take their numbers from here.
+struct LaneLayout {
+  uint32_t slots, lpr;
+  int lgG;
+  uint32_t ktiles;
+};
+LaneLayout lane_layout(int64_t K, int vec) {
+  LaneLayout l;
+  l.slots = (uint32_t)((K + vec - 1) / vec);  // feature packets per row
+  l.lpr = l.slots >= 64 ? 64u : (1u << ilog2_ceil(l.slots));
+  l.lgG = 6 - ilog2_ceil(l.lpr);
+  l.ktiles = (l.slots + 63) / 64;
+  return l;
+}
+
+// Elements per lane packet: the widest for the type (see dispatch_spmm), halved until it divides K and every pointer the
+// kernel moves packets through is aligned to it -- arg_out (min / max only) in packets of `vec` 8-byte ids, 4-byte with
+// arg32.  spmm_entry and tsamd_spmm_route both ask here.
+[[maybe_unused]] int packet_width(int dtype, bool minmax, bool arg32, int64_t K, const void *mat, const void *out,
+                                  const void *arg_out) {
+  const size_t es = dtype_size(dtype);
+  int vec = es <= 2 ? 4 : (int)(16 / es);
+  while (vec > 1 && !((K % vec) == 0 && ((uintptr_t)mat % (vec * es)) == 0 && ((uintptr_t)out % (vec * es)) == 0 &&
+                      (!minmax || ((uintptr_t)arg_out % (vec * (arg32 ? 4 : 8))) == 0)))
+    vec >>= 1;
+  return vec;
+}
+
+// min / max and the record-writing forward: how far a partition boundary snaps back to a row start (spmm_partition_kernel)
+[[maybe_unused]] int64_t snap_items(int64_t items) { return TSAMD_RECORD_SNAP < items / 2 ? TSAMD_RECORD_SNAP : items / 2; }
+
 template <typename T, int VEC, int RED>
 int launch_spmm(const SpmmCall &c, Workspace ws) {
   const int64_t *rowptr = c.rowptr, *col = c.col;
@@ -2008,10 +2041,9 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   const bool mean = c.reduce == TSAMD_MEAN;
   hipStream_t stream = c.stream;
   hipEvent_t *ev = c.ev;
-  const uint32_t slots = (uint32_t)((K + VEC - 1) / VEC);  // feature packets per row
-  const uint32_t lpr = slots >= 64 ? 64u : (1u << ilog2_ceil(slots));
-  const int lgG = 6 - ilog2_ceil(lpr);
-  const uint32_t ktiles = (slots + 63) / 64;
+  const LaneLayout lay = lane_layout(K, VEC);
+  const uint32_t ktiles = lay.ktiles;
+  const int lgG = lay.lgG;
   const unsigned int threads = kWavesPerBlock * kWave;
 
   // hot rows: floating-point sums with full-width packets (the shapes relabel_possible admits have no others)
@@ -2242,14 +2274,14 @@ int spmm_entry(const SpmmCall &c, Launch launch) {
       ws.rec_stride = win_record_stride(K);
       ws.rec_meta = (uint32_t)ceil_div(K, 32);
       ws.rec_has_z = ((ws.rec_meta + 3u) & 3u) != 0u ? 1 : 0;
-      ws.snap = TSAMD_RECORD_SNAP < ws.items / 2 ? TSAMD_RECORD_SNAP : ws.items / 2;
+      ws.snap = snap_items(ws.items);
     }
   }
   // min / max: partition boundaries snap to row starts (spmm_partition_kernel) -- fewer cut rows, fewer carry records and
   // fix-up waves: configs[2] forward 1.024-1.029 -> 1.000 ms (bf16), 1.57 -> 1.55 (fp32), same box
   // (profiles/r06_ab_minmax_snap.jsonl).  The result does not depend on where a row is cut (no rounding in min / max);
   // sums keep their partition: theirs does, in the last bits.
-  if (minmax && ws.snap == 0) ws.snap = TSAMD_RECORD_SNAP < ws.items / 2 ? TSAMD_RECORD_SNAP : ws.items / 2;
+  if (minmax && ws.snap == 0) ws.snap = snap_items(ws.items);
   if (c.partial) {
     if (reduce == TSAMD_MEAN && c.deg_rowptr == nullptr) return TSAMD_ERR_INVALID;
     ws.partial = 1;
@@ -2265,13 +2297,7 @@ int spmm_entry(const SpmmCall &c, Launch launch) {
     ws.rec_meta = (uint32_t)ceil_div(K, 32);
     ws.rec_has_z = (ws.rec_meta <= 32u && ((ws.rec_meta + 3u) & 3u) != 0u) ? 1 : 0;  // a padding word behind (id, value)
   }
-  const size_t es = dtype_size(dtype);
-  int vec = es <= 2 ? 4 : (int)(16 / es);  // widest packet for the type (see dispatch_spmm)
-  while (vec > 1 && !((K % vec) == 0 && ((uintptr_t)c.mat % (vec * es)) == 0 &&
-                      ((uintptr_t)c.out % (vec * es)) == 0 &&
-                      (!minmax || ((uintptr_t)c.arg_out % (vec * (c.arg32 ? 4 : 8))) == 0)))
-    vec >>= 1;
-  return launch(vec, ws);
+  return launch(packet_width(dtype, minmax, c.arg32, K, c.mat, c.out, c.arg_out), ws);
 }
 
 }  // namespace
