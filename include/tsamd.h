@@ -738,6 +738,13 @@ enum {
   TSAMD_KEEP_MASK_COL = 4,
   TSAMD_KEEP_COL_MAPPED = 5
 };
+/* tsamd_index_route: host arithmetic only.  The sizes at which the index kernels (exclusive scan, ind2ptr /
+ * ptr2ind, select, filter) change route: out[0] = entries per scan tile (one more scan level for every factor
+ * of it); out[1] = entries per tile of ptr2ind / select_fill, also the most segments a tile may intersect and
+ * still stage their pointers in LDS (more: it searches global memory in place); out[2] = entries per tile of
+ * filter_count / filter_write; out[3] = entries per slice of such a tile; out[4] = ind2ptr: a boundary whose
+ * row pointers span this many rows or more is resolved by the long-run kernel; the rest 0. */
+int tsamd_index_route(int64_t out[8]);
 size_t tsamd_select_workspace_bytes(int64_t K);
 int tsamd_select_plan(const int64_t *ptr, int64_t S, const int64_t *idx, int64_t K,
                       int64_t *out_ptr, int64_t *info, void *workspace, size_t workspace_bytes,

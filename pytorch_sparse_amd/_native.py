@@ -34,7 +34,7 @@ SYMBOLS = [
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
     'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
     'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
-    'tsamd_select_workspace_bytes', 'tsamd_select_plan', 'tsamd_select_fill',
+    'tsamd_index_route', 'tsamd_select_workspace_bytes', 'tsamd_select_plan', 'tsamd_select_fill',
     'tsamd_filter_workspace_bytes', 'tsamd_filter_plan', 'tsamd_filter_apply',
     'tsamd_filter_tiles_workspace_bytes', 'tsamd_filter_count', 'tsamd_filter_write',
     'tsamd_scatter_rows',
@@ -94,6 +94,10 @@ def lib():
         L.tsamd_spmm_minmax_records_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_segment_softmax_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_select_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_filter_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_filter_tiles_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_num_diag.restype = ctypes.c_int64
         _lib = L
     return _lib
 

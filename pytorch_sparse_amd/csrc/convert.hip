@@ -8,10 +8,9 @@ namespace tsamd {
 namespace {
 
 // Thread t in [0, E] owns the boundary between ind[t-1] and ind[t] and fills every row pointer
-// that falls into it (empty rows make the run longer than 1).  Runs of more than kLongRun empty rows
-// are left at the -1 the output was pre-set to and resolved by ind2ptr_long_kernel, one thread per
+// that falls into it (empty rows make the run longer than 1).  Runs of more than kLongRun (expand.h) empty
+// rows are left at the -1 the output was pre-set to and resolved by ind2ptr_long_kernel, one thread per
 // row pointer with a binary search: a single thread filling a 32 M-row gap took 840 ms.
-constexpr int64_t kLongRun = 1024;
 
 __global__ void ind2ptr_kernel(const int64_t *__restrict__ ind, int64_t *__restrict__ out,
                                int64_t M, int64_t E) {

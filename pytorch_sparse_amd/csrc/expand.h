@@ -11,6 +11,9 @@ namespace tsamd {
 
 constexpr int kExpandTile = 2048;
 
+// ind2ptr (convert.hip): a boundary whose row pointers span kLongRun rows or more is left to the long-run kernel
+constexpr int64_t kLongRun = 1024;
+
 // last i in [0, n) with ptr[i] <= e; needs ptr non-decreasing and ptr[0] <= e.  Among equal
 // pointers (empty segments) this is the last one, i.e. the segment that really holds entry e.
 __device__ inline int64_t segment_of(const int64_t *__restrict__ ptr, int64_t n, int64_t e) {

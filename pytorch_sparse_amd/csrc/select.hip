@@ -281,7 +281,8 @@ __global__ void set_diag_fill_kernel(const int64_t *__restrict__ pos, const int6
 // input order (wave ballots + a 4-entry LDS prefix per 256-entry slice).  Traffic: the predicate's
 // inputs twice + the outputs once, against flags + scan + positions (5 x 8 B per entry) before.
 constexpr int kFilterTile = 2048;
-constexpr int kFilterSlices = kFilterTile / 256;
+constexpr int kFilterSlice = 256;  // entries per pass of the workgroup: one per thread
+constexpr int kFilterSlices = kFilterTile / kFilterSlice;
 
 __global__ __launch_bounds__(256) void filter_count_kernel(int pred, const int64_t *__restrict__ row,
                                                            const int64_t *__restrict__ col,
@@ -380,6 +381,18 @@ __global__ __launch_bounds__(256) void filter_write_kernel(
 }  // namespace tsamd
 
 using namespace tsamd;
+
+// The sizes at which the index kernels change route (tests/index_reference.py computes its census from them).
+extern "C" int tsamd_index_route(int64_t out[8]) {
+  if (!out) return TSAMD_ERR_INVALID;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[0] = kScanTile;     // entries per scan tile; one more level of the scan for every factor of it
+  out[1] = kExpandTile;   // entries per tile of ptr2ind / select_fill = the most segments a tile stages in LDS
+  out[2] = kFilterTile;   // entries per tile of filter_count / filter_write
+  out[3] = kFilterSlice;  // entries per slice of a filter tile (four waves of 64)
+  out[4] = kLongRun;      // ind2ptr: a boundary over this many rows or more goes to the long-run kernel
+  return TSAMD_OK;
+}
 
 extern "C" size_t tsamd_select_workspace_bytes(int64_t K) { return scan_workspace_bytes(K + 1); }
 
@@ -584,6 +597,7 @@ extern "C" int tsamd_filter_write(int pred, const int64_t *row, const int64_t *c
                                   int64_t *col_out, int64_t *src_out, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (n < 0 || !workspace) return TSAMD_ERR_INVALID;
+  if (pred < TSAMD_KEEP_COL_RANGE || pred > TSAMD_KEEP_COL_MAPPED) return TSAMD_ERR_UNSUPPORTED;  // as tsamd_filter_count
   if (n == 0) return TSAMD_OK;
   if (!filter_args_ok(pred, row, col, mask, map, n) || (row_out && !row) || (col_out && !col))
     return TSAMD_ERR_INVALID;
