@@ -408,6 +408,39 @@ int tsamd_spmm_minmax_bw_csc_records(int dtype, const int64_t *rowptr, const int
                                      void *grad_value, void *grad_mat, int64_t B, int64_t M, int64_t N, int64_t K,
                                      int64_t E, void *workspace, size_t workspace_bytes, void *stream);
 
+/* tsamd_spmm_minmax_bw_route (inspection and tests): what a min / max backward call decides before it launches anything.
+ * Host arithmetic only -- no HIP call, no device -- through the very plan functions the four entries run.
+ *   winners   0 int64 ids (tsamd_spmm_minmax_bw_csc), 1 int32 ids (_arg32), 2 records (_records), 3 none: the bare
+ *             scatter entry tsamd_spmm_minmax_bw
+ *   want_value / want_mat   whether grad_value / grad_mat are asked for
+ *   mat, grad_out, grad_mat count for their alignment only (NULL: aligned); every array the query does not take is
+ *             taken as present, the workspace as large enough and 256-byte aligned.
+ *   route[0]  status  the TSAMD_* status the entry answers; when it is not TSAMD_OK the other words are 0
+ *   route[1]  value   how grad_value is made: 0 not at all, 1 zero fill, 2 masked SDDMM over the records, 3 the
+ *                     row-parallel kernel (spmm_minmax_bw_kernel<.., GVAL>: LDS sums)
+ *   route[2]  sddmm   masked SDDMM only: 1 spmm_value_bw_masked_kernel (pipelined, <= 64 packets per row),
+ *                     2 spmm_value_bw_kernel<.., true>; route[3] its lgG (2^lgG entries side by side)
+ *   route[4]  mat     how grad_mat is made: 0 not at all, 1 zero fill, 2 pull (masked sum), 3 scatter (atomics)
+ *   route[5]  write_records  pull only: 1 when minmax_winrec_kernel writes the records first (winners 0 and 1)
+ *   route[6..8] W, S, has_z  pull only: mask words and stride of a record in 32-bit words, and whether the masked sum
+ *                     reads word W + 3 as the non-zero-word bitmap (the padding leaves it and W <= 32)
+ *   route[9]  lgG, route[10] cap   scatter / row-parallel kernel: 2^lgG rows side by side, LDS sums per row and pass
+ *                     (rows of more than `cap` entries take several passes)
+ *   route[11] packed  scatter of grad_mat: 0 per-element atomics (fp32, fp64, or the fp32 shadow), 1 packed f16 / bf16
+ *                     atomics whose word mates are lanes (2j, 2j + 1) of a row (even K), 2 packed with the half chosen by
+ *                     the element's index (odd K)
+ *   route[12] shadow  1 when f16 / bf16 grad_mat goes through an fp32 shadow and narrow_from_f32_kernel (grad_mat not
+ *                     4-byte aligned, or B * N * K odd); route[13] the workspace bytes it needs
+ *   route[14] items, route[15] P, route[16] fixup, route[17] relabel, route[18] copy, route[19] vec, route[20] lpr,
+ *   route[21] lgG, route[22] ktiles, route[24] family   pull only: the words of tsamd_spmm_route for the masked sum --
+ *                     the SUM of the transposed problem (N rows, M columns, `grad_out` gathered, `grad_mat` written)
+ *                     with relabel 1 in place of 2: no probe of the ids, the copy of grad_out wherever it is possible
+ *   route[23]         pull only: the entry's workspace bytes; the other words are 0.
+ * TSAMD_ERR_INVALID for route == NULL or winners outside 0 .. 3, TSAMD_OK otherwise. */
+int tsamd_spmm_minmax_bw_route(int winners, int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                               int want_value, int want_mat, const void *mat, const void *grad_out, const void *grad_mat,
+                               int64_t route[32]);
+
 /* ------------------------------------------------------------------------ *
  * COO row ids <-> CSR row pointer.  Replace ind2ptr_cuda / ptr2ind_cuda
  * (csrc/cuda/convert_cuda.cu:26-67, csrc/cpu/convert_cpu.cpp:7-57).

@@ -25,7 +25,7 @@ SYMBOLS = [
     'tsamd_spmm_coo_small_supported', 'tsamd_spmm_coo_small',
     'tsamd_spmm_value_bw',
     'tsamd_spmm_minmax_bw_workspace_bytes', 'tsamd_spmm_minmax_bw',
-    'tsamd_spmm_minmax_bw_csc_workspace_bytes', 'tsamd_spmm_minmax_bw_csc',
+    'tsamd_spmm_minmax_bw_csc_workspace_bytes', 'tsamd_spmm_minmax_bw_csc', 'tsamd_spmm_minmax_bw_route',
     'tsamd_ind2ptr', 'tsamd_ptr2ind',
     'tsamd_coo_order', 'tsamd_coo_check', 'tsamd_sort_rank_mode', 'tsamd_sort_route', 'tsamd_sort_coalesce_workspace_bytes', 'tsamd_sort_coalesce', 'tsamd_sort_coalesce_reduce', 'tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo', 'tsamd_sort_coo_auto', 'tsamd_sort_coo_probed', 'tsamd_sort_coo_values',
     'tsamd_coalesce_workspace_bytes', 'tsamd_coalesce_index', 'tsamd_segment_reduce',
@@ -296,9 +296,57 @@ def spspmm_value_bw(side, segptr, segind, listptr, list_ind, list_val, rowptrC, 
     return grad, P
 
 
-def spmm_minmax_bw(rowptr, col, value, mat, grad_out, arg_out, want_value=True, want_mat=True):
+def _given(buf, numel, dtype, what):
+    """A caller's output buffer (tests fill it with a sentinel first): contiguous, of the right type and size."""
+    if buf.dtype != dtype or buf.numel() != numel or not buf.is_contiguous():
+        raise TsamdError('%s: the given buffer must be contiguous, %s, %d elements' % (what, dtype, numel))
+    return buf
+
+
+def _out_buffer(given, wanted, numel, mat, like=False):
+    if not wanted:
+        return None
+    if given is not None:
+        return _given(given, numel, mat.dtype, 'output')
+    return torch.empty_like(mat) if like else torch.empty(numel, dtype=mat.dtype, device=mat.device)
+
+
+MINMAX_BW_ROUTE_FIELDS = ('status', 'value', 'sddmm', 'sddmm_lgG', 'mat', 'write_records', 'W', 'S', 'has_z', 'lgG', 'cap',
+                          'packed', 'shadow', 'shadow_bytes', 'items', 'P', 'fixup', 'relabel', 'copy', 'vec', 'lpr',
+                          'sum_lgG', 'ktiles', 'workspace_bytes', 'family')
+MINMAX_BW_WINNERS = ('ids64', 'ids32', 'records', 'none')
+MINMAX_BW_VALUE = ('none', 'zero', 'masked_sddmm', 'row_parallel')
+MINMAX_BW_SDDMM = ('none', 'pipelined', 'round4')
+MINMAX_BW_MAT = ('none', 'zero', 'pull', 'scatter')
+MINMAX_BW_PACKED = ('plain', 'merge_pairs', 'idx_parity')
+
+
+def spmm_minmax_bw_route(winners, dtype, B, M, N, K, E, want_value=False, want_mat=True, mat=0, grad_out=0, grad_mat=0):
+    """C-ABI ``tsamd_spmm_minmax_bw_route`` (host arithmetic, no device): what the min / max backward decides for these
+    operands, as a dict of MINMAX_BW_ROUTE_FIELDS.  winners: one of MINMAX_BW_WINNERS ('none': the bare scatter entry);
+    mat / grad_out / grad_mat: tensors or plain addresses (their alignment counts; 0 = aligned).  ``status`` is the
+    entry's answer as an int (0 = OK; the other fields are then filled), ``value`` / ``sddmm`` / ``mat`` / ``packed`` are
+    names, ``family`` one of SPMM_FAMILIES."""
+    def addr(p):
+        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
+    words = (ctypes.c_int64 * 32)()
+    dt = dtype if isinstance(dtype, int) else dtype_code(dtype)
+    st = lib().tsamd_spmm_minmax_bw_route(MINMAX_BW_WINNERS.index(winners), dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E),
+                                          ctypes.c_int(1 if want_value else 0), ctypes.c_int(1 if want_mat else 0),
+                                          addr(mat), addr(grad_out), addr(grad_mat), words)
+    check(st, 'tsamd_spmm_minmax_bw_route')
+    r = dict(zip(MINMAX_BW_ROUTE_FIELDS, (int(x) for x in words)))
+    r['value'] = MINMAX_BW_VALUE[r['value']]
+    r['sddmm'] = MINMAX_BW_SDDMM[r['sddmm']]
+    r['mat'] = MINMAX_BW_MAT[r['mat']]
+    r['packed'] = MINMAX_BW_PACKED[r['packed']]
+    r['family'] = SPMM_FAMILIES[r['family']]
+    return r
+
+
+def spmm_minmax_bw(rowptr, col, value, mat, grad_out, arg_out, want_value=True, want_mat=True, gv=None, gm=None):
     """C-ABI ``tsamd_spmm_minmax_bw``: (grad_value or None, grad_mat or None).  ``rowptr`` may be
-    None when ``want_value`` is False."""
+    None when ``want_value`` is False.  gv / gm: buffers to write into instead of fresh ones."""
     require_gpu(rowptr, col, value, mat, grad_out, arg_out)
     dt = dtype_code(mat.dtype)
     mat, grad_out, arg_out = mat.contiguous(), grad_out.contiguous(), arg_out.contiguous()
@@ -306,10 +354,12 @@ def spmm_minmax_bw(rowptr, col, value, mat, grad_out, arg_out, want_value=True, 
     N, K = mat.size(-2), mat.size(-1)
     M = grad_out.size(-2)
     B = mat.numel() // (N * K) if N * K > 0 else 1
-    gv = torch.empty(E, dtype=mat.dtype, device=mat.device) if want_value else None
-    gm = torch.empty_like(mat) if want_mat else None
+    gv = _out_buffer(gv, want_value, E, mat)
+    gm = _out_buffer(gm, want_mat, mat.numel(), mat, like=True)
     L = lib()
     nb = L.tsamd_spmm_minmax_bw_workspace_bytes(dt, _i64(B), _i64(N), _i64(K), _i64(E))
+    if gm is not None and gm.data_ptr() % 4 != 0:  # a misaligned f16 / bf16 grad_mat takes the fp32 shadow at any count
+        nb = max(nb, 4 * B * N * K + 256)
     ws = workspace(nb, mat.device)
     with torch.cuda.device(mat.device):
         st = L.tsamd_spmm_minmax_bw(dt, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(grad_out),
@@ -344,9 +394,9 @@ def spmm_minmax_arg32(rowptr, col, value, mat, reduce):
 
 
 def spmm_minmax_bw_csc(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2csc, row, want_value=True,
-                       want_mat=True):
+                       want_mat=True, gv=None, gm=None):
     """C-ABI ``tsamd_spmm_minmax_bw_csc`` (pull formulation over the CSC arrays, no atomics):
-    (grad_value or None, grad_mat or None)."""
+    (grad_value or None, grad_mat or None).  gv / gm: buffers to write into instead of fresh ones."""
     require_gpu(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2csc, row)
     dt = dtype_code(mat.dtype)
     mat, grad_out, arg_out = mat.contiguous(), grad_out.contiguous(), arg_out.contiguous()
@@ -354,8 +404,8 @@ def spmm_minmax_bw_csc(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2c
     N, K = mat.size(-2), mat.size(-1)
     M = grad_out.size(-2)
     B = mat.numel() // (N * K) if N * K > 0 else 1
-    gv = torch.empty(E, dtype=mat.dtype, device=mat.device) if want_value else None
-    gm = torch.empty_like(mat) if want_mat else None
+    gv = _out_buffer(gv, want_value, E, mat)
+    gm = _out_buffer(gm, want_mat, mat.numel(), mat, like=True)
     L = lib()
     nb = L.tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E))
     ws = workspace(nb, mat.device)
@@ -369,7 +419,7 @@ def spmm_minmax_bw_csc(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2c
     return gv, gm
 
 
-def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False):
+def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False, out=None, rec=None):
     """C-ABI ``tsamd_spmm_minmax_records``: min / max forward that leaves the winner records of the pull backward
     -> (out, records as int32 words).  zero: the buffer starts as zeros (padding words of a record are never written)."""
     require_gpu(rowptr, col, value, mat, row)
@@ -379,10 +429,16 @@ def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False):
     B = mat.numel() // (N * K) if N * K > 0 else 1
     red = REDUCES[reduce]
     dt = dtype_code(mat.dtype)
-    out = torch.empty(list(mat.shape[:-2]) + [M, K], dtype=mat.dtype, device=mat.device)
+    if out is None:
+        out = torch.empty(list(mat.shape[:-2]) + [M, K], dtype=mat.dtype, device=mat.device)
+    else:
+        _given(out, B * M * K, mat.dtype, 'out')
     L = lib()
-    rec = (torch.zeros if zero else torch.empty)(L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4,
-                                                 dtype=torch.int32, device=mat.device)
+    nrec = L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4
+    if rec is None:
+        rec = (torch.zeros if zero else torch.empty)(nrec, dtype=torch.int32, device=mat.device)
+    else:
+        _given(rec, nrec, torch.int32, 'records')
     ws = workspace(L.tsamd_spmm_minmax_records_workspace_bytes(dt, red, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)),
                    mat.device)
     with torch.cuda.device(mat.device):
@@ -393,15 +449,19 @@ def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False):
     return out, rec
 
 
-def spmm_minmax_winrec(row, value, arg32, K):
+def spmm_minmax_winrec(row, value, arg32, K, rec=None, dtype=None):
     """C-ABI ``tsamd_spmm_minmax_winrec``: the winner records of int32 winner ids [B, M, K] -> int32 words."""
     require_gpu(row, value, arg32)
     arg32 = arg32.contiguous()
     E, M = row.numel(), arg32.size(-2)
     B = arg32.numel() // (M * K) if M * K > 0 else 1
     L = lib()
-    rec = torch.zeros(L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4, dtype=torch.int32, device=row.device)
-    dt = dtype_code(value.dtype) if value is not None else 0
+    nrec = L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4
+    if rec is None:
+        rec = torch.zeros(nrec, dtype=torch.int32, device=row.device)
+    else:
+        _given(rec, nrec, torch.int32, 'records')
+    dt = dtype_code(value.dtype) if value is not None else (dtype_code(dtype) if dtype is not None else 0)
     with torch.cuda.device(row.device):
         st = L.tsamd_spmm_minmax_winrec(dt, _ptr(row), _ptr(value), _ptr(arg32), _ptr(rec), _i64(B), _i64(M), _i64(K),
                                         _i64(E), stream_ptr(row.device))
@@ -409,7 +469,8 @@ def spmm_minmax_winrec(row, value, arg32, K):
     return rec
 
 
-def spmm_minmax_bw_csc_records(rowptr, col, has_value, mat, grad_out, records, colptr, csr2csc, row, want_value=False):
+def spmm_minmax_bw_csc_records(rowptr, col, has_value, mat, grad_out, records, colptr, csr2csc, row, want_value=False,
+                               gv=None, gm=None):
     """C-ABI ``tsamd_spmm_minmax_bw_csc_records``: the pull backward on records -> (grad_value or None, grad_mat)."""
     require_gpu(rowptr, col, mat, grad_out, records, colptr, csr2csc, row)
     dt = dtype_code(mat.dtype)
@@ -418,8 +479,8 @@ def spmm_minmax_bw_csc_records(rowptr, col, has_value, mat, grad_out, records, c
     N, K = mat.size(-2), mat.size(-1)
     M = grad_out.size(-2)
     B = mat.numel() // (N * K) if N * K > 0 else 1
-    gv = torch.empty(E, dtype=mat.dtype, device=mat.device) if want_value else None
-    gm = torch.empty_like(mat)
+    gv = _out_buffer(gv, want_value, E, mat)
+    gm = _out_buffer(gm, True, mat.numel(), mat, like=True)
     L = lib()
     ws = workspace(L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes(dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)),
                    mat.device)

@@ -568,6 +568,13 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
       csr2csc = s[6].contiguous();
       row = s[7].contiguous();
     }
+    // The records route makes grad_value only as the masked SDDMM (16-byte packets) and has no ids to fall back on: an
+    // operand that is contiguous but not 16-byte aligned (a view into a larger buffer) is copied into a fresh, aligned
+    // allocation first.  The forward's gate has already kept rows that are no whole packets away.
+    if (records && want_value) {
+      if ((uintptr_t)grad_out.data_ptr() % 16 != 0) grad_out = grad_out.clone(at::MemoryFormat::Contiguous);
+      if ((uintptr_t)mat.data_ptr() % 16 != 0) mat = mat.clone(at::MemoryFormat::Contiguous);
+    }
     const bool narrow = arg_out.scalar_type() == at::kInt;
     const bool fits32 = N < ((int64_t)1 << 32) && M < ((int64_t)1 << 32) && E < ((int64_t)1 << 32) && K < ((int64_t)1 << 31);
     const bool packets16 = row.defined() && row.data_ptr() != nullptr && (K * (int64_t)mat.element_size()) % 16 == 0 &&

@@ -70,9 +70,11 @@ static bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64
 
 // What a forward call decides before it launches (include/tsamd.h): spmm_entry's checks in their order, then the
 // planning functions of spmm_kernels.h and the instantiation chain of launch_spmm restated on the host.
-extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
-                                const void *mat, const void *out, const void *arg_out, int arg32, void *workspace,
-                                int64_t route[24]) {
+// `masked`: the call is spmm_masked_sum's (the pull of the min / max backward) -- no reference-order mode, no probe of
+// `col` (launch_spmm turns relabel mode 2 into 1 there) and hence no hot table.
+int tsamd::spmm_route_words(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, const void *mat,
+                            const void *out, const void *arg_out, int arg32, void *workspace, bool masked,
+                            int64_t route[24]) {
   if (!route || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
   for (int i = 0; i < 24; ++i) route[i] = 0;
   if (reduce < TSAMD_SUM || reduce > TSAMD_MAX) return TSAMD_ERR_UNSUPPORTED;
@@ -83,7 +85,7 @@ extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int
   const bool floating = dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
   if (arg32 && !minmax) return TSAMD_ERR_UNSUPPORTED;  // (tsamd_spmm_minmax_arg32)
   if (B * M * K == 0) return TSAMD_OK;                 // family 0: nothing is launched
-  if (spmm_reference_order_on()) {
+  if (spmm_reference_order_on() && !masked) {
     route[0] = 7;
     return TSAMD_OK;
   }
@@ -100,7 +102,8 @@ extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int
   const LaneLayout lay = lane_layout(K, vec);
   const size_t es = dtype_size(dtype);
   const int max_vec = es <= 2 ? 4 : (int)(16 / es);
-  const int mode = ws.xperm != nullptr && vec > 1 ? 2 : 0;
+  int mode = ws.xperm != nullptr && vec > 1 ? 2 : 0;
+  if (mode == 2 && masked) mode = 1;
   int copy = mode != 0 ? 1 : 0;
   if (mode == 2 && floating && !minmax && vec == max_vec && lay.lgG < 3) {  // kHotable, and launch_spmm's condition
     void *side = nullptr;
@@ -134,6 +137,12 @@ extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int
     route[16] = ceil_div(K, 32) == 4 && win_record_stride(K) == 8u ? 1 : 2;
   route[17] = B * (int64_t)lay.ktiles;
   return TSAMD_OK;
+}
+
+extern "C" int tsamd_spmm_route(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                const void *mat, const void *out, const void *arg_out, int arg32, void *workspace,
+                                int64_t route[24]) {
+  return spmm_route_words(dtype, reduce, B, M, N, K, E, mat, out, arg_out, arg32, workspace, false, route);
 }
 
 // ---------------------------------------------------------------------------

@@ -344,6 +344,10 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_value_bw_masked_ke
 constexpr int kBwRows = 2;     // row groups in flight per wave
 constexpr int kBwTiles = 2;    // 64-feature tiles in flight per row
 constexpr int kBwSlots = 512;  // LDS accumulator slots per wave (grad_value)
+// LDS slots per row in flight, and whether the two lanes of an aligned 4-byte word are mates of one packed atomic: the
+// kernel and tsamd_spmm_minmax_bw_route both ask here.
+__host__ __device__ constexpr int bw_cap(int lgG) { return kBwSlots / kBwRows >> lgG; }
+__host__ __device__ constexpr bool bw_merge_pairs(bool packed, uint32_t K) { return packed && (K & 1u) == 0; }
 
 typedef short short2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -396,9 +400,9 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void spmm_minmax_bw_kernel(
   const int g = lane >> (6 - lgG);
   const int kl = lane & (lpr - 1);
   const uint32_t ktiles = (K + (uint32_t)lpr - 1) / (uint32_t)lpr;
-  const int cap = kBwSlots / kBwRows >> lgG;  // LDS slots per row in flight
+  const int cap = bw_cap(lgG);  // LDS slots per row in flight
   const int64_t unit = (int64_t)blockIdx.x * kWavesPerBlock + wib;
-  const bool merge_pairs = kPacked && (K & 1u) == 0;  // word mates = lanes (2j, 2j+1) of one row
+  const bool merge_pairs = bw_merge_pairs(kPacked, K);  // word mates = lanes (2j, 2j+1) of one row
 
   int64_t m[kBwRows], rs[kBwRows], deg[kBwRows];
   bool ok[kBwRows];
@@ -711,16 +715,29 @@ int launch_value_bw(const int64_t *row, const int64_t *rowptr, const int64_t *co
   return TSAMD_OK;
 }
 
+// Which masked SDDMM serves rows of K elements of `es` bytes: the pipelined kernel takes one 16-byte packet per lane and
+// step (at most 64 packets per row), the round-4 kernel the wider rows.  launch_value_bw_masked and
+// tsamd_spmm_minmax_bw_route both ask here.
+struct MaskedSddmmPlan {
+  bool pipelined;
+  int lgG;
+};
+MaskedSddmmPlan plan_masked_sddmm(size_t es, int64_t K, uint32_t rec_stride) {
+  const int64_t vec = 16 / (int64_t)es;
+  const uint32_t slots = (uint32_t)(K / vec);
+  return {slots <= 64u && K % vec == 0 && (uint64_t)kWave * rec_stride < (1ull << 32), lg_groups(slots)};
+}
+
 // grad_value of the min/max backward from the winner records (16-byte packets required)
 template <typename T>
 int launch_value_bw_masked(const int64_t *row, const int64_t *rowptr, const int64_t *col, const T *mat,
                            const T *grad, T *out, const uint32_t *rec, uint32_t rec_stride, int64_t B,
                            int64_t M, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
   constexpr int VEC = 16 / (int)sizeof(T);
-  const uint32_t slots = (uint32_t)(K / VEC);
-  const int lgG = lg_groups(slots);
+  const MaskedSddmmPlan plan = plan_masked_sddmm(sizeof(T), K, rec_stride);
+  const int lgG = plan.lgG;
   const unsigned int blocks = entry_blocks(E);
-  if (slots <= 64u && K % VEC == 0 && (uint64_t)kWave * rec_stride < (1ull << 32)) {
+  if (plan.pipelined) {
     hipLaunchKernelGGL((spmm_value_bw_masked_kernel<T>), dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream, row,
                        rowptr, col, mat, grad, out, B, M, N, (uint32_t)K, E, lgG, rec, rec_stride);
   } else {
@@ -779,9 +796,8 @@ int write_winrec(int dtype, const int64_t *row, const void *value, const Winners
 template <typename T, typename TM>
 int launch_minmax_bw(const int64_t *rowptr, const int64_t *col, const void *value, const void *mat,
                      const void *grad_out, const int64_t *arg_out, void *gval, TM *gmat, int64_t B,
-                     int64_t M, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
+                     int64_t M, int64_t N, int64_t K, int64_t E, int lgG, hipStream_t stream) {
   if (B * M * K == 0) return TSAMD_OK;
-  const int lgG = lg_groups((uint32_t)K);
   const int64_t rows_per_wave = (int64_t)kBwRows << lgG;
   const unsigned int blocks = (unsigned int)ceil_div(ceil_div(M, rows_per_wave), kWavesPerBlock);
   const T *v = reinterpret_cast<const T *>(value), *x = reinterpret_cast<const T *>(mat),
@@ -806,6 +822,60 @@ int narrow_out(const float *src, void *dst, int64_t n, hipStream_t stream) {
                      stream, src, reinterpret_cast<T *>(dst), n);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
+}
+
+// What tsamd_spmm_minmax_bw answers and launches, from its arguments alone (no HIP call in here); the entry carries it
+// out and tsamd_spmm_minmax_bw_route reports it.  Pointers count for being NULL or not; grad_mat for its alignment too.
+struct MinMaxScatterPlan {
+  int status = TSAMD_OK;
+  enum Value { NoValue, ZeroValue, RowParallel } value = NoValue;
+  enum Mat { NoMat, ZeroMat, Scatter } mat = NoMat;
+  // f16 / bf16 grad_mat: packed atomics on the final buffer where they can work; the fp32 shadow otherwise
+  // (round once; costs a memset, fp32 atomics on twice as many 64-byte segments and a narrowing pass over [B,N,K]).
+  bool shadow = false;
+  size_t shadow_bytes = 0;  // workspace the shadow needs
+  bool packed = false, merge_pairs = false;
+  int lgG = 0, cap = 0;
+};
+
+// the fp32 shadow of a narrow grad_mat: packed atomics need whole, aligned 4-byte words inside the buffer
+bool scatter_needs_shadow(int dtype, const void *grad_mat, int64_t nmat) {
+  const bool narrow = dtype == TSAMD_F16 || dtype == TSAMD_BF16;
+  return narrow && (((uintptr_t)grad_mat % 4) != 0 || (nmat % 2) != 0);
+}
+
+MinMaxScatterPlan plan_minmax_scatter(int dtype, const void *rowptr, const void *col, const void *mat, const void *grad_out,
+                                      const void *arg_out, const void *grad_value, const void *grad_mat, int64_t B, int64_t M,
+                                      int64_t N, int64_t K, int64_t E, const void *workspace, size_t workspace_bytes) {
+  MinMaxScatterPlan p;
+  auto answer = [&p](int status) { return p.status = status, p; };
+  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return answer(TSAMD_ERR_INVALID);
+  if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16)
+    return answer(TSAMD_ERR_UNSUPPORTED);
+  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31) return answer(TSAMD_ERR_UNSUPPORTED);
+  const int64_t total = B * M * K;
+  if (total > 0 && (!col || !mat || !grad_out || !arg_out)) return answer(TSAMD_ERR_INVALID);
+  if (grad_value && E > 0 && !rowptr) return answer(TSAMD_ERR_INVALID);  // grad_value is laid out by rows
+  const int64_t nmat = B * N * K;
+  if (total == 0 || (!grad_value && !grad_mat)) {  // nothing to add up: zero fills, straight into the outputs
+    if (grad_mat && nmat > 0) p.mat = MinMaxScatterPlan::ZeroMat;
+    if (grad_value && E > 0) p.value = MinMaxScatterPlan::ZeroValue;
+    return p;
+  }
+  p.lgG = lg_groups((uint32_t)K);
+  p.cap = bw_cap(p.lgG);
+  if (grad_value) p.value = MinMaxScatterPlan::RowParallel;
+  if (grad_mat) {
+    p.mat = MinMaxScatterPlan::Scatter;
+    p.shadow = scatter_needs_shadow(dtype, grad_mat, nmat);
+    if (p.shadow) {
+      p.shadow_bytes = align_up(sizeof(float) * (size_t)nmat, 256);
+      if (!workspace || workspace_bytes < p.shadow_bytes) return answer(TSAMD_ERR_WORKSPACE);
+    }
+    p.packed = (dtype == TSAMD_F16 || dtype == TSAMD_BF16) && !p.shadow;
+    p.merge_pairs = bw_merge_pairs(p.packed, (uint32_t)K);
+  }
+  return p;
 }
 
 }  // namespace
@@ -839,15 +909,11 @@ extern "C" int tsamd_spmm_value_bw(int dtype, int reduce, const int64_t *row,
   });
 }
 
-// f16 / bf16 grad_mat: packed atomics on the final buffer where they can work; the fp32 shadow otherwise
-// (round once; costs a memset, fp32 atomics on twice as many 64-byte segments and a narrowing pass over [B,N,K]).
+// the fp32 shadow's bytes for a grad_mat that starts on a 4-byte boundary (a misaligned one takes it at any count)
 extern "C" size_t tsamd_spmm_minmax_bw_workspace_bytes(int dtype, int64_t B, int64_t N, int64_t K,
                                                        int64_t E) {
   (void)E;
-  const bool narrow = dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-  // packed atomics need whole 4-byte words inside the buffer: an odd element count takes the shadow
-  if (narrow && ((B * N * K) % 2) != 0)
-    return align_up(sizeof(float) * (size_t)(B * N * K), 256);
+  if (scatter_needs_shadow(dtype, nullptr, B * N * K)) return align_up(sizeof(float) * (size_t)(B * N * K), 256);
   return 0;
 }
 
@@ -857,40 +923,30 @@ extern "C" int tsamd_spmm_minmax_bw(int dtype, const int64_t *rowptr, const int6
                                     int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                                     void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16)
-    return TSAMD_ERR_UNSUPPORTED;
-  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31) return TSAMD_ERR_UNSUPPORTED;
-  const int64_t total = B * M * K;
-  if (total > 0 && (!col || !mat || !grad_out || !arg_out)) return TSAMD_ERR_INVALID;
-  if (grad_value && E > 0 && !rowptr) return TSAMD_ERR_INVALID;  // grad_value is laid out by rows
+  const MinMaxScatterPlan p = plan_minmax_scatter(dtype, rowptr, col, mat, grad_out, arg_out, grad_value, grad_mat, B, M, N,
+                                                  K, E, workspace, workspace_bytes);
+  if (p.status != TSAMD_OK) return p.status;
   const size_t es = dtype_size(dtype);
   const size_t nmat = (size_t)(B * N * K);
-  const bool narrow = dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-  // packed atomics work on aligned 4-byte words inside the buffer
-  const bool shadow = narrow && grad_mat && (((uintptr_t)grad_mat % 4) != 0 || (nmat % 2) != 0);
+  if (p.value == MinMaxScatterPlan::ZeroValue) TSAMD_HIP_TRY(hipMemsetAsync(grad_value, 0, es * (size_t)E, stream));
+  if (p.mat == MinMaxScatterPlan::ZeroMat) TSAMD_HIP_TRY(hipMemsetAsync(grad_mat, 0, es * nmat, stream));
+  if (p.value != MinMaxScatterPlan::RowParallel && p.mat != MinMaxScatterPlan::Scatter) return TSAMD_OK;
   float *shadow_mat = nullptr;
-  if (shadow) {
-    const size_t need = align_up(sizeof(float) * nmat, 256);
-    if (!workspace || workspace_bytes < need) return TSAMD_ERR_WORKSPACE;
+  if (p.shadow) {
     shadow_mat = reinterpret_cast<float *>(workspace);
     TSAMD_HIP_TRY(hipMemsetAsync(shadow_mat, 0, sizeof(float) * nmat, stream));
-  } else if (grad_mat) {
+  } else if (p.mat == MinMaxScatterPlan::Scatter) {
     TSAMD_HIP_TRY(hipMemsetAsync(grad_mat, 0, es * nmat, stream));
-  }
-  if (total == 0 || (!grad_value && !grad_mat)) {
-    if (grad_value && E > 0) TSAMD_HIP_TRY(hipMemsetAsync(grad_value, 0, es * (size_t)E, stream));
-    return TSAMD_OK;
   }
   int st = dispatch_float(dtype, [&](auto t) -> int {
     using T = decltype(t);
     if constexpr (Traits<T>::kNarrow) {
       if (shadow_mat != nullptr || grad_mat == nullptr)
         return launch_minmax_bw<T, float>(rowptr, col, value, mat, grad_out, arg_out, grad_value, shadow_mat, B, M, N, K, E,
-                                          stream);
+                                          p.lgG, stream);
     }
     return launch_minmax_bw<T, T>(rowptr, col, value, mat, grad_out, arg_out, grad_value, static_cast<T *>(grad_mat), B, M,
-                                  N, K, E, stream);
+                                  N, K, E, p.lgG, stream);
   });
   if (st != TSAMD_OK) return st;
   if (shadow_mat) {
@@ -1083,4 +1139,79 @@ extern "C" int tsamd_spmm_minmax_winrec(int dtype, const int64_t *row, const voi
   if (E >= (int64_t)1 << 31 || M >= (int64_t)1 << 32) return TSAMD_ERR_UNSUPPORTED;
   return tsamd::minmax_winrec_from_ids(dtype, row, value, arg_out32, records, B, M, K, E,
                                        reinterpret_cast<hipStream_t>(stream_));
+}
+
+// What a min / max backward call decides before it launches (include/tsamd.h): the plan functions the four entries run,
+// fed with stand-in pointers (everything the query does not take is present, the workspace large enough and aligned).
+extern "C" int tsamd_spmm_minmax_bw_route(int winners, int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                          int want_value, int want_mat, const void *mat, const void *grad_out,
+                                          const void *grad_mat, int64_t route[32]) {
+  if (!route || winners < 0 || winners > 3) return TSAMD_ERR_INVALID;
+  for (int i = 0; i < 32; ++i) route[i] = 0;
+  void *const here = reinterpret_cast<void *>((uintptr_t)0x1000);  // present and aligned; never dereferenced
+  if (!mat) mat = here;
+  if (!grad_out) grad_out = here;
+  if (!grad_mat) grad_mat = here;
+  void *gv = want_value ? here : nullptr;
+  void *gm = want_mat ? const_cast<void *>(grad_mat) : nullptr;
+  if (winners == 3) {  // tsamd_spmm_minmax_bw
+    const MinMaxScatterPlan p = plan_minmax_scatter(dtype, here, here, mat, grad_out, here, gv, gm, B, M, N, K, E, here, ~(size_t)0);
+    route[0] = p.status;
+    if (p.status != TSAMD_OK) return TSAMD_OK;
+    route[1] = p.value == MinMaxScatterPlan::ZeroValue ? 1 : (p.value == MinMaxScatterPlan::RowParallel ? 3 : 0);
+    route[4] = p.mat == MinMaxScatterPlan::ZeroMat ? 1 : (p.mat == MinMaxScatterPlan::Scatter ? 3 : 0);
+    if (route[1] == 3 || route[4] == 3) {
+      route[9] = p.lgG;
+      route[10] = p.cap;
+      route[11] = p.packed ? (p.merge_pairs ? 1 : 2) : 0;
+      route[12] = p.shadow ? 1 : 0;
+      route[13] = (int64_t)p.shadow_bytes;
+    }
+    return TSAMD_OK;
+  }
+  const Winners::Kind kind = winners == 0 ? Winners::Ids64 : (winners == 1 ? Winners::Ids32 : Winners::Records);
+  const MinMaxCscCall c{dtype, static_cast<const int64_t *>(here), static_cast<const int64_t *>(here), here, true, mat,
+                        grad_out, Winners{kind, here}, static_cast<const int64_t *>(here),
+                        static_cast<const int64_t *>(here), static_cast<const int64_t *>(here), gv, gm, B, M, N, K, E, here,
+                        ~(size_t)0, nullptr};
+  const MinMaxCscPlan p = plan_minmax_csc(c);
+  route[0] = p.status;
+  if (p.status != TSAMD_OK) return TSAMD_OK;
+  route[1] = (int64_t)p.value;  // NoValue, ZeroValue, MaskedSddmm, RowParallel: 0 .. 3
+  route[4] = (int64_t)p.mat;    // NoMat, ZeroMat, Pull: 0 .. 2
+  const uint32_t W = (uint32_t)ceil_div(K, 32), S = win_record_stride(K);
+  if (p.value == MinMaxCscPlan::MaskedSddmm) {
+    const MaskedSddmmPlan s = plan_masked_sddmm(dtype_size(dtype), K, S);
+    route[2] = s.pipelined ? 1 : 2;
+    route[3] = s.lgG;
+  }
+  if (p.value == MinMaxCscPlan::RowParallel) {  // through tsamd_spmm_minmax_bw, grad_value alone
+    const MinMaxScatterPlan s = plan_minmax_scatter(dtype, here, here, mat, grad_out, here, gv, nullptr, B, M, N, K, E, nullptr, 0);
+    if (s.value == MinMaxScatterPlan::ZeroValue) route[1] = 1;
+    if (s.value == MinMaxScatterPlan::NoValue) route[1] = 0;
+    route[9] = s.lgG;
+    route[10] = s.cap;
+  }
+  if (p.mat == MinMaxCscPlan::Pull) {
+    route[5] = p.write_records ? 1 : 0;
+    route[6] = W;
+    route[7] = S;
+    route[8] = win_record_masked_has_z(W);
+    // the masked sum is the forward's SUM on the transposed problem: N rows, M "columns", grad_out gathered
+    int64_t f[24];
+    const int st = spmm_route_words(dtype, TSAMD_SUM, B, N, M, K, E, grad_out, grad_mat, nullptr, 0, nullptr, true, f);
+    if (st != TSAMD_OK) return route[0] = st, TSAMD_OK;
+    route[14] = f[7];   // items
+    route[15] = f[6];   // P
+    route[16] = f[11];  // fixup
+    route[17] = f[9];   // relabel
+    route[18] = f[10];  // copy
+    route[19] = f[1];   // vec
+    route[20] = f[3];   // lpr
+    route[21] = f[4];   // lgG
+    route[22] = f[5];   // ktiles
+    route[24] = f[0];   // family
+    route[23] = (int64_t)minmax_csc_workspace(kind, dtype, B, M, N, K, E);
+  }
+  return TSAMD_OK;
 }

@@ -29,6 +29,14 @@ static inline uint32_t win_record_stride(int64_t K) {
   return (w + 3u) & ~3u;
 }
 
+// Whether the masked sum reads word W + 3 of a record as the non-zero-word bitmap: the padding must leave that word, and
+// the bitmap has 32 bits (wider masks are read whole).  spmm_entry and tsamd_spmm_minmax_bw_route both ask here.
+static inline int win_record_masked_has_z(uint32_t W) { return (W <= 32u && ((W + 3u) & 3u) != 0u) ? 1 : 0; }
+
+// The words of tsamd_spmm_route (include/tsamd.h); `masked`: as spmm_masked_sum runs the product (csrc/spmm.hip).
+int spmm_route_words(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, const void *mat,
+                     const void *out, const void *arg_out, int arg32, void *workspace, bool masked, int64_t route[24]);
+
 // out[b, m, k] = sum over the entries i of row m of the pattern `rowptr` (entry i is record perm[i], perm
 // may be NULL) whose bit k is set of round_T(value * mat[b, id, k]) -- the merge-path SpMM of csrc/spmm_kernels.h
 // with a per-(entry, feature) predicate; E < 2^32.  Workspace as for tsamd_spmm (SUM).

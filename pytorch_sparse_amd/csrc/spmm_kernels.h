@@ -2295,7 +2295,7 @@ int spmm_entry(const SpmmCall &c, Launch launch) {
     ws.wmask = c.wmask;
     ws.rec_stride = win_record_stride(K);
     ws.rec_meta = (uint32_t)ceil_div(K, 32);
-    ws.rec_has_z = (ws.rec_meta <= 32u && ((ws.rec_meta + 3u) & 3u) != 0u) ? 1 : 0;  // a padding word behind (id, value)
+    ws.rec_has_z = win_record_masked_has_z(ws.rec_meta);  // a padding word behind (id, value)
   }
   return launch(packet_width(dtype, minmax, c.arg32, K, c.mat, c.out, c.arg_out), ws);
 }

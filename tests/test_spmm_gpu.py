@@ -181,6 +181,18 @@ def test_value_bw(dev, dtype, reduce):
             assert (err <= SUM_TOL[dtype] * l1 + SUM_ATOL[dtype]).all()
 
 
+def _value_violations(c, v, x, gout, arg, gv, dtype):
+    """grad_value against the per-element bound of tests/minmax_bw_reference.py (at most B K products summed in the
+    accumulator type, rounded once), for the winners `arg`; CPU tensors of the element type in"""
+    from tests import minmax_bw_reference as mr
+    shape = tuple(x.shape)
+    B = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
+    x3 = x.double().numpy().reshape((B, ) + shape[-2:])
+    g3 = gout.double().numpy().reshape((B, -1, shape[-1]))
+    a3 = arg.cpu().numpy().reshape(g3.shape)
+    return mr.value_violations(c.numpy(), v.double().numpy(), x3, g3, a3, gv.cpu(), dtype)
+
+
 @pytest.mark.parametrize('dtype', FLOAT_DTYPES)
 @pytest.mark.parametrize('reduce', ['min', 'max'])
 def test_minmax_bw(dev, dtype, reduce):
@@ -209,9 +221,10 @@ def test_minmax_bw(dev, dtype, reduce):
         err = np.abs(gm.cpu().double().numpy() - egm)
         floor = 2.0 ** -25 if dtype == torch.float16 else 1e-40  # half a subnormal step per addition
         assert (err <= (cnt + 1) * (u * l1 * 1.01 + floor)).all(), float((err / ((cnt + 1) * u * l1 + 1e-30)).max())
-        if has_value:
-            scale = max(1.0, float(np.abs(egv).max()))
-            assert np.allclose(gv.cpu().double().numpy(), egv, rtol=tol, atol=tol * scale)
+        if has_value:  # LDS sums in the accumulator type, rounded once: the per-element bound of the reference
+            assert np.allclose(gv.cpu().double().numpy(), egv, rtol=tol, atol=tol * max(1.0, float(np.abs(egv).max())))
+            bad, ratio = _value_violations(c, v, x, gout, arg, gv, dtype)
+            assert bad == 0, (K, batch, bad, ratio)
 
 
 def _csc_arrays(rp, c, n_cols):
@@ -311,6 +324,8 @@ def test_minmax_bw_csc_pull(dev, dtype, reduce):
             tol = {torch.float32: 1e-5, torch.float64: 1e-12, torch.float16: 4e-3, torch.bfloat16: 3e-2}[dtype]
             scale = max(1.0, float(np.abs(egv).max()))
             assert np.allclose(gv.cpu().double().numpy(), egv, rtol=tol, atol=tol * scale), K
+            bad, ratio = _value_violations(c, v, x, gout, arg, gv, dtype)
+            assert bad == 0, (K, batch, bad, ratio)
         # through autograd: the front-end hands the CSC arrays over when `mat` needs a gradient
         if batch == ():
             import pytorch_sparse_amd as ts
@@ -445,6 +460,8 @@ def assert_within_scatter_bound(c, v, x, gout, arg, grad_mat, grad_value, tag):
     if grad_value is not None:
         tol = 1e-5 if dtype == torch.float32 else 3e-2
         assert np.allclose(grad_value.cpu().double().numpy(), egv, rtol=tol, atol=tol * max(1.0, float(np.abs(egv).max())))
+        bad, ratio = _value_violations(c, v, x, gout, arg, grad_value, dtype)
+        assert bad == 0, (tag, 'grad_value', bad, ratio)
 
 
 def test_minmax_backward_route_rule(dev):
