@@ -495,6 +495,61 @@ int tsamd_segment_softmax_bw(int dtype, const void *y, const void *grad, const i
                              const int64_t *seg_ptr, int64_t nseg, int64_t E, int64_t D, void *grad_value,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Sparse attention over a pattern (csrc/sddmm.hip, csrc/spmm_heads.hip): the scores before and the aggregation
+ * after SparseTensor.softmax, with H heads side by side.  (ptr, ind) is a segmented order of the E entries: the
+ * rows through (rowptr, col) with perm = NULL, the columns through (colptr, row) with perm = csr2csc.  Entry i of
+ * that order is element p(i) = perm ? perm[i] : i of the [E, H] array (out of the SDDMM, value of the SpMM); its
+ * segment is s(i) (ptr[s] <= i < ptr[s + 1]), its source ind[i].  All arrays are contiguous; float32, float64,
+ * float16 and bfloat16; float32 / float16 / bfloat16 accumulate in fp32, float64 in fp64, one rounding on the
+ * store.  Work is split by entries, never by segments; deterministic (two calls give the same bits), no
+ * floating-point atomics, no host sync.  Needs ptr[0] = 0 and ptr[nseg] = E.
+ *
+ *   tsamd_sddmm_heads   out[p(i), h] = scale * sum_d q[s(i), h, d] * k[ind[i], h, d];  q [nseg, H, D],
+ *                       k [nsrc, H, D].  row [E] holds s(i) in the segmented order, or is NULL: then s(i) is
+ *                       searched in ptr (one of row / ptr may be NULL, not both).  One launch, no workspace.  A
+ *                       non-finite element of q (k) reaches the scores of its head on its row (column) only.
+ *   tsamd_spmm_heads    out[s, h, :] = sum over i in [ptr[s], ptr[s+1]) of value[p(i), h] * x[ind[i], h, :];
+ *                       x [nsrc, H, D], out [nseg, H, D], value NULL = all ones.  out is zeroed first: segments
+ *                       without entries are zeros and out is fully defined on return.  A segment cut by a chunk
+ *                       boundary leaves head / tail records (accumulator rows of H * D) that one fix-up launch
+ *                       adds in chunk order (fp32 records fold in fp64): a fixed combine tree.  A non-finite
+ *                       product reaches the outputs of the segment that holds the entry, in that head, only.
+ *
+ * Status, in this order: a negative size TSAMD_ERR_INVALID; a non-floating dtype, or nseg / nsrc / H / D /
+ * H * D above 2^31 - 1 (the SpMM: H * D above 65535 * 64), or an E whose byte offsets leave int64,
+ * TSAMD_ERR_UNSUPPORTED; then
+ *   SDDMM: E == 0, H == 0 or D == 0 TSAMD_OK without a launch; a null out / ind / q / k, row and ptr both null,
+ *          or nseg == 0 / nsrc == 0 TSAMD_ERR_INVALID;
+ *   SpMM:  nseg * H * D == 0 TSAMD_OK (out has no element); a null out TSAMD_ERR_INVALID; E == 0 TSAMD_OK with
+ *          out zero-filled; a null ptr / ind / x or nsrc == 0 TSAMD_ERR_INVALID; a missing or short workspace
+ *          TSAMD_ERR_WORKSPACE.  Every one of these is decided on the host before the first device call.
+ *
+ * The *_route calls are host arithmetic only, through the functions the drivers plan with; a null route array or
+ * a negative size is TSAMD_ERR_INVALID, a non-floating dtype TSAMD_ERR_UNSUPPORTED.  Only the alignment of the
+ * pointers is looked at (NULL counts as aligned).
+ *   tsamd_sddmm_heads_route: out[0] route: 0 packets (16-byte loads; D * itemsize a multiple of 16, packets per head
+ *   a power of two, q and k on a 16-byte boundary), 1 generic (element loads, any D >= 1); out[1] elements per
+ *   load; out[2] lanes per head (the butterfly runs over these); out[3] entries side by side in a wave; out[4]
+ *   heads side by side in a group of lanes (H above it takes several passes); out[5] entries per wave window
+ *   (64); out[6] entries per workgroup (256); out[7] the most heads a pass holds (16).
+ *   tsamd_spmm_heads_route: out[0] route: 0 packets (D * itemsize a multiple of 16, x and out on a 16-byte
+ *   boundary), 1 generic; out[1] elements per lane; out[2] lanes per row; out[3] groups (chunks) side by side in a
+ *   wave; out[4] entries per chunk = 8 * out[2] (a function of dtype, H, D alone); out[5] entries per workgroup
+ *   tile (2048); out[6] the largest number of segments a tile stages in LDS; out[7] column blocks.
+ *   workspace = 2 * align256(acc * nchunks * H * D) + 2 * align256(8 * nchunks), nchunks = ceil(E / out[4]),
+ *   acc = 8 for float64, else 4 (0 bytes for a dtype or a size that is not supported).
+ * ------------------------------------------------------------------------ */
+int tsamd_sddmm_heads_route(int dtype, int64_t H, int64_t D, const void *q, const void *k, int64_t out[8]);
+int tsamd_sddmm_heads(int dtype, const int64_t *row, const int64_t *ptr, const int64_t *ind, const int64_t *perm,
+                      const void *q, const void *k, double scale, void *out, int64_t nseg, int64_t nsrc,
+                      int64_t H, int64_t D, int64_t E, void *stream);
+int tsamd_spmm_heads_route(int dtype, int64_t H, int64_t D, const void *x, const void *out, int64_t out_route[8]);
+size_t tsamd_spmm_heads_workspace_bytes(int dtype, int64_t nseg, int64_t H, int64_t D, int64_t E);
+int tsamd_spmm_heads(int dtype, const int64_t *ptr, const int64_t *ind, const int64_t *perm, const void *value,
+                     const void *x, void *out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):

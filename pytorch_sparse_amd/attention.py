@@ -1,0 +1,153 @@
+"""Attention over a sparse pattern: the two ends of ``scores -> softmax -> aggregate``.
+
+``sddmm(adj, q, k, scale)``   a score per stored entry and head, ``scale * <q[row], k[col]>``, as the values of ``adj``
+                              (``tsamd::sddmm_heads``, csrc/sddmm.hip) -- no ``[nnz, H, D]`` gather is materialised;
+``matmul_heads(adj, x)``      ``out[m, h] = sum_n adj[m, n, h] * x[n, h]`` for ``[nnz, H]`` values
+                              (``tsamd::spmm_heads``, csrc/spmm_heads.hip) -- no Python loop over the heads.
+
+With ``SparseTensor.softmax`` in between::
+
+    out = adj.sddmm(q, k, D ** -0.5).softmax(1).matmul_heads(v)
+
+Both are differentiable (once), and the two kernels close over each other: the gradient of ``sddmm`` w.r.t. ``q`` is
+the multi-head SpMM with the score gradient as values, w.r.t. ``k`` the same on the columns (``colptr``, ``csr2csc``);
+the value gradient of ``matmul_heads`` is an SDDMM of ``grad_out`` with ``x``, its ``x`` gradient the SpMM on the columns.
+The column-side caches of the storage are only built when such a gradient will be asked for.
+"""
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from .tensor import SparseTensor
+
+
+def _csc_side(st):
+    """(colptr, row ids in column order, csr2csc): the segmented order of the columns"""
+    csr2csc = st.csr2csc()
+    return st.colptr(), st.row().index_select(0, csr2csc), csr2csc
+
+
+class _SddmmHeads(torch.autograd.Function):
+    """scores = tsamd::sddmm_heads; grad_q = scale * spmm_heads(rows; g, k), grad_k = scale * spmm_heads(columns; g, q)"""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, row: Optional[Tensor], rowptr: Tensor, col: Tensor,
+                colptr: Optional[Tensor], row_csc: Optional[Tensor], csr2csc: Optional[Tensor], scale: float):
+        out = torch.ops.tsamd.sddmm_heads(row, rowptr, col, None, q.detach(), k.detach(), scale)
+        ctx.scale = scale
+        ctx.has_csc = colptr is not None
+        ctx.save_for_backward(*([q, k, rowptr, col] + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        q, k, rowptr, col = ctx.saved_tensors[:4]
+        g = grad_out.contiguous()
+        grad_q = grad_k = None
+        if ctx.needs_input_grad[0]:
+            grad_q = torch.ops.tsamd.spmm_heads(rowptr, col, None, g, k, q.size(0))
+            if ctx.scale != 1.0:
+                grad_q.mul_(ctx.scale)
+        if ctx.needs_input_grad[1]:
+            colptr, row_csc, csr2csc = ctx.saved_tensors[4:7]
+            grad_k = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, g, q, k.size(0))
+            if ctx.scale != 1.0:
+                grad_k.mul_(ctx.scale)
+        return grad_q, grad_k, None, None, None, None, None, None, None
+
+
+class _SpmmHeads(torch.autograd.Function):
+    """out = tsamd::spmm_heads; grad_value = sddmm_heads(grad_out, x), grad_x = spmm_heads(columns; value, grad_out)"""
+
+    @staticmethod
+    def forward(ctx, value: Tensor, x: Tensor, row: Optional[Tensor], rowptr: Tensor, col: Tensor,
+                colptr: Optional[Tensor], row_csc: Optional[Tensor], csr2csc: Optional[Tensor], nseg: int):
+        out = torch.ops.tsamd.spmm_heads(rowptr, col, None, value.detach(), x.detach(), nseg)
+        ctx.has_row = row is not None
+        ctx.has_csc = colptr is not None
+        ctx.save_for_backward(*([value, x, rowptr, col] + ([row] if ctx.has_row else []) +
+                                ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        value, x, rowptr, col = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        row = rest.pop(0) if ctx.has_row else None
+        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
+        grad_value = grad_x = None
+        if ctx.needs_input_grad[0]:
+            grad_value = torch.ops.tsamd.sddmm_heads(row, rowptr, col, None, g, x, 1.0)
+        if ctx.needs_input_grad[1]:
+            colptr, row_csc, csr2csc = rest
+            grad_x = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, value, g, x.size(0))
+        return grad_value, grad_x, None, None, None, None, None, None, None
+
+
+def _check_operand(t: Tensor, name: str, rows: int, what: str) -> None:
+    if not isinstance(t, Tensor):
+        raise TypeError('%s must be a Tensor' % name)
+    if not t.is_floating_point():
+        raise ValueError('%s must be floating point, got %s' % (name, t.dtype))
+    if t.size(0) != rows:
+        raise ValueError('%s has %d rows, the sparse pattern has %d %s' % (name, t.size(0), rows, what))
+
+
+def sddmm(adj: SparseTensor, q: Tensor, k: Tensor, scale: float = 1.0) -> SparseTensor:
+    """``adj`` with the values ``scale * (q[row] * k[col]).sum(-1)``: ``[nnz]`` for ``q [M, D]``, ``k [N, D]``, ``[nnz, H]``
+    for ``q [M, H, D]``, ``k [N, H, D]``, in storage order.  Only the pattern of ``adj`` is used, its values are not
+    read.  Differentiable (once) w.r.t. ``q`` and ``k``."""
+    if q.dim() != k.dim() or q.dim() not in (2, 3):
+        raise ValueError('q and k must both be [rows, D] or [rows, H, D], got %d and %d dimensions'
+                         % (q.dim(), k.dim()))
+    _check_operand(q, 'q', adj.sparse_size(0), 'rows')
+    _check_operand(k, 'k', adj.sparse_size(1), 'columns')
+    if q.dtype != k.dtype:
+        raise ValueError('q and k differ in dtype: %s and %s' % (q.dtype, k.dtype))
+    if q.shape[1:] != k.shape[1:]:
+        raise ValueError('q is %s per row, k is %s: heads and features must agree'
+                         % (tuple(q.shape[1:]), tuple(k.shape[1:])))
+    flat = q.dim() == 2
+    if flat:
+        q, k = q.unsqueeze(1), k.unsqueeze(1)
+    st = adj.storage
+    rowptr, col, row = st.rowptr(), st.col(), st._row
+    grad = torch.is_grad_enabled()
+    if grad and (q.requires_grad or k.requires_grad):
+        colptr, row_csc, csr2csc = _csc_side(st) if k.requires_grad else (None, None, None)
+        out = _SddmmHeads.apply(q, k, row, rowptr, col, colptr, row_csc, csr2csc, float(scale))
+    else:
+        out = torch.ops.tsamd.sddmm_heads(row, rowptr, col, None, q, k, float(scale))
+    return adj.set_value(out.squeeze(1) if flat else out, layout='coo')
+
+
+def matmul_heads(adj: SparseTensor, x: Tensor) -> Tensor:
+    """``out[m, h, :] = sum over the stored entries (m, n) of value[(m, n), h] * x[n, h, :]``: values ``[nnz, H]``,
+    ``x [N, H, D]`` -> ``[M, H, D]``; rows without entries are zeros.  Differentiable (once) w.r.t. the values and
+    ``x``.  One weight per entry for all features is ``matmul``."""
+    value = adj.storage.value()
+    if value is None or value.dim() != 2:
+        raise ValueError('matmul_heads needs [nnz, H] values, got %s; a SparseTensor without values or with one '
+                         'weight per entry goes through matmul' % ('none' if value is None else tuple(value.shape)))
+    if x.dim() != 3:
+        raise ValueError('x must be [N, H, D], got %d dimensions' % x.dim())
+    _check_operand(x, 'x', adj.sparse_size(1), 'columns')
+    if not value.is_floating_point():
+        raise ValueError('matmul_heads needs floating-point values, got %s' % value.dtype)
+    if value.size(1) != x.size(1):
+        raise ValueError('the values have %d heads, x has %d' % (value.size(1), x.size(1)))
+    value = value.to(x.dtype)
+    st = adj.storage
+    rowptr, col, nseg = st.rowptr(), st.col(), adj.sparse_size(0)
+    grad = torch.is_grad_enabled()
+    if grad and (value.requires_grad or x.requires_grad):
+        colptr, row_csc, csr2csc = _csc_side(st) if x.requires_grad else (None, None, None)
+        return _SpmmHeads.apply(value, x, st._row, rowptr, col, colptr, row_csc, csr2csc, nseg)
+    return torch.ops.tsamd.spmm_heads(rowptr, col, None, value, x, nseg)
+
+
+SparseTensor.sddmm = lambda self, q, k, scale=1.0: sddmm(self, q, k, scale)
+SparseTensor.matmul_heads = lambda self, x: matmul_heads(self, x)
