@@ -147,6 +147,27 @@ int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const int64_t *col,
  * Returns the mode in force.  Process-wide; the backward kernels are not affected. */
 int tsamd_spmm_reference_order(int set);
 
+/* Column order of the merge kernel.  Sums / means over rows of >= 256 bytes run their partitions in an order built on
+ * the device in every call: the partitions that lie wholly inside one row ("single-row": table[p].row < M,
+ * table[p].entry > rowptr[row], table[p + 1].row == row) go behind all others, sorted by
+ * (col[e0] + col[e1 - 1], p), so that the waves in flight gather the same rows of `mat` at the same time.  Only the
+ * order of execution changes: results are bit-identical with every setting.
+ *   tsamd_spmm_column_order(set): 0 off, 1 auto (the default: calls with E >= 2^20, N >= 4096, E >= 8 N and
+ *   power-of-two rows, when the device counts at least layout[5] single-row partitions that are at least an eighth of
+ *   all), 2 on for every call in scope; anything else: query.  Returns the setting in force.  Process-wide.
+ *   tsamd_spmm_order_layout (inspection and tests; no device work): 0 when tsamd_spmm with these operands keeps
+ *   slot = partition, else the mode (1 auto, 2 forced) and
+ *     layout[0]  byte offset in `workspace` of the header (uint32): [0] 1 = the order is in force for this call (auto
+ *                engaged, or forced; 0 also when one of the builder's key buckets held more than layout[6] keys),
+ *                [1] the number of single-row partitions, [2] the largest bucket
+ *     layout[1]  byte offset of the slot -> partition map (uint32 [layout[2]], layout[2] = P): the other partitions in
+ *                ascending order, then the single-row ones by (key, p); written only when the order is in force
+ *     layout[3]  byte offset of the keys (uint32 [P], 0xFFFFFFFF = not single-row)
+ *     layout[4]  the builder's bucket of a key is key >> layout[4] (buckets only bound its work; the order is exact). */
+int tsamd_spmm_column_order(int set);
+int tsamd_spmm_order_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                            const void *mat, const void *out, void *workspace, int64_t *layout);
+
 /* The same product with the entries of the CSR taken through a permutation: entry e is
  * (col[perm[e]], value[perm[e]]), perm [E] int64.  With (rowptr, col, perm) = (colptr, row, csr2csc)
  * this multiplies by the TRANSPOSE of a matrix straight from its COO/CSR arrays -- the

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('TSAMD_LIB') or os.path.join(_HERE, 'lib', 'libtsamd.s
 # Every symbol include/tsamd.h declares (tests check that all of them resolve).
 SYMBOLS = [
     'tsamd_hip_version', 'tsamd_build_flags', 'tsamd_last_hip_error', 'tsamd_status_string',
-    'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm_route', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
+    'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm_route', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_column_order', 'tsamd_spmm_order_layout', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
     'tsamd_spmm_partial_workspace_bytes', 'tsamd_spmm_partial',
     'tsamd_spmm_operand_cache_bytes', 'tsamd_spmm_cached_workspace_bytes', 'tsamd_spmm_cached',
     'tsamd_spmm_minmax_arg32', 'tsamd_spmm_minmax_bw_csc_arg32',
@@ -207,6 +207,24 @@ def spmm_route(dtype, reduce, B, M, N, K, E, mat=0, out=0, arg_out=0, arg32=Fals
     check(st, 'tsamd_spmm_route')
     r = dict(zip(SPMM_ROUTE_FIELDS, (int(x) for x in words)))
     r['family'] = SPMM_FAMILIES[r['family']]
+    return r
+
+
+SPMM_ORDER_FIELDS = ('hdr_off', 'order_off', 'P', 'keys_off', 'shift', 'min_singles', 'bucket_max')
+
+
+def spmm_order_layout(dtype, reduce, B, M, N, K, E, mat, out, workspace):
+    """C-ABI ``tsamd_spmm_order_layout`` (host arithmetic): None when the call keeps slot = partition, else a dict of
+    SPMM_ORDER_FIELDS plus ``mode`` (1 auto, 2 forced).  mat / out / workspace: tensors or plain addresses."""
+    def addr(p):
+        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
+    words = (ctypes.c_int64 * 8)()
+    mode = lib().tsamd_spmm_order_layout(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E),
+                                         addr(mat), addr(out), addr(workspace), words)
+    if mode == 0:
+        return None
+    r = dict(zip(SPMM_ORDER_FIELDS, (int(x) for x in words)))
+    r['mode'] = int(mode)
     return r
 
 

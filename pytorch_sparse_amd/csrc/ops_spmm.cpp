@@ -874,6 +874,10 @@ int64_t cuda_version() { return tsamd_hip_version(); }
 // operations (bit-identical results, slow), 0 = the product kernels, anything else = query; returns the mode in force
 int64_t reference_order(int64_t set) { return (int64_t)tsamd_spmm_reference_order((int)set); }
 
+// tsamd_spmm_column_order (include/tsamd.h): 0 = the merge kernel runs its partitions in their own order, 1 = auto,
+// 2 = column order for every call in scope, anything else = query; returns the setting in force
+int64_t column_order(int64_t set) { return (int64_t)tsamd_spmm_column_order((int)set); }
+
 // torch.are_deterministic_algorithms_enabled() for TorchScript callers (storage_spmm)
 bool deterministic_mode() { return at::globalContext().deterministicAlgorithms(); }
 
@@ -896,6 +900,7 @@ static auto registry_spmm = torch::RegisterOperators()
                            .op("tsamd::spmm_minmax", &spmm_minmax)
                            .op("tsamd::deterministic", &deterministic_mode)
                            .op("tsamd::reference_order", &reference_order)
+                           .op("tsamd::column_order", &column_order)
                            .op("tsamd::spmm_sum_owned", &spmm_sum_owned)
                            .op("tsamd::spmm_mean_owned", &spmm_mean_owned)
                            .op("tsamd::operand_cache", &operand_cache_ctl)

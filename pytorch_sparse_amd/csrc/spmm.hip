@@ -3,6 +3,8 @@
 #define TSAMD_SPMM_PARTIAL_BUILD 0
 #include "spmm_kernels.h"
 
+#include <atomic>
+
 using namespace tsamd;
 
 // sum / mean are instantiated here, min / max in spmm_min.hip / spmm_max.hip
@@ -64,6 +66,40 @@ extern "C" int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, in
 
 extern "C" int tsamd_spmm_hot_block_min(void) { return kHotBlockMin; }
 
+// column order (include/tsamd.h; spmm_kernels.h, section 1b): the process-wide setting, and where a call's order sits
+namespace tsamd {
+namespace {
+std::atomic<int> g_column_order{1};
+}
+int spmm_column_order_mode() { return g_column_order.load(std::memory_order_relaxed); }
+}  // namespace tsamd
+
+extern "C" int tsamd_spmm_column_order(int set) {
+  if (set >= 0 && set <= 2) tsamd::g_column_order.store(set, std::memory_order_relaxed);
+  return tsamd::g_column_order.load(std::memory_order_relaxed);
+}
+
+extern "C" int tsamd_spmm_order_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                       const void *mat, const void *out, void *workspace, int64_t *layout) {
+  if (!layout || !workspace || dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
+  if (reduce != TSAMD_SUM && reduce != TSAMD_MEAN) return 0;
+  if (B * M * K == 0 || spmm_reference_order_on() || (uintptr_t)workspace % 256 != 0) return 0;
+  Workspace ws;
+  carve(workspace, dtype, reduce, B, M, N, K, E, &ws);
+  const int mode = order_mode_of(ws, dtype, reduce, N, K, E, lane_layout(K, packet_width(dtype, false, false, K, mat, out, nullptr)).lgG);
+  if (mode == 0) return 0;
+  const char *base = reinterpret_cast<const char *>(workspace);
+  layout[0] = reinterpret_cast<const char *>(ws.order_hdr) - base;
+  layout[1] = reinterpret_cast<const char *>(ws.order) - base;
+  layout[2] = ws.P;
+  layout[3] = reinterpret_cast<const char *>(ws.order_cls) - base;
+  layout[4] = ws.order_shift;
+  layout[5] = kOrderMinSingles;
+  layout[6] = kOrderBucketMax;
+  layout[7] = 0;
+  return mode;
+}
+
 // min / max with int32 ids: which record-writing instantiation tsamd_spmm_minmax_records takes for these operands
 // (0 = none: the records come from the ids)
 static bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64_t E, const void *mat, const void *out);
@@ -97,7 +133,7 @@ int tsamd::spmm_route_words(int dtype, int reduce, int64_t B, int64_t M, int64_t
   if (!base) base = reinterpret_cast<char *>(align_up((size_t)(uintptr_t)mat + 1, 4096));
   if (!mat) mat = base;
   Workspace ws;
-  route[18] = (int64_t)carve(base, dtype, reduce, B, M, N, K, E, &ws);
+  route[18] = (int64_t)carve(base, dtype, reduce, B, M, N, K, E, &ws, false, masked);
   const int vec = packet_width(dtype, minmax, arg32 != 0, K, mat, out, arg_out);
   const LaneLayout lay = lane_layout(K, vec);
   const size_t es = dtype_size(dtype);
@@ -376,7 +412,7 @@ extern "C" int tsamd_spmm_permuted(int dtype, int reduce, const int64_t *rowptr,
 // internal (spmm_internal.h): the masked sum behind tsamd_spmm_minmax_bw_csc
 namespace tsamd {
 size_t spmm_masked_sum_workspace_bytes(int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E) {
-  return carve(nullptr, dtype, TSAMD_SUM, B, M, N, K, E, nullptr);
+  return carve(nullptr, dtype, TSAMD_SUM, B, M, N, K, E, nullptr, false, /*masked=*/true);
 }
 int spmm_masked_sum(int dtype, const int64_t *rowptr, bool has_value, const int64_t *perm,
                     const uint32_t *records, const void *mat, void *out, int64_t B, int64_t M, int64_t N,

@@ -55,4 +55,7 @@ int spmm_reference_order_run(int dtype, int reduce, const int64_t *rowptr, const
                              const void *mat, void *out, void *arg_out, bool arg32, int64_t B, int64_t M, int64_t N,
                              int64_t K, int64_t E, hipStream_t stream);
 
+// Column order of the merge kernel (csrc/spmm_kernels.h, section 1b): the setting of tsamd_spmm_column_order.
+int spmm_column_order_mode();
+
 }  // namespace tsamd

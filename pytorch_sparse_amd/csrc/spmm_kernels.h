@@ -140,6 +140,17 @@ struct Workspace {
   uint32_t *blk_list;   // [ceil(N / 64)] indices of the selected blocks, compacted within every chunk of blk_chunk blocks
   uint32_t *blk_total;  // [kHotChunks] selected blocks per chunk
   uint32_t blk_chunk;   // blocks per chunk, a multiple of 256
+  // column order (see "column order" below): the merge kernel's wave number is a SLOT, the partition it runs comes from
+  // `order`.  Carved behind everything else; nullptr = the call is out of scope and slot = partition.
+  uint32_t *order_hdr;   // [kOrderHdrWords] device words, see spmm_order_* kernels; [0] != 0: the order is in force
+  uint32_t *order;       // [P] slot -> partition
+  uint32_t *order_cls;   // [P] key of a single-row partition, kOrderPad for every other partition
+  uint32_t *order_hist;  // [kOrderBuckets] single-row partitions per bucket, then [kOrderBuckets] scatter cursors
+  uint32_t *order_chunk;  // [ceil(P / 1024)] single-row partitions per chunk of 1024 partitions
+  uint32_t *order_start;  // [kOrderBuckets] exclusive scan of the bucket counts
+  uint64_t *order_tmp;   // [P] (key << 32 | partition) of the single-row partitions, grouped by bucket
+  uint32_t order_shift;  // bucket = key >> order_shift
+  int order_mode;        // 0 off, 1 auto (the device decides from the count), 2 forced on
 };
 
 // One SpMM call: the operands of tsamd_spmm (include/tsamd.h), then the optional modes (see Workspace), off unless set.
@@ -536,8 +547,25 @@ __global__ __launch_bounds__(256) void spmm_hot_block_copy_kernel(const void *__
 // ---------------------------------------------------------------------------
 // 1. merge-path partition: list A = row ends rowptr[1..M], list B = edge ids
 // ---------------------------------------------------------------------------
-__global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, int64_t M, int64_t E,
-                                      Workspace ws) {
+// column order (section 1b)
+constexpr uint32_t kOrderPad = 0xFFFFFFFFu;  // the key of a partition that is not single-row
+constexpr int kOrderBuckets = 4096;          // key ranges of 2^order_shift keys
+constexpr int kOrderChunkLg = 10;            // the scatter kernel's workgroup takes 1024 partitions
+constexpr int kOrderHdrWords = 64;           // [0] in force, [1] single-row partitions, [2] largest bucket
+#ifndef TSAMD_ORDER_MIN_SINGLES
+#define TSAMD_ORDER_MIN_SINGLES 1024
+#endif
+constexpr uint32_t kOrderMinSingles = TSAMD_ORDER_MIN_SINGLES;
+constexpr uint32_t kOrderBucketMax = 16384;
+// (equal-width key ranges; ranges of equal relative width -- leading bit and seven more -- were measured worse on the north
+// star: its keys do not crowd at the small ids alone, 0.233 ms of prologue against 0.167)
+__device__ __forceinline__ uint32_t order_bucket(uint32_t key, uint32_t shift) {
+  const uint32_t b = key >> shift;  // (valid column ids give b < kOrderBuckets: carve)
+  return b < (uint32_t)kOrderBuckets ? b : (uint32_t)kOrderBuckets - 1u;
+}
+
+__global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M,
+                                      int64_t E, Workspace ws) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p > ws.P) return;
   int64_t d = p * ws.items;
@@ -558,6 +586,131 @@ __global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, int64_
     if (e > rs && e - rs <= ws.snap) e = rs;
   }
   ws.table[p] = Coord{lo, e};
+  // column order: classify the partition while both coordinates are at hand.  The next boundary lies in the same row
+  // exactly when the search at the next diagonal would stop at `lo` again, which is one comparison.
+  if (ws.order == nullptr || p >= ws.P) return;
+  uint32_t key = kOrderPad;
+  if (lo < M && e > rowptr[lo]) {
+    int64_t d1 = d + ws.items;
+    if (d1 > M + E) d1 = M + E;
+    if (rowptr[lo + 1] > d1 - lo - 1) key = (uint32_t)col[e] + (uint32_t)col[e + ws.items - 1];
+  }
+  ws.order_cls[p] = key;
+  const bool single = key != kOrderPad;
+  if (single) atomicAdd(&ws.order_hist[order_bucket(key, ws.order_shift)], 1u);
+  // single-row partitions per chunk of kOrderChunk partitions (a wave's 64 partitions lie in one chunk)
+  const unsigned long long m = __ballot(single);
+  if (m != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(__ballot(true)))
+    atomicAdd(&ws.order_chunk[p >> kOrderChunkLg], (uint32_t)__popcll(m));
+}
+
+// ---------------------------------------------------------------------------
+// 1b. column order.  Which partition runs when is free: no sum depends on it.  On a skewed graph most entries lie in
+//    rows longer than a partition, and a partition that lies wholly inside one row ("single-row") gathers an
+//    ascending, narrow run of column ids (CSR entries are sorted by column inside a row).  In partition order the
+//    single-row pieces in flight together sit at unrelated columns; ordered by column they gather the SAME rows of X
+//    at the same time, and the L2s hit where they missed (docs/design/spmm_forward.md, "Column order").
+//
+//    The rule (tests/spmm_order_reference.py restates it in numpy):
+//      single-row    table[p].row < M, table[p].edge > rowptr[row] and table[p + 1].row == row
+//      key           col[e0] + col[e1 - 1]
+//      order         every other partition first, ascending; then the single-row ones by (key, p)
+//    Consecutive slots share a workgroup and consecutive workgroups go to the eight XCDs in turn, so all of them walk the
+//    sorted list together.  (Cutting the list into eight ranges, one per XCD, was measured slower.)
+//    Built per call, without a host sync: the partition kernel classifies and counts keys per bucket of 2^order_shift
+//    keys; the scatter kernel scans the buckets, places the other partitions and throws the single-row ones into their
+//    bucket's span (in any order); the rank kernel counts, for every one of them, the smaller (key, p) of its bucket --
+//    its exact rank.  Auto mode engages when the device finds at least kOrderMinSingles single-row partitions that
+//    are at least an eighth of all; otherwise both kernels leave at once and the merge kernel keeps slot = partition.
+//    A bucket of more than kOrderBucketMax members (the rank count is quadratic in it) keeps identity order too.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool order_engaged(int mode, uint32_t P, uint32_t ns, uint32_t maxb) {
+  if (maxb > kOrderBucketMax) return false;
+  return mode == 2 || (ns >= kOrderMinSingles && (uint64_t)ns * 8u >= (uint64_t)P);
+}
+
+// One workgroup of 1024 threads per chunk of 1024 partitions.  Every workgroup scans the bucket counts for itself
+// (4096 counts, four per thread); workgroup 0 leaves the verdict and the bucket starts for the other kernels.
+__global__ __launch_bounds__(1024) void spmm_order_scatter_kernel(Workspace ws) {
+  __shared__ uint32_t start[kOrderBuckets];
+  __shared__ uint32_t wsum[16], wmax[16], wcnt[16], wpart[16];
+  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+  const uint32_t P = (uint32_t)ws.P;
+  static_assert(kOrderBuckets == 4096 && kOrderChunkLg == 10, "four buckets per thread, a partition per thread");
+  const uint4 h = reinterpret_cast<const uint4 *>(ws.order_hist)[t];
+  const uint32_t mine = h.x + h.y + h.z + h.w;
+  uint32_t inc = mine, mx = max(max(h.x, h.y), max(h.z, h.w));
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t u = lane_read_u32(inc, lane >= (uint32_t)off ? (int)lane - off : (int)lane);
+    if (lane >= (uint32_t)off) inc += u;
+    mx = max(mx, lane_read_u32(mx, (int)(lane ^ (uint32_t)off)));
+  }
+  if (lane == 63u) wsum[wv] = inc;
+  if (lane == 0u) wmax[wv] = mx;
+  __syncthreads();
+  uint32_t base = 0, ns = 0, maxb = 0;
+  for (uint32_t i = 0; i < 16u; ++i) {
+    base += i < wv ? wsum[i] : 0u;
+    ns += wsum[i];
+    maxb = max(maxb, wmax[i]);
+  }
+  const bool on = order_engaged(ws.order_mode, P, ns, maxb);
+  if (blockIdx.x == 0 && t == 0) {
+    ws.order_hdr[0] = on ? 1u : 0u;
+    ws.order_hdr[1] = ns;
+    ws.order_hdr[2] = maxb;
+  }
+  if (!on) return;  // (uniform over the grid)
+  const uint32_t s0 = base + inc - mine;  // first place of bucket 4 t
+  const uint4 st = uint4{s0, s0 + h.x, s0 + h.x + h.y, s0 + h.x + h.y + h.z};
+  reinterpret_cast<uint4 *>(start)[t] = st;
+  if (blockIdx.x == 0) reinterpret_cast<uint4 *>(ws.order_start)[t] = st;
+  // single-row partitions in the chunks in front of this one
+  uint32_t part = 0;
+  for (uint32_t c = t; c < blockIdx.x; c += 1024u) part += ws.order_chunk[c];
+  for (int off = 32; off > 0; off >>= 1) part += lane_read_u32(part, (int)(lane ^ (uint32_t)off));
+  const uint32_t p = blockIdx.x * 1024u + t;
+  const uint32_t key = p < P ? ws.order_cls[p] : kOrderPad;
+  const bool single = key != kOrderPad;
+  const unsigned long long m = __ballot(single);
+  if (lane == 0u) {
+    wcnt[wv] = (uint32_t)__popcll(m);
+    wpart[wv] = part;  // (every lane holds the wave's sum)
+  }
+  __syncthreads();
+  uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  for (uint32_t i = 0; i < 16u; ++i) before += (i < wv ? wcnt[i] : 0u) + wpart[i];
+  if (p < P) {
+    if (!single) {
+      ws.order[p - before] = p;
+    } else {  // anywhere in the bucket's span: the rank kernel finds the exact place
+      const uint32_t b = order_bucket(key, ws.order_shift);
+      const uint32_t q = start[b] + atomicAdd(&ws.order_hist[kOrderBuckets + b], 1u);
+      ws.order_tmp[q] = ((uint64_t)key << 32) | p;
+    }
+  }
+}
+
+// A wave per single-row partition: its rank is its bucket's start plus the number of smaller (key, p) in the bucket,
+// counted 64 members at a time.  (A thread per partition took 0.06 ms on the north star: its largest buckets hold
+// thousands of members.)
+__global__ __launch_bounds__(256) void spmm_order_rank_kernel(Workspace ws) {
+  if (ws.order_hdr[0] == 0u) return;
+  const uint32_t ns = ws.order_hdr[1];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  for (uint32_t i = first; i < ns; i += gridDim.x * 4u) {
+    const uint64_t rec = ws.order_tmp[i];
+    const uint32_t b = order_bucket((uint32_t)(rec >> 32), ws.order_shift);
+    const uint32_t s0 = ws.order_start[b], s1 = s0 + ws.order_hist[b];
+    uint32_t rank = s0;
+    for (uint32_t base = s0; base < s1; base += 64u) {
+      const uint32_t j = base + lane;
+      const bool less = j < s1 && ws.order_tmp[j] < rec;
+      rank += (uint32_t)__popcll(__ballot(less));
+    }
+    if (lane == 0u) ws.order[(uint32_t)ws.P - ns + rank] = (uint32_t)rec;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1073,8 +1226,16 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
   __shared__ alignas(16) uint32_t rec_tile_[REC == 1 ? kWavesPerBlock * kWave * 4 : (REC == 2 ? kWavesPerBlock * kRecTileWords : 4)];
   const int lane = (int)(threadIdx.x & 63);
   const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t p = (int64_t)blockIdx.x * kWavesPerBlock + wib;
+  // the wave's number is a slot; with a column order in force (section 1b) the slot names the partition.  Both words
+  // are asked for at once: one round trip in front of the table's.  Everything below is indexed by the partition.
+  int64_t p = (int64_t)blockIdx.x * kWavesPerBlock + wib;
   if (p >= ws.P) return;
+  if constexpr (RED == RED_ADD && !SHORT && !MASKED && !A32 && REC == 0 && !kPartial) {
+    if (ws.order != nullptr) {
+      const uint32_t on = ws.order_hdr[0], q = ws.order[p];
+      if (on != 0u) p = (int64_t)q;
+    }
+  }
   const uint32_t y = blockIdx.y;
   const uint32_t b = y / ktiles;
   const uint32_t kt = y - b * ktiles;
@@ -1896,8 +2057,13 @@ bool relabel_possible(int dtype, int reduce, int64_t N, int64_t K, int64_t E) {
   return size_ok && camps;
 }
 
+// column order: header, bucket counts, scatter cursors, counts per chunk of partitions -- what a call clears
+size_t order_clear_bytes(int64_t P) {
+  return sizeof(uint32_t) * (size_t)(kOrderHdrWords + 2 * kOrderBuckets + ceil_div(P, (int64_t)1 << kOrderChunkLg));
+}
+
 size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K,
-             int64_t E, Workspace *ws, bool relabelled = false) {
+             int64_t E, Workspace *ws, bool relabelled = false, bool masked = false) {
   int64_t P, items;
   plan_partition(M, E, K * (int64_t)dtype_size(dtype), &P, &items);
   const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
@@ -1937,6 +2103,21 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   w.hot_word = hot_scope ? reinterpret_cast<uint32_t *>(take(16 * (size_t)hot_words)) : nullptr;
   w.hot_count = hot_scope ? reinterpret_cast<int64_t *>(take(sizeof(int64_t) * (size_t)hot_words)) : nullptr;
   w.hot_scan = hot_scope ? take(scan_workspace_bytes(hot_words)) : nullptr;
+  // column order (section 1b): sums of rows of >= 256 bytes (not the masked sum: its workspace is sized by
+  // spmm_masked_sum_workspace_bytes).  Behind everything else: no earlier offset moves.
+  const bool order_scope = !relabelled && !masked && !minmax && K * (int64_t)dtype_size(dtype) >= 256 && N < ((int64_t)1 << 31) &&
+                           P < ((int64_t)1 << 31);
+  // (header, bucket counts, cursors and chunk counts are one span: launch_spmm clears it with one memset)
+  w.order_hdr = order_scope ? reinterpret_cast<uint32_t *>(take(order_clear_bytes(P))) : nullptr;
+  w.order_hist = order_scope ? w.order_hdr + kOrderHdrWords : nullptr;
+  w.order_chunk = order_scope ? w.order_hist + 2 * kOrderBuckets : nullptr;
+  w.order_start = order_scope ? reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * kOrderBuckets)) : nullptr;
+  w.order = order_scope ? reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)P)) : nullptr;
+  w.order_cls = order_scope ? reinterpret_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)P)) : nullptr;
+  w.order_tmp = order_scope ? reinterpret_cast<uint64_t *>(take(sizeof(uint64_t) * (size_t)P)) : nullptr;
+  w.order_shift = 0;
+  while (w.order_shift < 32 && ((uint64_t)(2 * (N > 0 ? N : 1) - 1) >> w.order_shift) >= (uint64_t)kOrderBuckets) ++w.order_shift;
+  w.order_mode = 0;
   w.hot_side = nullptr;
   w.hot_side_row = 0;
   w.hot_stride = TSAMD_HOT_STRIDE;
@@ -1991,6 +2172,18 @@ bool hot_rows_place(const Workspace &ws, const void *mat, int64_t N, uint64_t ro
   *side = at;
   *side_row = (int32_t)rows;
   return true;
+}
+
+// column order: the host half of the decision -- 0 identity order, 1 the device decides from the count of single-row
+// partitions, 2 forced.  launch_spmm and tsamd_spmm_order_layout both ask here.  Auto is for the calls whose size makes
+// the relabelled copy possible: smaller ones would only pay the builder's launches.
+[[maybe_unused]] int order_mode_of(const Workspace &ws, int dtype, int reduce, int64_t N, int64_t K, int64_t E, int lgG) {
+  if (ws.order == nullptr || lgG >= 3 || ws.wmask != nullptr || ws.perm != nullptr || ws.out_relabel || ws.partial ||
+      ws.cache_state != 0 || ws.arg32 || ws.P < 2)
+    return 0;
+  const int sw = spmm_column_order_mode();
+  if (sw == 2) return 2;
+  return sw == 1 && relabel_possible(dtype, reduce, N, K, E) ? 1 : 0;
 }
 
 // `vec` = elements per lane packet, chosen by the caller: the largest power of two <= kMaxVec<T>
@@ -2127,9 +2320,25 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
                                      sizeof(unsigned long long) * kFingerprintWords, hipMemcpyDeviceToDevice, stream));
     }
   }
+  // column order (section 1b): the partition kernel classifies, two more launches build the slot -> partition map
+  const int order_mode = !kPartial && RED == RED_ADD ? order_mode_of(ws, c.dtype, c.reduce, N, K, E, lgG) : 0;
+  if (order_mode == 0) {
+    ws.order = nullptr;
+  } else {
+    ws.order_mode = order_mode;
+    TSAMD_HIP_TRY(hipMemsetAsync(ws.order_hdr, 0, order_clear_bytes(ws.P), stream));
+  }
   hipLaunchKernelGGL(spmm_partition_kernel, dim3((unsigned int)ceil_div(ws.P + 1, 256)), dim3(256),
-                     0, stream, rowptr, M, E, ws);
+                     0, stream, rowptr, col, M, E, ws);
   TSAMD_LAUNCH_CHECK();
+  if (order_mode != 0) {
+    hipLaunchKernelGGL(spmm_order_scatter_kernel, dim3((unsigned int)ceil_div(ws.P, (int64_t)1024)), dim3(1024), 0, stream,
+                       ws);
+    TSAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spmm_order_rank_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(ws.P, (int64_t)4), 2048)), dim3(256),
+                       0, stream, ws);
+    TSAMD_LAUNCH_CHECK();
+  }
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[1], stream));
   const unsigned int gx = (unsigned int)ceil_div(ws.P, kWavesPerBlock);
   // int32 winner ids (tsamd_spmm_minmax_arg32): min / max of the floating types (what autograd differentiates)
@@ -2248,11 +2457,11 @@ int spmm_entry(const SpmmCall &c, Launch launch) {
   const bool use_cache = c.cache != nullptr && !c.relabelled && cache_need > 0 && c.cache_bytes >= cache_need &&
                          ((uintptr_t)c.cache % 256) == 0 && ((uintptr_t)c.mat % 16) == 0;
   const bool no_xperm_in_ws = c.relabelled || use_cache || c.partial;
-  const size_t need = carve(nullptr, dtype, reduce, B, M, N, K, E, nullptr, no_xperm_in_ws);
+  const size_t need = carve(nullptr, dtype, reduce, B, M, N, K, E, nullptr, no_xperm_in_ws, c.wmask != nullptr);
   if (!c.workspace || c.workspace_bytes < need) return TSAMD_ERR_WORKSPACE;
   if ((uintptr_t)c.workspace % 256 != 0) return TSAMD_ERR_WORKSPACE;
   Workspace ws;
-  carve(c.workspace, dtype, reduce, B, M, N, K, E, &ws, no_xperm_in_ws);
+  carve(c.workspace, dtype, reduce, B, M, N, K, E, &ws, no_xperm_in_ws, c.wmask != nullptr);
   if (use_cache) {
     char *cb = reinterpret_cast<char *>(c.cache);
     ws.relabel_flag = reinterpret_cast<int *>(cb);
