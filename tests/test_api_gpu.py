@@ -351,9 +351,11 @@ def test_reductions_and_broadcast_mul(ts, dev):
 
 
 def test_spspmm_rmat_all_size_classes(ts, dev):
-    """A * A^T on an R-MAT graph: hub rows go through the global expand/sort path, mid rows through
-    the 256-thread LDS kernel, the rest through the one-wave radix-sort kernel.  Oracle =
-    torch.sparse.mm on CPU; integer-valued entries keep every sum exact."""
+    """A * A^T on an R-MAT graph: hub rows (more than 1024 products) go through the binned path -- per-range bins,
+    small bins merged into groups for one wave each, bigger bins accumulated densely in LDS --, mid rows (513..1024)
+    through the 256-thread LDS kernel, the rest through the one-wave register-sort kernel.  Oracle = torch.sparse.mm
+    on CPU; integer-valued entries keep every sum exact.  (The same generator on the CPU's random stream gives
+    5950 / 754 / 1488 rows in the three classes: none of them is empty by a wide margin, so seed 4 stays.)"""
     from pytorch_sparse_amd import synth
     rp, c = synth.rmat_csr(13, 8, seed=4, device=dev)
     n = 1 << 13
@@ -363,7 +365,7 @@ def test_spspmm_rmat_all_size_classes(ts, dev):
     At = A.t()
     rpB = At.storage.rowptr()
     prod = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, A.storage.row(), (rpB[1:] - rpB[:-1])[c])
-    assert int((prod <= 512).sum()) > 0 and int(((prod > 512) & (prod <= 4096)).sum()) > 0 and int((prod > 4096).sum()) > 0
+    assert int((prod <= 512).sum()) > 0 and int(((prod > 512) & (prod <= 1024)).sum()) > 0 and int((prod > 1024).sum()) > 0
     C = A @ At
     Cc = torch.sparse.mm(A.cpu().to_torch_sparse_coo_tensor(), At.cpu().to_torch_sparse_coo_tensor())
     row, col, v = C.coo()

@@ -25,12 +25,20 @@ TABLE = {
     F32: [
         (1,            13, 1,      4, 1, 0, 1, 1, 1),
         (2,            13, 1,      4, 1, 0, 1, 1, 1),
+        (97,           13, 1,      4, 1, 0, 1, 1, 1),
         (256,          13, 1,      4, 1, 0, 1, 1, 1),
         (257,          13, 1,      4, 1, 0, 2, 1, 1),
         (1 << 13,      13, 1,      4, 1, 0, 2, 1, 1),
         ((1 << 13) + 1, 13, 2,     4, 1, 0, 2, 1, 1),
+        (2 << 13,      13, 2,      4, 1, 0, 2, 1, 1),   # the grid of tests/test_spspmm_narrow_gpu.py: R = 2^13, R + 1, 2R,
+        ((2 << 13) + 1, 13, 3,     4, 1, 0, 2, 1, 1),   # 2R + 1, 8R, 15R - 3, 16R, config 4's 500 000, 2^21, 2^22
         (1 << 16,      13, 8,      4, 1, 0, 2, 1, 1),
         ((1 << 16) + 1, 13, 9,     4, 1, 0, 3, 1, 1),
+        ((15 << 13) - 3, 13, 15,   4, 1, 0, 3, 1, 1),
+        (16 << 13,     13, 16,     4, 1, 0, 3, 1, 1),
+        (500000,       13, 62,     4, 1, 0, 3, 1, 1),
+        (1 << 21,      13, 256,    4, 1, 0, 3, 1, 1),   # 256 ranges: the last N at which no group can close by span
+        (1 << 22,      13, 512,    4, 1, 0, 3, 1, 1),
         ((1 << 23) - 1, 13, 1024,  4, 1, 0, 3, 1, 1),
         (1 << 23,      13, 1024,   4, 1, 0, 3, 1, 1),   # last N with 32-bit (column << 9 | index) keys, offsets in LDS
         ((1 << 23) + 1, 13, 1025,  4, 0, 1, 3, 1, 1),   # pairs radix sort; 4100 segment offsets stay in global memory
@@ -46,8 +54,17 @@ TABLE = {
     ],
     F64: [
         (1,            12, 1,      4, 1, 0, 1, 1, 1),
+        (2,            12, 1,      4, 1, 0, 1, 1, 1),
+        (97,           12, 1,      4, 1, 0, 1, 1, 1),
         (1 << 12,      12, 1,      4, 1, 0, 2, 1, 1),
         ((1 << 12) + 1, 12, 2,     4, 1, 0, 2, 1, 1),
+        (2 << 12,      12, 2,      4, 1, 0, 2, 1, 1),   # the grid of tests/test_spspmm_narrow_gpu.py, R = 2^12
+        ((2 << 12) + 1, 12, 3,     4, 1, 0, 2, 1, 1),
+        (8 << 12,      12, 8,      4, 1, 0, 2, 1, 1),
+        ((15 << 12) - 3, 12, 15,   4, 1, 0, 2, 1, 1),
+        (16 << 12,     12, 16,     4, 1, 0, 2, 1, 1),
+        (500000,       12, 123,    4, 1, 0, 3, 1, 1),
+        (1 << 21,      12, 512,    4, 1, 0, 3, 1, 1),
         ((1 << 22) - 1, 12, 1024,  4, 1, 0, 3, 1, 1),
         (1 << 22,      12, 1024,   4, 1, 0, 3, 1, 1),
         ((1 << 22) + 1, 12, 1025,  4, 0, 0, 3, 1, 1),
