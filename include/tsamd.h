@@ -571,6 +571,69 @@ int tsamd_spmm_heads(int dtype, const int64_t *ptr, const int64_t *ind, const in
                      const void *x, void *out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Fused attention over a pattern (csrc/attention.hip): scores, softmax over the row and aggregation in one pass.
+ * (rowptr, col) is the CSR order of the E entries; q [nseg, H, D], k and v [nsrc, H, D], out [nseg, H, D],
+ * lse [nseg, H] in the accumulator type (float, double for float64).  bias is NULL or holds one element of the
+ * operands' dtype per entry (bias_heads = 1, shared by the heads) or per entry and head (bias_heads = H, [E, H]).
+ * All arrays are contiguous; float32, float64, float16 and bfloat16; fp32 accumulators (fp64 for float64), one
+ * rounding on the store.  Work is split by entries, never by rows; deterministic (two calls give the same bits), no
+ * atomics, no host sync.  Needs rowptr[0] = 0 and rowptr[nseg] = E.
+ *
+ *   tsamd_attention_heads     s(i, h) = scale * <q[r, h, :], k[col[i], h, :]> + bias for the entries i of row r;
+ *                             out[r, h, :] = sum_i softmax_i(s(., h)) * v[col[i], h, :], lse[r, h] = log sum_i
+ *                             exp(s(i, h)).  The softmax is online (running maximum, e = __expf in fp32, exp in
+ *                             fp64); nothing of size E is written.  out is zeroed and lse set to -inf first: rows
+ *                             without entries are zeros.  A row cut by a chunk boundary leaves head / tail records
+ *                             ((m, l) per head and an accumulator row of H * D) that one fix-up launch folds in
+ *                             chunk order, every piece rescaled to the running maximum.  At most three launches
+ *                             (fill, tile, fix-up).  A NaN or +inf score makes its row and head NaN (lse NaN), a row
+ *                             of -inf scores only is NaN with lse = -inf, -inf beside finite scores weighs zero;
+ *                             nothing else is touched.
+ *   tsamd_attention_heads_bw  per entry i of row r and head h, from the forward's out and lse:
+ *                             p = e(s(i, h) - lse[r, h]), ds = p * (<grad_out[r, h], v[col[i], h]> -
+ *                             <grad_out[r, h], out[r, h]>), both [E, H] of the operands' dtype in storage order.
+ *                             lse[r, h] not finite: p = ds = NaN; s = -inf: p = ds = 0.  row [E] holds the row ids
+ *                             or is NULL (then they are searched in rowptr; not both NULL).  One launch, no
+ *                             workspace.  The gradients follow through tsamd_spmm_heads: grad_q = scale *
+ *                             spmm(rows; ds, k), grad_k = scale * spmm(columns; ds, q), grad_v = spmm(columns; p,
+ *                             grad_out), grad_bias = ds.
+ *
+ * Status, in this order: a negative size TSAMD_ERR_INVALID; a non-floating dtype, or nseg / nsrc / H / D / H * D
+ * above 2^31 - 1, more than 65535 column blocks, an out above 2^39 elements, or an E whose byte offsets leave int64,
+ * TSAMD_ERR_UNSUPPORTED; a bias with bias_heads other than 1 or H TSAMD_ERR_INVALID; then
+ *   forward:  nseg * H * D == 0 TSAMD_OK, nothing is written (D == 0 leaves lse undefined); a null out / lse
+ *             TSAMD_ERR_INVALID; E == 0 TSAMD_OK with out zero-filled and lse = -inf; a null rowptr / col / q / k / v
+ *             or nsrc == 0 TSAMD_ERR_INVALID; a missing or short workspace TSAMD_ERR_WORKSPACE;
+ *   backward: E == 0 or H == 0 TSAMD_OK without a launch; D == 0, a null array (row and rowptr both), nseg == 0 or
+ *             nsrc == 0 TSAMD_ERR_INVALID.
+ * Every one of these is decided on the host before the first device call.
+ *
+ * tsamd_attention_heads_route is host arithmetic only, through the function the driver plans with; a null route
+ * array or a negative size is TSAMD_ERR_INVALID, a non-floating dtype TSAMD_ERR_UNSUPPORTED.  Only the alignment of
+ * the pointers is looked at (NULL counts as aligned).  out[0] route: 0 packets (16-byte loads and stores;
+ * D * itemsize a multiple of 16 and q, k, v, out on a 16-byte boundary), 1 generic (element loads, any D >= 1);
+ * out[1] elements per load; out[2] lanes per head (the butterfly runs over these; a lane covers 16 / itemsize
+ * adjacent features on both routes); out[3] heads side by side in a group of lanes; out[4] column blocks =
+ * ceil(H / out[3]) * out[7]; out[5] entries per chunk = 8 * out[2] * out[3]; out[6] entries per workgroup tile
+ * (2048), also the largest number of rows a tile stages in LDS; out[7] feature blocks of a head (1 unless
+ * D * itemsize > 1024).  out[2..7] -- hence the workspace -- are a function of (dtype, H, D) alone.
+ *   workspace = 2 * align256(acc * nchunks * H * D) + 2 * align256(2 * acc * nchunks * H) + 2 * align256(8 * nchunks),
+ *   nchunks = ceil(E / out[5]), acc = 8 for float64, else 4 (0 bytes for a dtype or a size that is not supported).
+ * ------------------------------------------------------------------------ */
+int tsamd_attention_heads_route(int dtype, int64_t H, int64_t D, const void *q, const void *k, const void *v,
+                                const void *out, int64_t out_route[8]);
+size_t tsamd_attention_heads_workspace_bytes(int dtype, int64_t H, int64_t D, int64_t E);
+int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                          int64_t bias_heads, const void *q, const void *k, const void *v, double scale, void *out,
+                          void *lse, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                             const void *bias, int64_t bias_heads, const void *q, const void *k, const void *v,
+                             const void *out, const void *lse, const void *grad_out, double scale, void *p_out,
+                             void *ds_out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
+                             void *stream);
+
 /* ------------------------------------------------------------------------ *
  * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):

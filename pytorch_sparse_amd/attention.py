@@ -1,4 +1,4 @@
-"""Attention over a sparse pattern: the two ends of ``scores -> softmax -> aggregate``.
+"""Attention over a sparse pattern: the two ends of ``scores -> softmax -> aggregate``, and the three fused.
 
 ``sddmm(adj, q, k, scale)``   a score per stored entry and head, ``scale * <q[row], k[col]>``, as the values of ``adj``
                               (``tsamd::sddmm_heads``, csrc/sddmm.hip) -- no ``[nnz, H, D]`` gather is materialised;
@@ -13,6 +13,13 @@ Both are differentiable (once), and the two kernels close over each other: the g
 the multi-head SpMM with the score gradient as values, w.r.t. ``k`` the same on the columns (``colptr``, ``csr2csc``);
 the value gradient of ``matmul_heads`` is an SDDMM of ``grad_out`` with ``x``, its ``x`` gradient the SpMM on the columns.
 The column-side caches of the storage are only built when such a gradient will be asked for.
+
+``attention(adj, q, k, v, scale=None, bias=False)`` is the whole chain in one call (``tsamd::attention_heads``,
+csrc/attention.hip): the scores are formed, normalised with an online softmax over the row and multiplied into ``v``
+in one pass over the entries, so the forward writes nothing of size ``nnz``.  It keeps ``out`` and the row-wise
+``lse = log sum exp(score)`` for the backward, where one kernel (``tsamd::attention_heads_bw``) recomputes the
+probabilities ``p`` and the score gradients ``ds = p * (<grad_out, v> - <grad_out, out>)`` per entry and
+``tsamd::spmm_heads`` turns them into ``grad_q``, ``grad_k`` and ``grad_v``; ``ds`` itself is the gradient of the bias.
 """
 from typing import Optional
 
@@ -87,6 +94,49 @@ class _SpmmHeads(torch.autograd.Function):
         return grad_value, grad_x, None, None, None, None, None, None, None
 
 
+class _AttentionHeads(torch.autograd.Function):
+    """out = tsamd::attention_heads; backward: (p, ds) = tsamd::attention_heads_bw, then grad_q = scale * spmm_heads(rows;
+    ds, k), grad_k = scale * spmm_heads(columns; ds, q), grad_v = spmm_heads(columns; p, grad_out), grad_bias = ds"""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor], rowptr: Tensor,
+                col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor], csr2csc: Optional[Tensor],
+                scale: float):
+        b = None if bias is None else bias.detach()
+        out, lse = torch.ops.tsamd.attention_heads(rowptr, col, b, q.detach(), k.detach(), v.detach(), scale)
+        ctx.scale = scale
+        ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
+        ctx.save_for_backward(*([q, k, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
+                                ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        q, k, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        bias = rest.pop(0) if ctx.has_bias else None
+        row = rest.pop(0) if ctx.has_row else None
+        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
+        p, ds = torch.ops.tsamd.attention_heads_bw(row, rowptr, col, bias, q, k, v, out, lse, g, ctx.scale)
+        grad_q = grad_k = grad_v = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_q = torch.ops.tsamd.spmm_heads(rowptr, col, None, ds, k, q.size(0))
+            if ctx.scale != 1.0:
+                grad_q.mul_(ctx.scale)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            colptr, row_csc, csr2csc = rest
+            if ctx.needs_input_grad[1]:
+                grad_k = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, ds, q, k.size(0))
+                if ctx.scale != 1.0:
+                    grad_k.mul_(ctx.scale)
+            if ctx.needs_input_grad[2]:
+                grad_v = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, p, g, k.size(0))
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            grad_bias = ds if bias.dim() == 2 else ds.sum(1, dtype=lse.dtype).to(ds.dtype)
+        return grad_q, grad_k, grad_v, grad_bias, None, None, None, None, None, None, None
+
+
 def _check_operand(t: Tensor, name: str, rows: int, what: str) -> None:
     if not isinstance(t, Tensor):
         raise TypeError('%s must be a Tensor' % name)
@@ -149,5 +199,59 @@ def matmul_heads(adj: SparseTensor, x: Tensor) -> Tensor:
     return torch.ops.tsamd.spmm_heads(rowptr, col, None, value, x, nseg)
 
 
+def attention(adj: SparseTensor, q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None,
+              bias: bool = False) -> Tensor:
+    """Attention over the pattern of ``adj`` in one fused pass: for row ``m`` and head ``h`` the score of a stored entry
+    ``(m, n)`` is ``scale * <q[m, h], k[n, h]>`` (``scale=None``: ``D ** -0.5``), plus, with ``bias=True``, the entry's own
+    value (``[nnz]`` shared by the heads or ``[nnz, H]``; ``-inf`` masks an entry); ``out[m, h] = sum_n softmax_n(score) *
+    v[n, h]``.  ``q [M, H, D]``, ``k`` and ``v [N, H, D]`` -> ``[M, H, D]``; 2-D operands mean one head.  Rows without
+    entries are zeros.  Differentiable (once) w.r.t. ``q``, ``k``, ``v`` and, with ``bias=True``, the values."""
+    for t, name in ((q, 'q'), (k, 'k'), (v, 'v')):
+        if not isinstance(t, Tensor):
+            raise TypeError('%s must be a Tensor' % name)
+    if not (q.dim() == k.dim() == v.dim()) or q.dim() not in (2, 3):
+        raise ValueError('q, k and v must all be [rows, D] or [rows, H, D], got %d, %d and %d dimensions'
+                         % (q.dim(), k.dim(), v.dim()))
+    _check_operand(q, 'q', adj.sparse_size(0), 'rows')
+    _check_operand(k, 'k', adj.sparse_size(1), 'columns')
+    _check_operand(v, 'v', adj.sparse_size(1), 'columns')
+    if q.dtype != k.dtype or q.dtype != v.dtype:
+        raise ValueError('q, k and v differ in dtype: %s, %s and %s' % (q.dtype, k.dtype, v.dtype))
+    if q.shape[1:] != k.shape[1:]:
+        raise ValueError('q is %s per row, k is %s: heads and features must agree'
+                         % (tuple(q.shape[1:]), tuple(k.shape[1:])))
+    if v.shape != k.shape:
+        raise ValueError('v must have the shape of k, got %s and %s: a value width of its own is not supported'
+                         % (tuple(v.shape), tuple(k.shape)))
+    flat = q.dim() == 2
+    if flat:
+        q, k, v = q.unsqueeze(1), k.unsqueeze(1), v.unsqueeze(1)
+    H, D = q.size(1), q.size(2)
+    if D == 0:
+        raise ValueError('attention needs at least one feature per head')
+    b = None
+    if bias:
+        b = adj.storage.value()
+        if b is None:
+            raise ValueError('bias=True needs a SparseTensor with values, this one has none')
+        if not b.is_floating_point():
+            raise ValueError('the bias must be floating point, got %s values' % b.dtype)
+        if b.dim() not in (1, 2) or (b.dim() == 2 and b.size(1) != H):
+            raise ValueError('the bias must be [nnz] or [nnz, %d] values (q has %d heads), got %s'
+                             % (H, H, tuple(b.shape)))
+        b = b.to(q.dtype)
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    st = adj.storage
+    rowptr, col = st.rowptr(), st.col()
+    grad = torch.is_grad_enabled()
+    if grad and (q.requires_grad or k.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
+        csc = _csc_side(st) if k.requires_grad or v.requires_grad else (None, None, None)
+        out = _AttentionHeads.apply(q, k, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], scale)
+    else:
+        out = torch.ops.tsamd.attention_heads(rowptr, col, b, q, k, v, scale)[0]
+    return out.squeeze(1) if flat else out
+
+
+SparseTensor.attention = lambda self, q, k, v, scale=None, bias=False: attention(self, q, k, v, scale, bias)
 SparseTensor.sddmm = lambda self, q, k, scale=1.0: sddmm(self, q, k, scale)
 SparseTensor.matmul_heads = lambda self, x: matmul_heads(self, x)

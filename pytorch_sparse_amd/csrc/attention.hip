@@ -1,0 +1,690 @@
+// Fused attention over a sparse pattern: scores, softmax over the row and aggregation in one pass,
+//   s(i, h)      = scale * <q[r, h, :], k[col[i], h, :]> (+ bias[i] or bias[i, h])     for i in [rowptr[r], rowptr[r+1]),
+//   out[r, h, :] = sum_i softmax_i(s(., h)) * v[col[i], h, :],    lse[r, h] = log sum_i exp(s(i, h)),
+// q [M, H, D], k and v [N, H, D], out [M, H, D], lse [M, H] (fp32, fp64 for double).  Nothing of size E is written.
+//
+// The ENTRIES are split evenly, on the tiling of spmm_heads.hip: a workgroup owns a tile of 2048 consecutive entries
+// and stages the pointer slice that meets them in LDS (expand.h), a wave owns 512 of them.  A group of
+// LPR = LPH * HPP lanes walks a CHUNK of L = 8 * LPR consecutive entries, one after the other, in 8 windows of LPR
+// entries (ids, segments and flags read once per window, a lane per entry, handed round by lane reads); the gathers
+// of four entries -- their k and v parts -- are issued before the first of them is used.
+//
+//   lanes   LPH lanes (a power of two) cover the D features of one head, VEC = 16 / itemsize adjacent features per
+//           lane; HPP heads (a power of two) sit side by side in the group, so the lanes of a head are a block that
+//           starts at a multiple of LPH.  H > HPP takes ceil(H / HPP) column blocks (blockIdx.y): whole heads only.
+//           D > 64 * VEC (the WIDE instantiation) splits the features of a head over FB = ceil(D / (64 * VEC))
+//           further blocks; each of them forms the whole score (a strided loop over q and k) and keeps its own
+//           features of the accumulator, so a head's softmax state never crosses a block.
+//   score   the lanes of head h hold their part of q[row, h, :], reloaded where the segment changes, gather the same
+//           part of k[col, h, :] and reduce with a xor butterfly whose masks stay below LPH.  scale, then the bias.
+//   online  per group and head (m, l, acc[VEC]); an entry of score s and value part x is folded as
+//           m' = max(m, s), l = l * e(m - m') + e(s - m'), acc = acc * e(m - m') + e(s - m') * x, the combine of
+//           softmax.hip with exp(-inf - x) taken as 0 also for x = -inf.  e is __expf for fp32 accumulators and exp
+//           for fp64 -- no exp2 with a folded scale.
+//   rows    where a segment that began inside the chunk ends, acc / l goes to out and m + log(l) to lse.  A segment
+//           that began before the chunk leaves the chunk's HEAD record, one still open at its end the TAIL record:
+//           (m, l) per head and the accumulator row.  The fix-up launch (a wave per chunk with a head record, lanes
+//           over the H * D columns) folds the tail records of the chunks [rowptr[s] / L, b) in chunk order, then the
+//           head record, every piece rescaled to the running maximum, and writes out and lse.
+//   fill    out is zeroed and lse set to -inf first (one launch): rows without entries are zeros.
+//
+// Non-finite scores follow softmax.hip per row and head: a NaN or +inf score ends with m NaN / +inf, which the final
+// expression turns into NaN for the whole row of that head (lse NaN); a row of -inf only ends with l = 0, 0 / 0 = NaN
+// and lse = -inf; -inf beside finite scores weighs 0.  State is cleared where a segment ends, so nothing reaches a
+// neighbour of the chunk or the record.
+//
+//   packet route    D * itemsize a multiple of 16 and q, k, v, out on a 16-byte boundary: 16-byte loads and stores.
+//   generic route   every other D >= 1 or operands off the boundary: the same lane-to-feature map, one element per
+//                   load (VEC = 1 loads), features beyond D read as zero.
+// The lane map -- hence the chunk length and the workspace -- is a function of (dtype, H, D) alone.
+//
+// Workspace: nchunks = ceil(E / L),
+//   2 * align256(acc * nchunks * H * D)   head and tail accumulator rows
+// + 2 * align256(2 * acc * nchunks * H)   head and tail (m, l) pairs
+// + 2 * align256(8 * nchunks)             head and tail segment ids (-1: no record)
+// Fixed combine tree (the entries of a chunk in order, the records in chunk order): two calls give the same bits.  No
+// atomics, no host sync, three launches (fill, tile, fix-up).
+//
+// Backward (tsamd_attention_heads_bw), on the layout of sddmm_heads_kernel: a wave owns 64 consecutive entries, LPH
+// lanes per head, heads and entries side by side.  An entry's ids are read once; three dot products share the
+// butterfly: s = scale * <q, k> + bias, dp = <grad_out[row], v[col]>, delta = <grad_out[row], out[row]>.  It stores
+// p = e(s - lse[row]) and ds = p * (dp - delta) as [E, H]; lse not finite: NaN both; s = -inf: 0 both.  One launch.
+#include "common.h"
+#include "expand.h"
+
+#include <type_traits>
+
+namespace tsamd {
+namespace {
+
+constexpr int kAtWaves = 4;
+constexpr int kAtWaveEntries = kExpandTile / kAtWaves;  // 512
+constexpr int kAtWindows = 8;                           // windows of LPR entries per chunk
+constexpr int kAtBatch = 4;                             // entries whose gathers are in flight
+constexpr int kAtBwHeads = 16;                          // heads side by side in the backward at most
+static_assert(kAtWaveEntries == kWave * kAtWindows, "a chunk is 8 windows of the group's lanes");
+
+constexpr int kAtValid = 1, kAtEnd = 2, kAtFresh = 4;
+
+struct AtPlan {
+  int generic;
+  int vec;          // elements per load
+  int lg_lph;       // lanes per head
+  int lg_hpp;       // heads side by side
+  int fblocks;      // feature blocks of a head (1 unless D > 64 * (16 / itemsize))
+  int64_t blocks;   // column blocks = ceil(H / HPP) * fblocks
+  int64_t chunk;    // entries per group
+};
+
+__device__ __forceinline__ float at_exp(float x) { return __expf(x); }
+__device__ __forceinline__ double at_exp(double x) { return exp(x); }
+__device__ __forceinline__ float at_log(float x) { return logf(x); }
+__device__ __forceinline__ double at_log(double x) { return log(x); }
+
+bool at_float_dtype(int dtype) {
+  return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
+}
+
+bool at_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int at_lg_ceil(int64_t x) {
+  int lg = 0;
+  while (((int64_t)1 << lg) < x) ++lg;
+  return lg;
+}
+
+// the lane map: a function of (dtype, H, D) alone
+void at_lanes(int dtype, int64_t H, int64_t D, int max_lg_hpp, AtPlan *p) {
+  const int64_t vec = 16 / (int64_t)dtype_size(dtype);
+  const int64_t slots = D > 0 ? ceil_div(D, vec) : 1;
+  p->lg_lph = slots >= kWave ? 6 : at_lg_ceil(slots);
+  p->lg_hpp = at_lg_ceil(H > 0 ? H : 1);
+  if (p->lg_hpp > max_lg_hpp) p->lg_hpp = max_lg_hpp;
+  if (p->lg_hpp > 6 - p->lg_lph) p->lg_hpp = 6 - p->lg_lph;
+  p->fblocks = (int)ceil_div(slots, (int64_t)kWave);
+  p->blocks = ceil_div(H > 0 ? H : 1, (int64_t)1 << p->lg_hpp) * p->fblocks;
+  p->chunk = (int64_t)kAtWindows << (p->lg_lph + p->lg_hpp);
+}
+
+// the one place the route is decided: the driver and tsamd_attention_heads_route both plan through it
+AtPlan at_plan(int dtype, int64_t H, int64_t D, const void *q, const void *k, const void *v, const void *out) {
+  AtPlan p;
+  const int64_t vec = 16 / (int64_t)dtype_size(dtype);
+  const bool packets =
+      D > 0 && D % vec == 0 && at_aligned16(q) && at_aligned16(k) && at_aligned16(v) && at_aligned16(out);
+  p.generic = packets ? 0 : 1;
+  p.vec = packets ? (int)vec : 1;
+  at_lanes(dtype, H, D, 6, &p);
+  return p;
+}
+
+size_t at_workspace_bytes(size_t acc, int64_t chunk, int64_t H, int64_t D, int64_t E) {
+  const size_t nchunks = (size_t)ceil_div(E > 0 ? E : 1, chunk);
+  const size_t h = (size_t)(H > 0 ? H : 1), w = h * (size_t)(D > 0 ? D : 1);
+  return 2 * align_up(acc * nchunks * w, 256) + 2 * align_up(2 * acc * nchunks * h, 256) +
+         2 * align_up(sizeof(int64_t) * nchunks, 256);
+}
+
+// VEC adjacent features of a head row, from feature d0: one 16-byte load, or element loads that read zero beyond D
+template <typename T, bool PACKED>
+__device__ __forceinline__ Pack<T, 16 / (int)sizeof(T)> at_load(const T *__restrict__ head_row, int64_t d0,
+                                                                  int64_t D) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  using P = Pack<T, VEC>;
+  if constexpr (PACKED) {
+    return *reinterpret_cast<const P *>(head_row + d0);
+  } else {
+    P r = P();
+#pragma unroll
+    for (int v = 0; v < VEC; ++v)
+      if (d0 + v < D) r.v[v] = head_row[d0 + v];
+    return r;
+  }
+}
+
+template <typename T, bool PACKED, typename A>
+__device__ __forceinline__ void at_store(T *__restrict__ head_row, int64_t d0, int64_t D, const A *x) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  using P = Pack<T, VEC>;
+  if constexpr (PACKED) {
+    P o;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) o.v[v] = Traits<T>::from_acc(x[v]);
+    *reinterpret_cast<P *>(head_row + d0) = o;
+  } else {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v)
+      if (d0 + v < D) head_row[d0 + v] = Traits<T>::from_acc(x[v]);
+  }
+}
+
+// l of the final expression: m = +inf or NaN makes the row NaN (softmax.hip: SmForward::finish)
+template <typename A>
+__device__ __forceinline__ A at_final_l(A m, A l) {
+  return m < std::numeric_limits<A>::infinity() ? l : std::numeric_limits<A>::quiet_NaN();
+}
+
+// out = 0, lse = -inf.  out is cleared in 16-byte units of its enclosing aligned range, the two ragged ends by bytes.
+template <typename A>
+__global__ __launch_bounds__(256) void attention_fill_kernel(unsigned char *__restrict__ out, int64_t out_bytes,
+                                                              A *__restrict__ lse, int64_t nlse) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const uintptr_t begin = reinterpret_cast<uintptr_t>(out), end = begin + (uintptr_t)out_bytes;
+  const uintptr_t unit = (begin & ~(uintptr_t)15) + (uintptr_t)i * 16;
+  if (unit < end) {
+    if (unit >= begin && unit + 16 <= end) {
+      *reinterpret_cast<uint4 *>(unit) = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+      for (uintptr_t b = unit < begin ? begin : unit; b < unit + 16 && b < end; ++b)
+        *reinterpret_cast<unsigned char *>(b) = 0;
+    }
+  }
+  if (i < nlse) lse[i] = -std::numeric_limits<A>::infinity();
+}
+
+template <typename T, bool PACKED, bool WIDE>
+__global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
+    const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind, const T *__restrict__ bias, int64_t bias_heads,
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ x, typename Traits<T>::acc_t scale,
+    T *__restrict__ out, typename Traits<T>::acc_t *__restrict__ lse, typename Traits<T>::acc_t *__restrict__ head_acc,
+    typename Traits<T>::acc_t *__restrict__ tail_acc, typename Traits<T>::acc_t *__restrict__ head_ml,
+    typename Traits<T>::acc_t *__restrict__ tail_ml, int64_t *__restrict__ head_seg, int64_t *__restrict__ tail_seg,
+    int64_t nseg, int64_t E, int64_t H, int64_t D, int lg_lph, int lg_hpp, int fblocks) {
+  using A = typename Traits<T>::acc_t;
+  constexpr int VEC = 16 / (int)sizeof(T);
+  using P = Pack<T, VEC>;
+  constexpr A kNegInf = -std::numeric_limits<A>::infinity();
+  __shared__ int64_t sp[kExpandTile + 1];
+  __shared__ int64_t span[2];
+  const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
+  const int64_t e1 = e0 + kExpandTile < E ? e0 + kExpandTile : E;
+  int64_t lo, hi;
+  tile_span(ptr, nseg, e0, e1, span, &lo, &hi);
+  const int64_t S = hi - lo + 1;
+  const bool staged = S <= kExpandTile;
+  if (staged) {
+    for (int i = threadIdx.x; i <= (int)S; i += blockDim.x) sp[i] = ptr[lo + i];
+    __syncthreads();
+  }
+  const int lane = (int)(threadIdx.x & 63);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t w0 = e0 + (int64_t)wave * kAtWaveEntries;
+  if (w0 >= e1) return;  // such a wave has no chunk
+
+  const int lg_lpr = lg_lph + lg_hpp;
+  const int lpr = 1 << lg_lpr, lph = 1 << lg_lph;
+  const int lg_g = 6 - lg_lpr;
+  const int g = lane >> lg_lpr;
+  const int gl = lane & (lpr - 1);  // lane of the group
+  const int hs = gl >> lg_lph;      // head slot
+  const int kl = gl & (lph - 1);    // lane of the head
+  const int64_t L = (int64_t)kAtWindows << lg_lpr;
+  const int64_t chunk = (((int64_t)blockIdx.x * kAtWaves + wave) << lg_g) + g;
+  const int64_t c0 = chunk * L;
+  const int64_t c1 = c0 + L < e1 ? c0 + L : e1;  // c0 >= e1: a group without a chunk (chunk >= nchunks)
+  const int64_t W = H * D;
+  const int hb = (int)blockIdx.y / fblocks, fb = (int)blockIdx.y - hb * fblocks;
+  const int64_t h = ((int64_t)hb << lg_hpp) + hs;
+  const bool hok = h < H;
+  const int64_t slots = (D + VEC - 1) / VEC;
+  const int64_t slot = (int64_t)fb * kWave + kl;
+  const bool colok = hok && slot < slots;  // the packet route has D % VEC == 0: a packet is inside the head or outside
+  const int64_t d0 = slot * VEC;
+  const int64_t hoff = hok ? h * D : 0;
+  const bool scribe = gl == 0 && blockIdx.y == 0;  // writes the segment ids of the chunk's records
+  const bool clerk = hok && kl == 0 && fb == 0;    // writes (m, l) and lse of its head
+
+  A m = kNegInf, l = A(0);
+  A acc[VEC], qa[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc[v] = qa[v] = A(0);
+  bool open = false, had_head = false;
+  int32_t cur = -1;   // segment of the last entry taken
+  int32_t qrow = -1;  // segment whose q the lane holds
+
+  for (int w = 0; w < kAtWindows; ++w) {
+    // one entry of the window per lane of the group
+    const int64_t e = c0 + (int64_t)w * lpr + gl;
+    int32_t fl_l = 0, seg_l = 0;
+    uint32_t c_l = 0;
+    if (e < c1) {
+      int64_t seg, sstart, send;
+      if (staged) {
+        const int i = segment_of_lds(sp, (int)S, e);
+        seg = lo + i;
+        sstart = sp[i];
+        send = sp[i + 1];
+      } else {
+        seg = lo + segment_of(ptr + lo, S, e);
+        sstart = ptr[seg];
+        send = ptr[seg + 1];
+      }
+      seg_l = (int32_t)seg;
+      c_l = (uint32_t)ind[e];
+      fl_l = kAtValid | (e + 1 == send ? kAtEnd : 0) | (sstart >= c0 ? kAtFresh : 0);
+    }
+    for (int j0 = 0; j0 < lpr; j0 += kAtBatch) {  // wave-uniform: every lane answers the lane reads
+      int32_t fl[kAtBatch], sg[kAtBatch];
+      uint32_t cc[kAtBatch];
+      P kx[kAtBatch], xv[kAtBatch];
+      A bb[kAtBatch];
+#pragma unroll
+      for (int u = 0; u < kAtBatch; ++u) {
+        const int j = j0 + u;
+        const int src = (g << lg_lpr) + (j < lpr ? j : 0);
+        fl[u] = lane_read(fl_l, src);
+        if (j >= lpr) fl[u] = 0;
+        sg[u] = lane_read(seg_l, src);
+        cc[u] = lane_read(c_l, src);
+        kx[u] = P();
+        xv[u] = P();
+        bb[u] = A(0);
+        if ((fl[u] & kAtValid) && hok) {
+          const uint64_t at = (uint64_t)cc[u] * (uint64_t)W + (uint64_t)hoff;
+          if (colok) {
+            if constexpr (!WIDE) kx[u] = at_load<T, PACKED>(k + at, d0, D);
+            xv[u] = at_load<T, PACKED>(x + at, d0, D);
+          }
+          if (bias) {
+            const int64_t p = c0 + (int64_t)w * lpr + j;
+            bb[u] = Traits<T>::to_acc(bias[bias_heads > 1 ? p * bias_heads + h : p]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kAtBatch; ++u) {
+        const bool valid = (fl[u] & kAtValid) != 0;
+        A part = A(0);
+        if constexpr (WIDE) {
+          if (valid && hok) {
+            const T *qr = q + (uint64_t)sg[u] * (uint64_t)W + (uint64_t)hoff;
+            const T *kr = k + (uint64_t)cc[u] * (uint64_t)W + (uint64_t)hoff;
+            for (int64_t sl = kl; sl < slots; sl += kWave) {
+              const P a = at_load<T, PACKED>(qr, sl * VEC, D), b = at_load<T, PACKED>(kr, sl * VEC, D);
+#pragma unroll
+              for (int v = 0; v < VEC; ++v) part += Traits<T>::to_acc(a.v[v]) * Traits<T>::to_acc(b.v[v]);
+            }
+          }
+        } else {
+          if (valid && sg[u] != qrow) {  // the segment changes: this lane's part of q[row, h, :]
+            qrow = sg[u];
+            P a = P();
+            if (colok) a = at_load<T, PACKED>(q + (uint64_t)qrow * (uint64_t)W + (uint64_t)hoff, d0, D);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) qa[v] = Traits<T>::to_acc(a.v[v]);
+          }
+          if (valid) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) part += qa[v] * Traits<T>::to_acc(kx[u].v[v]);
+          }
+        }
+        for (int off = lph >> 1; off > 0; off >>= 1) part += lane_xor(part, off);  // inside the head: off < lph
+        if (valid) {  // an entry beyond the chunk adds nothing
+          const A s = part * scale + bb[u];
+          cur = sg[u];
+          open = true;
+          const bool first = m >= s;  // false when either is NaN: the factor below is NaN then
+          const A mhi = first ? m : s, mlo = first ? s : m;
+          const A f = mlo == kNegInf ? A(0) : at_exp(mlo - mhi);
+          const A fa = first ? A(1) : f, fb_ = first ? f : A(1);  // weights of the state and of the entry
+          m = mhi;
+          l = l * fa + fb_;
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) acc[v] = acc[v] * fa + fb_ * Traits<T>::to_acc(xv[u].v[v]);
+        }
+        if (fl[u] & kAtEnd) {
+          if (fl[u] & kAtFresh) {
+            const A lf = at_final_l(m, l);
+            if (colok) {
+              A o[VEC];
+#pragma unroll
+              for (int v = 0; v < VEC; ++v) o[v] = acc[v] / lf;
+              at_store<T, PACKED>(out + (uint64_t)sg[u] * (uint64_t)W + (uint64_t)hoff, d0, D, o);
+            }
+            if (clerk) lse[(uint64_t)sg[u] * (uint64_t)H + (uint64_t)h] = m + at_log(lf);
+          } else {  // began before this chunk: the fix-up kernel finishes it
+            had_head = true;
+            if (colok) {
+#pragma unroll
+              for (int v = 0; v < VEC; ++v)
+                if (d0 + v < D) head_acc[(uint64_t)chunk * (uint64_t)W + (uint64_t)(hoff + d0 + v)] = acc[v];
+            }
+            if (clerk) {
+              head_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2] = m;
+              head_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2 + 1] = l;
+            }
+            if (scribe) head_seg[chunk] = sg[u];
+          }
+          m = kNegInf;
+          l = A(0);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) acc[v] = A(0);
+          open = false;
+        }
+      }
+    }
+  }
+  if (c0 < e1) {
+    if (open && colok) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        if (d0 + v < D) tail_acc[(uint64_t)chunk * (uint64_t)W + (uint64_t)(hoff + d0 + v)] = acc[v];
+    }
+    if (open && clerk) {
+      tail_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2] = m;
+      tail_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2 + 1] = l;
+    }
+    if (scribe) {
+      tail_seg[chunk] = open ? (int64_t)cur : -1;
+      if (!had_head) head_seg[chunk] = -1;
+    }
+  }
+}
+
+// (m, l, a) (+) (m2, l2, a2), every piece rescaled to the larger maximum: the combine of softmax.hip with a column of
+// the accumulator row beside l
+template <typename A>
+__device__ __forceinline__ void at_combine(A &m, A &l, A &a, A m2, A l2, A a2) {
+  const bool first = m >= m2;
+  const A mhi = first ? m : m2, mlo = first ? m2 : m;
+  const A f = mlo == -std::numeric_limits<A>::infinity() ? A(0) : at_exp(mlo - mhi);
+  const A fa = first ? A(1) : f, fb = first ? f : A(1);
+  m = mhi;
+  l = l * fa + l2 * fb;
+  a = a * fa + a2 * fb;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kAtWaves *kWave) void attention_fixup_kernel(
+    const int64_t *__restrict__ ptr, T *__restrict__ out, typename Traits<T>::acc_t *__restrict__ lse,
+    const typename Traits<T>::acc_t *__restrict__ head_acc, const typename Traits<T>::acc_t *__restrict__ tail_acc,
+    const typename Traits<T>::acc_t *__restrict__ head_ml, const typename Traits<T>::acc_t *__restrict__ tail_ml,
+    const int64_t *__restrict__ head_seg, int64_t H, int64_t D, int64_t L, int64_t nchunks) {
+  using A = typename Traits<T>::acc_t;
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t b = (int64_t)blockIdx.x * kAtWaves + (threadIdx.x >> 6);
+  if (b >= nchunks) return;
+  const int64_t s = head_seg[b];
+  if (s < 0) return;
+  const int64_t W = H * D;
+  const int64_t first = ptr[s] / L;  // every chunk in [first, b) ended inside s: its tail record is a piece of s
+  for (int64_t col = lane; col < W; col += kWave) {
+    const int64_t h = col / D;
+    A m = -std::numeric_limits<A>::infinity(), l = A(0), a = A(0);
+    for (int64_t i = first; i < b; ++i) {
+      const uint64_t at = ((uint64_t)i * (uint64_t)H + (uint64_t)h) * 2;
+      at_combine(m, l, a, tail_ml[at], tail_ml[at + 1], tail_acc[(uint64_t)i * (uint64_t)W + (uint64_t)col]);
+    }
+    const uint64_t at = ((uint64_t)b * (uint64_t)H + (uint64_t)h) * 2;
+    at_combine(m, l, a, head_ml[at], head_ml[at + 1], head_acc[(uint64_t)b * (uint64_t)W + (uint64_t)col]);
+    const A lf = at_final_l(m, l);
+    out[(uint64_t)s * (uint64_t)W + (uint64_t)col] = Traits<T>::from_acc(a / lf);
+    if (col - h * D == 0) lse[(uint64_t)s * (uint64_t)H + (uint64_t)h] = m + at_log(lf);
+  }
+}
+
+template <typename T>
+int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, const void *bias, int64_t bias_heads,
+                     const void *q, const void *k, const void *v, double scale, void *out, void *lse, int64_t nseg,
+                     int64_t H, int64_t D, int64_t E, void *workspace, hipStream_t stream) {
+  using A = typename Traits<T>::acc_t;
+  const int64_t W = H * D;
+  const dim3 block(kAtWaves * kWave);
+  T *oo = reinterpret_cast<T *>(out);
+  A *ll = reinterpret_cast<A *>(lse);
+  {  // rows without entries: out = 0, lse = -inf
+    const int64_t bytes = (int64_t)sizeof(T) * nseg * W;
+    const int64_t units = bytes / 16 + 2, n = units > nseg * H ? units : nseg * H;
+    hipLaunchKernelGGL((attention_fill_kernel<A>), dim3((unsigned int)ceil_div(n, (int64_t)256)), block, 0, stream,
+                       reinterpret_cast<unsigned char *>(out), bytes, ll, nseg * H);
+    TSAMD_LAUNCH_CHECK();
+  }
+  if (E == 0) return TSAMD_OK;
+  const int64_t nchunks = ceil_div(E, p.chunk);
+  const size_t rec = align_up(sizeof(A) * (size_t)(nchunks * W), 256);
+  const size_t mlrec = align_up(2 * sizeof(A) * (size_t)(nchunks * H), 256);
+  char *wp = reinterpret_cast<char *>(workspace);
+  A *head_acc = reinterpret_cast<A *>(wp);
+  A *tail_acc = reinterpret_cast<A *>(wp + rec);
+  A *head_ml = reinterpret_cast<A *>(wp + 2 * rec);
+  A *tail_ml = reinterpret_cast<A *>(wp + 2 * rec + mlrec);
+  int64_t *head_seg = reinterpret_cast<int64_t *>(wp + 2 * rec + 2 * mlrec);
+  int64_t *tail_seg = head_seg + align_up(sizeof(int64_t) * (size_t)nchunks, 256) / sizeof(int64_t);
+  const dim3 tiles((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)p.blocks);
+  const T *bb = reinterpret_cast<const T *>(bias), *qq = reinterpret_cast<const T *>(q),
+          *kk = reinterpret_cast<const T *>(k), *xx = reinterpret_cast<const T *>(v);
+#define TSAMD_AT_LAUNCH(PACKED, WIDE)                                                                              \
+  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE>), tiles, block, 0, stream, ptr, ind, bb, bias_heads, \
+                     qq, kk, xx, (A)scale, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg, tail_seg, nseg, \
+                     E, H, D, p.lg_lph, p.lg_hpp, p.fblocks)
+  if (p.fblocks > 1) {
+    if (p.generic) TSAMD_AT_LAUNCH(false, true); else TSAMD_AT_LAUNCH(true, true);
+  } else {
+    if (p.generic) TSAMD_AT_LAUNCH(false, false); else TSAMD_AT_LAUNCH(true, false);
+  }
+#undef TSAMD_AT_LAUNCH
+  TSAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL((attention_fixup_kernel<T>), dim3((unsigned int)ceil_div(nchunks, (int64_t)kAtWaves)), block, 0,
+                     stream, ptr, oo, ll, (const A *)head_acc, (const A *)tail_acc, (const A *)head_ml,
+                     (const A *)tail_ml, (const int64_t *)head_seg, H, D, p.chunk, nchunks);
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+// ---- backward: p and ds per entry and head ---------------------------------------------------------------------------
+template <typename T, bool PACKED>
+__global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
+    const int64_t *__restrict__ row, const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind,
+    const T *__restrict__ bias, int64_t bias_heads, const T *__restrict__ q, const T *__restrict__ k,
+    const T *__restrict__ x, const T *__restrict__ o, const typename Traits<T>::acc_t *__restrict__ lse,
+    const T *__restrict__ go, typename Traits<T>::acc_t scale, T *__restrict__ p_out, T *__restrict__ ds_out,
+    int64_t nseg, int64_t H, int64_t D, int64_t E, int lg_lph, int lg_hpp) {
+  using A = typename Traits<T>::acc_t;
+  constexpr int VEC = 16 / (int)sizeof(T);
+  using P = Pack<T, VEC>;
+  const int lane = (int)(threadIdx.x & 63);
+  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t base = ((int64_t)blockIdx.x * kAtWaves + wib) * kWave;
+  if (base >= E) return;
+  const int64_t rem = E - base;
+  const int n = rem < kWave ? (int)rem : kWave;
+
+  // this lane's entry
+  uint32_t c_l = 0, r_l = 0;
+  if (lane < n) {
+    const int64_t e = base + lane;
+    c_l = (uint32_t)ind[e];
+    r_l = (uint32_t)(row != nullptr ? row[e] : segment_of(ptr, nseg, e));
+  }
+
+  const int lg_lpr = lg_lph + lg_hpp;
+  const int lph = 1 << lg_lph, hpp = 1 << lg_hpp;
+  const int lg_g = 6 - lg_lpr;
+  const int g = lane >> lg_lpr;                           // entry slot of the step
+  const int hs = (lane & ((1 << lg_lpr) - 1)) >> lg_lph;  // head slot of the pass
+  const int kl = lane & (lph - 1);                        // lane of the head
+  const int64_t slots = (D + VEC - 1) / VEC;
+  const int64_t W = H * D;
+  const int nsteps = (n + (1 << lg_g) - 1) >> lg_g;
+
+  for (int64_t h0 = 0; h0 < H; h0 += hpp) {
+    const int64_t h = h0 + hs;
+    const bool active = h < H;
+    for (int s = 0; s < nsteps; ++s) {
+      const int idx = (s << lg_g) + g;
+      const int src = idx < n ? idx : n - 1;
+      const uint32_t c = lane_read(c_l, src);
+      const uint32_t r = lane_read(r_l, src);
+      A ps = A(0), pd = A(0), pl = A(0);
+      if (active) {
+        const uint64_t ar = (uint64_t)r * (uint64_t)W + (uint64_t)(h * D);
+        const uint64_t ac = (uint64_t)c * (uint64_t)W + (uint64_t)(h * D);
+        for (int64_t sl = kl; sl < slots; sl += lph) {
+          const P qv = at_load<T, PACKED>(q + ar, sl * VEC, D), kv = at_load<T, PACKED>(k + ac, sl * VEC, D);
+          const P xv = at_load<T, PACKED>(x + ac, sl * VEC, D), gv = at_load<T, PACKED>(go + ar, sl * VEC, D);
+          const P ov = at_load<T, PACKED>(o + ar, sl * VEC, D);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) {
+            const A gj = Traits<T>::to_acc(gv.v[j]);
+            ps += Traits<T>::to_acc(qv.v[j]) * Traits<T>::to_acc(kv.v[j]);
+            pd += gj * Traits<T>::to_acc(xv.v[j]);
+            pl += gj * Traits<T>::to_acc(ov.v[j]);
+          }
+        }
+      }
+      for (int off = lph >> 1; off > 0; off >>= 1) {  // inside the head: off < lph
+        ps += lane_xor(ps, off);
+        pd += lane_xor(pd, off);
+        pl += lane_xor(pl, off);
+      }
+      if (active && kl == 0 && idx < n) {
+        const int64_t e = base + idx;
+        A sc = ps * scale;
+        if (bias) sc += Traits<T>::to_acc(bias[bias_heads > 1 ? e * bias_heads + h : e]);
+        const A ls = lse[(uint64_t)r * (uint64_t)H + (uint64_t)h];
+        A pv, dv;
+        if (!(ls - ls == A(0))) {  // -inf, +inf or NaN: the row is NaN in the forward
+          pv = dv = std::numeric_limits<A>::quiet_NaN();
+        } else if (sc == -std::numeric_limits<A>::infinity()) {
+          pv = dv = A(0);
+        } else {
+          pv = at_exp(sc - ls);
+          dv = pv * (pd - pl);
+        }
+        p_out[e * H + h] = Traits<T>::from_acc(pv);
+        ds_out[e * H + h] = Traits<T>::from_acc(dv);
+      }
+    }
+  }
+}
+
+template <typename T>
+int launch_attention_bw(const AtPlan &p, const int64_t *row, const int64_t *ptr, const int64_t *ind, const void *bias,
+                        int64_t bias_heads, const void *q, const void *k, const void *v, const void *out,
+                        const void *lse, const void *go, double scale, void *p_out, void *ds_out, int64_t nseg,
+                        int64_t H, int64_t D, int64_t E, hipStream_t stream) {
+  using A = typename Traits<T>::acc_t;
+  const dim3 grid((unsigned int)ceil_div(E, (int64_t)kAtWaves * kWave)), block(kAtWaves * kWave);
+#define TSAMD_AT_BW(PACKED)                                                                                         \
+  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED>), grid, block, 0, stream, row, ptr, ind,                       \
+                     reinterpret_cast<const T *>(bias), bias_heads, reinterpret_cast<const T *>(q),                 \
+                     reinterpret_cast<const T *>(k), reinterpret_cast<const T *>(v), reinterpret_cast<const T *>(out), \
+                     reinterpret_cast<const A *>(lse), reinterpret_cast<const T *>(go), (A)scale,                   \
+                     reinterpret_cast<T *>(p_out), reinterpret_cast<T *>(ds_out), nseg, H, D, E, p.lg_lph, p.lg_hpp)
+  if (p.generic) TSAMD_AT_BW(false); else TSAMD_AT_BW(true);
+#undef TSAMD_AT_BW
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+// sizes the 32-bit ids and the grids can carry
+bool at_indexable(int dtype, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E) {
+  const int64_t lim = 2147483647;
+  if (nseg > lim || nsrc > lim || H > lim || D > lim) return false;
+  if (H > 0 && D > lim / H) return false;                                  // W = H * D
+  if (H > 0 && E > (int64_t)9223372036854775807LL / 16 / H) return false;  // byte offsets into [E, H] arrays
+  if (H > 0 && D > 0 && nseg > lim / 2 * 512 / (H * D)) return false;      // the fill: 16-byte units of out / 256
+  AtPlan p;
+  at_lanes(dtype, H, D, 6, &p);
+  if (p.blocks > 65535) return false;  // column blocks are blockIdx.y
+  return ceil_div(E, (int64_t)kAtWaves * kWave) <= lim;
+}
+
+}  // namespace
+}  // namespace tsamd
+
+using namespace tsamd;
+
+extern "C" int tsamd_attention_heads_route(int dtype, int64_t H, int64_t D, const void *q, const void *k,
+                                           const void *v, const void *out, int64_t out_route[8]) {
+  if (!out_route || H < 0 || D < 0) return TSAMD_ERR_INVALID;
+  for (int i = 0; i < 8; ++i) out_route[i] = 0;
+  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (H > 0 && D > 2147483647 / H) return TSAMD_ERR_UNSUPPORTED;
+  const AtPlan p = at_plan(dtype, H, D, q, k, v, out);
+  out_route[0] = p.generic;
+  out_route[1] = p.vec;
+  out_route[2] = (int64_t)1 << p.lg_lph;
+  out_route[3] = (int64_t)1 << p.lg_hpp;
+  out_route[4] = p.blocks;
+  out_route[5] = p.chunk;
+  out_route[6] = kExpandTile;  // entries per tile; a tile stages its pointer slice when it meets at most this many segments
+  out_route[7] = p.fblocks;
+  return TSAMD_OK;
+}
+
+extern "C" size_t tsamd_attention_heads_workspace_bytes(int dtype, int64_t H, int64_t D, int64_t E) {
+  if (!at_float_dtype(dtype) || H < 0 || D < 0 || E < 0) return 0;
+  if (H > 0 && D > 2147483647 / H) return 0;
+  AtPlan p;
+  at_lanes(dtype, H, D, 6, &p);
+  return at_workspace_bytes(acc_size(dtype), p.chunk, H, D, E);
+}
+
+extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                                     int64_t bias_heads, const void *q, const void *k, const void *v, double scale,
+                                     void *out, void *lse, int64_t nseg, int64_t nsrc, int64_t H, int64_t D,
+                                     int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
+  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
+  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
+  if (nseg * H * D == 0) return TSAMD_OK;  // out has no element
+  if (!out || !lse) return TSAMD_ERR_INVALID;
+  if (E > 0) {
+    if (nsrc == 0 || !rowptr || !col || !q || !k || !v) return TSAMD_ERR_INVALID;
+    if (!workspace || workspace_bytes < tsamd_attention_heads_workspace_bytes(dtype, H, D, E))
+      return TSAMD_ERR_WORKSPACE;
+  }
+  const AtPlan p = at_plan(dtype, H, D, q, k, v, out);
+  switch (dtype) {
+#define TSAMD_AT_CASE(code, elem_t)                                                                                  \
+  case code:                                                                                                         \
+    return launch_attention<elem_t>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D, E,       \
+                                    workspace, stream);
+    TSAMD_AT_CASE(TSAMD_F32, float)
+    TSAMD_AT_CASE(TSAMD_F64, double)
+    TSAMD_AT_CASE(TSAMD_F16, f16_t)
+    default:
+      TSAMD_AT_CASE(TSAMD_BF16, bf16_t)
+#undef TSAMD_AT_CASE
+  }
+}
+
+extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                        const void *bias, int64_t bias_heads, const void *q, const void *k,
+                                        const void *v, const void *out, const void *lse, const void *grad_out,
+                                        double scale, void *p_out, void *ds_out, int64_t nseg, int64_t nsrc, int64_t H,
+                                        int64_t D, int64_t E, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
+  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
+  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
+  if (E == 0 || H == 0) return TSAMD_OK;  // p and ds have no element
+  if (D == 0) return TSAMD_ERR_INVALID;   // the forward defines no lse for D = 0
+  if (nseg == 0 || nsrc == 0 || !p_out || !ds_out || !col || !q || !k || !v || !out || !lse || !grad_out ||
+      (!row && !rowptr))
+    return TSAMD_ERR_INVALID;
+  AtPlan p;
+  const int64_t vec = 16 / (int64_t)dtype_size(dtype);
+  const bool packets = D % vec == 0 && at_aligned16(q) && at_aligned16(k) && at_aligned16(v) && at_aligned16(out) &&
+                       at_aligned16(grad_out);
+  p.generic = packets ? 0 : 1;
+  p.vec = packets ? (int)vec : 1;
+  at_lanes(dtype, H, D, 4, &p);  // at most kAtBwHeads heads side by side; H above takes passes
+  static_assert(kAtBwHeads == 16, "at_lanes(..., 4, ...) above");
+  switch (dtype) {
+#define TSAMD_AT_CASE(code, elem_t)                                                                                 \
+  case code:                                                                                                        \
+    return launch_attention_bw<elem_t>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out, scale,   \
+                                       p_out, ds_out, nseg, H, D, E, stream);
+    TSAMD_AT_CASE(TSAMD_F32, float)
+    TSAMD_AT_CASE(TSAMD_F64, double)
+    TSAMD_AT_CASE(TSAMD_F16, f16_t)
+    default:
+      TSAMD_AT_CASE(TSAMD_BF16, bf16_t)
+#undef TSAMD_AT_CASE
+  }
+}

@@ -1,5 +1,5 @@
 // torch operator glue, part 7: sparse attention -- the multi-head SDDMM (csrc/sddmm.hip) and the multi-head SpMM over
-// [nnz, H] values (csrc/spmm_heads.hip).  See ops_spmm.cpp for the conventions; pytorch_sparse_amd/attention.py holds
+// [nnz, H] values (csrc/spmm_heads.hip), and the fused call with its backward kernel (csrc/attention.hip).  See ops_spmm.cpp for the conventions; pytorch_sparse_amd/attention.py holds
 // the autograd pair.  (ptr, ind, perm) is a segmented order of the entries: (rowptr, col, None) or
 // (colptr, row, csr2csc).
 #include "ops_common.h"
@@ -89,6 +89,115 @@ Tensor spmm_heads(Tensor ptr, Tensor ind, OptTensor perm, OptTensor value, Tenso
   return out;
 }
 
+// the checks both fused operators share -> the bias made contiguous (undefined without one)
+Tensor check_attention(const Tensor &rowptr, const Tensor &col, const OptTensor &bias, const Tensor &q,
+                       const Tensor &k, const Tensor &v) {
+  check_index(rowptr, "rowptr");
+  check_index(col, "col");
+  check_heads_operand(q, "q");
+  check_heads_operand(k, "k");
+  check_heads_operand(v, "v");
+  TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type(),
+              "q, k and v differ in dtype: ", q.scalar_type(), ", ", k.scalar_type(), " and ", v.scalar_type());
+  TORCH_CHECK(q.get_device() == k.get_device() && q.get_device() == v.get_device() &&
+                  q.get_device() == col.get_device(),
+              "q, k, v and the pattern must be on one device");
+  TORCH_CHECK(q.size(1) == k.size(1), "q has ", q.size(1), " heads, k has ", k.size(1));
+  TORCH_CHECK(q.size(2) == k.size(2), "q has ", q.size(2), " features per head, k has ", k.size(2));
+  TORCH_CHECK(v.sizes() == k.sizes(), "v must have the shape of k, got ", v.sizes(), " and ", k.sizes());
+  TORCH_CHECK(rowptr.numel() == q.size(0) + 1, "rowptr has ", rowptr.numel(), " elements, q has ", q.size(0),
+              " rows");
+  Tensor b;
+  if (bias.has_value()) {
+    b = bias.value();
+    check_gpu(b, "bias");
+    const int64_t E = col.numel(), H = q.size(1);
+    TORCH_CHECK(b.dim() == 1 || b.dim() == 2, "bias must be [nnz] or [nnz, heads], got ", b.dim(), " dimension(s)");
+    TORCH_CHECK(b.size(0) == E, "bias has ", b.size(0), " rows, the pattern has ", E, " entries");
+    TORCH_CHECK(b.dim() == 1 || b.size(1) == H, "bias has ", b.dim() == 2 ? b.size(1) : 1, " heads, q has ", H);
+    TORCH_CHECK(b.scalar_type() == q.scalar_type(), "bias and q differ in dtype: ", b.scalar_type(), " and ",
+                q.scalar_type());
+    TORCH_CHECK(b.get_device() == q.get_device(), "bias and q must be on one device");
+    b = b.contiguous();
+  }
+  return b;
+}
+
+// fused scores -> softmax over the row -> aggregation (csrc/attention.hip) -> (out [M, H, D], lse [M, H])
+std::tuple<Tensor, Tensor> attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor q, Tensor k, Tensor v,
+                                           double scale) {
+  Tensor b = check_attention(rowptr, col, bias, q, k, v);
+  const int64_t M = q.size(0), N = k.size(0), H = q.size(1), D = q.size(2), E = col.numel();
+  c10::hip::HIPGuard guard(q.get_device());
+  q = q.contiguous();
+  k = k.contiguous();
+  v = v.contiguous();
+  rowptr = rowptr.contiguous();
+  col = col.contiguous();
+  Tensor out = torch::empty({M, H, D}, q.options().requires_grad(false));
+  const auto acc = q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  Tensor lse = torch::empty({M, H}, q.options().dtype(acc).requires_grad(false));
+  if (out.numel() == 0) {  // D == 0: every score is its bias alone, nothing is aggregated
+    TORCH_CHECK(D > 0 || lse.numel() == 0, "attention_heads needs at least one feature per head");
+    return std::make_tuple(out, lse);
+  }
+  const int dt = dtype_code(q);
+  Tensor ws = workspace(tsamd_attention_heads_workspace_bytes(dt, H, D, E), q);
+  check_status(tsamd_attention_heads(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
+                                     b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
+                                     q.data_ptr(), k.data_ptr(), v.data_ptr(), scale, out.data_ptr(), lse.data_ptr(),
+                                     M, N, H, D, E, ws.data_ptr(), (size_t)ws.numel(), current_stream(q)),
+               "tsamd_attention_heads");
+  return std::make_tuple(out, lse);
+}
+
+// p = e(s - lse[row]) and ds = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>) -> two [E, H] arrays
+std::tuple<Tensor, Tensor> attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias, Tensor q,
+                                              Tensor k, Tensor v, Tensor out, Tensor lse, Tensor grad_out,
+                                              double scale) {
+  Tensor b = check_attention(rowptr, col, bias, q, k, v);
+  if (row.has_value()) check_index(row.value(), "row");
+  check_heads_operand(out, "out");
+  check_heads_operand(grad_out, "grad_out");
+  check_gpu(lse, "lse");
+  const int64_t M = q.size(0), N = k.size(0), H = q.size(1), D = q.size(2), E = col.numel();
+  TORCH_CHECK(out.sizes() == q.sizes(), "out must have the shape of q, got ", out.sizes(), " and ", q.sizes());
+  TORCH_CHECK(grad_out.sizes() == q.sizes(), "grad_out must have the shape of q, got ", grad_out.sizes(), " and ",
+              q.sizes());
+  TORCH_CHECK(out.scalar_type() == q.scalar_type() && grad_out.scalar_type() == q.scalar_type(),
+              "out, grad_out and q differ in dtype: ", out.scalar_type(), ", ", grad_out.scalar_type(), " and ",
+              q.scalar_type());
+  const auto acc = q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == M && lse.size(1) == H && lse.scalar_type() == acc,
+              "lse must be [rows, heads] of ", acc, ", got ", lse.sizes(), " of ", lse.scalar_type());
+  TORCH_CHECK(out.get_device() == q.get_device() && grad_out.get_device() == q.get_device() &&
+                  lse.get_device() == q.get_device(),
+              "out, lse, grad_out and q must be on one device");
+  TORCH_CHECK(!row.has_value() || row.value().numel() == E, "row and col differ in length");
+  TORCH_CHECK(D > 0 || E == 0 || H == 0, "attention_heads_bw needs at least one feature per head");
+  c10::hip::HIPGuard guard(q.get_device());
+  q = q.contiguous();
+  k = k.contiguous();
+  v = v.contiguous();
+  out = out.contiguous();
+  lse = lse.contiguous();
+  grad_out = grad_out.contiguous();
+  rowptr = rowptr.contiguous();
+  col = col.contiguous();
+  Tensor r = row.has_value() ? row.value().contiguous() : Tensor();
+  Tensor p = torch::empty({E, H}, q.options().requires_grad(false));
+  Tensor ds = torch::empty({E, H}, q.options().requires_grad(false));
+  if (p.numel() == 0) return std::make_tuple(p, ds);
+  check_status(tsamd_attention_heads_bw(dtype_code(q), row.has_value() ? r.data_ptr<int64_t>() : nullptr,
+                                        rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
+                                        b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
+                                        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                        grad_out.data_ptr(), scale, p.data_ptr(), ds.data_ptr(), M, N, H, D, E,
+                                        current_stream(q)),
+               "tsamd_attention_heads_bw");
+  return std::make_tuple(p, ds);
+}
+
 }  // namespace
 }  // namespace tsamd_ops
 
@@ -100,4 +209,10 @@ static auto registry_attention =
             "float scale=1.0) -> Tensor",
             &sddmm_heads)
         .op("tsamd::spmm_heads(Tensor ptr, Tensor ind, Tensor? perm, Tensor? value, Tensor x, int nseg) -> Tensor",
-            &spmm_heads);
+            &spmm_heads)
+        .op("tsamd::attention_heads(Tensor rowptr, Tensor col, Tensor? bias, Tensor q, Tensor k, Tensor v, "
+            "float scale) -> (Tensor, Tensor)",
+            &attention_heads)
+        .op("tsamd::attention_heads_bw(Tensor? row, Tensor rowptr, Tensor col, Tensor? bias, Tensor q, Tensor k, "
+            "Tensor v, Tensor out, Tensor lse, Tensor grad_out, float scale) -> (Tensor, Tensor)",
+            &attention_heads_bw);
