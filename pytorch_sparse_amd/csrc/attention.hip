@@ -3,11 +3,8 @@
 //   out[r, h, :] = sum_i softmax_i(s(., h)) * v[col[i], h, :],    lse[r, h] = log sum_i exp(s(i, h)),
 // q [M, H, D], k and v [N, H, D], out [M, H, D], lse [M, H] (fp32, fp64 for double).  Nothing of size E is written.
 //
-// The ENTRIES are split evenly, on the tiling of spmm_heads.hip: a workgroup owns a tile of 2048 consecutive entries
-// and stages the pointer slice that meets them in LDS (expand.h), a wave owns 512 of them.  A group of
-// LPR = LPH * HPP lanes walks a CHUNK of L = 8 * LPR consecutive entries, one after the other, in 8 windows of LPR
-// entries (ids, segments and flags read once per window, a lane per entry, handed round by lane reads); the gathers
-// of four entries -- their k and v parts -- are issued before the first of them is used.
+// The group-walk kernel of segtile.h with LPR = LPH * HPP lanes per group; the gathers of four entries -- their k and v
+// parts -- are issued before the first of them is used.
 //
 //   lanes   LPH lanes (a power of two) cover the D features of one head, VEC = 16 / itemsize adjacent features per
 //           lane; HPP heads (a power of two) sit side by side in the group, so the lanes of a head are a block that
@@ -18,11 +15,9 @@
 //   score   the lanes of head h hold their part of q[row, h, :], reloaded where the segment changes, gather the same
 //           part of k[col, h, :] and reduce with a xor butterfly whose masks stay below LPH.  scale, then the bias.
 //   online  per group and head (m, l, acc[VEC]); an entry of score s and value part x is folded as
-//           m' = max(m, s), l = l * e(m - m') + e(s - m'), acc = acc * e(m - m') + e(s - m') * x, the combine of
-//           softmax.hip with exp(-inf - x) taken as 0 also for x = -inf.  e is __expf for fp32 accumulators and exp
-//           for fp64 -- no exp2 with a folded scale.
-//   rows    where a segment that began inside the chunk ends, acc / l goes to out and m + log(l) to lse.  A segment
-//           that began before the chunk leaves the chunk's HEAD record, one still open at its end the TAIL record:
+//           m' = max(m, s), l = l * e(m - m') + e(s - m'), acc = acc * e(m - m') + e(s - m') * x (soft_scale of
+//           segtile.h).  e is __expf for fp32 accumulators and exp for fp64 -- no exp2 with a folded scale.
+//   rows    where a segment that began inside the chunk ends, acc / l goes to out and m + log(l) to lse.  A record is
 //           (m, l) per head and the accumulator row.  The fix-up launch (a wave per chunk with a head record, lanes
 //           over the H * D columns) folds the tail records of the chunks [rowptr[s] / L, b) in chunk order, then the
 //           head record, every piece rescaled to the running maximum, and writes out and lse.
@@ -49,22 +44,17 @@
 // lanes per head, heads and entries side by side.  An entry's ids are read once; three dot products share the
 // butterfly: s = scale * <q, k> + bias, dp = <grad_out[row], v[col]>, delta = <grad_out[row], out[row]>.  It stores
 // p = e(s - lse[row]) and ds = p * (dp - delta) as [E, H]; lse not finite: NaN both; s = -inf: 0 both.  One launch.
-#include "common.h"
-#include "expand.h"
+#include "segtile.h"
 
 #include <type_traits>
 
 namespace tsamd {
 namespace {
 
-constexpr int kAtWaves = 4;
-constexpr int kAtWaveEntries = kExpandTile / kAtWaves;  // 512
-constexpr int kAtWindows = 8;                           // windows of LPR entries per chunk
-constexpr int kAtBatch = 4;                             // entries whose gathers are in flight
-constexpr int kAtBwHeads = 16;                          // heads side by side in the backward at most
-static_assert(kAtWaveEntries == kWave * kAtWindows, "a chunk is 8 windows of the group's lanes");
-
-constexpr int kAtValid = 1, kAtEnd = 2, kAtFresh = 4;
+constexpr int kAtWaves = kSegWaves;
+constexpr int kAtBatch = 4;     // entries whose gathers are in flight
+constexpr int kAtFwHeads = 64;  // heads side by side at most: forward (a whole wave),
+constexpr int kAtBwHeads = 16;  // backward (H above takes passes)
 
 struct AtPlan {
   int generic;
@@ -76,53 +66,40 @@ struct AtPlan {
   int64_t chunk;    // entries per group
 };
 
-__device__ __forceinline__ float at_exp(float x) { return __expf(x); }
-__device__ __forceinline__ double at_exp(double x) { return exp(x); }
 __device__ __forceinline__ float at_log(float x) { return logf(x); }
 __device__ __forceinline__ double at_log(double x) { return log(x); }
 
-bool at_float_dtype(int dtype) {
-  return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-}
-
-bool at_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int at_lg_ceil(int64_t x) {
-  int lg = 0;
-  while (((int64_t)1 << lg) < x) ++lg;
-  return lg;
-}
-
 // the lane map: a function of (dtype, H, D) alone
-void at_lanes(int dtype, int64_t H, int64_t D, int max_lg_hpp, AtPlan *p) {
+void at_lanes(int dtype, int64_t H, int64_t D, int max_heads, AtPlan *p) {
+  const int max_lg_hpp = lg_ceil(max_heads);
   const int64_t vec = 16 / (int64_t)dtype_size(dtype);
   const int64_t slots = D > 0 ? ceil_div(D, vec) : 1;
-  p->lg_lph = slots >= kWave ? 6 : at_lg_ceil(slots);
-  p->lg_hpp = at_lg_ceil(H > 0 ? H : 1);
+  p->lg_lph = slots >= kWave ? 6 : lg_ceil(slots);
+  p->lg_hpp = lg_ceil(H > 0 ? H : 1);
   if (p->lg_hpp > max_lg_hpp) p->lg_hpp = max_lg_hpp;
   if (p->lg_hpp > 6 - p->lg_lph) p->lg_hpp = 6 - p->lg_lph;
   p->fblocks = (int)ceil_div(slots, (int64_t)kWave);
   p->blocks = ceil_div(H > 0 ? H : 1, (int64_t)1 << p->lg_hpp) * p->fblocks;
-  p->chunk = (int64_t)kAtWindows << (p->lg_lph + p->lg_hpp);
+  p->chunk = (int64_t)kSegWindows << (p->lg_lph + p->lg_hpp);
 }
 
 // the one place the route is decided: the driver and tsamd_attention_heads_route both plan through it
-AtPlan at_plan(int dtype, int64_t H, int64_t D, const void *q, const void *k, const void *v, const void *out) {
+AtPlan at_plan(int dtype, int64_t H, int64_t D, int max_heads, const void *q, const void *k, const void *v,
+               const void *out, const void *more = nullptr) {
   AtPlan p;
   const int64_t vec = 16 / (int64_t)dtype_size(dtype);
-  const bool packets =
-      D > 0 && D % vec == 0 && at_aligned16(q) && at_aligned16(k) && at_aligned16(v) && at_aligned16(out);
+  const bool packets = D > 0 && D % vec == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) &&
+                       aligned16(more);
   p.generic = packets ? 0 : 1;
   p.vec = packets ? (int)vec : 1;
-  at_lanes(dtype, H, D, 6, &p);
+  at_lanes(dtype, H, D, max_heads, &p);
   return p;
 }
 
-size_t at_workspace_bytes(size_t acc, int64_t chunk, int64_t H, int64_t D, int64_t E) {
-  const size_t nchunks = (size_t)ceil_div(E > 0 ? E : 1, chunk);
+// head and tail records: an accumulator row and (m, l) per head each
+SegRecords at_records(size_t acc, int64_t chunk, int64_t H, int64_t D, int64_t E) {
   const size_t h = (size_t)(H > 0 ? H : 1), w = h * (size_t)(D > 0 ? D : 1);
-  return 2 * align_up(acc * nchunks * w, 256) + 2 * align_up(2 * acc * nchunks * h, 256) +
-         2 * align_up(sizeof(int64_t) * nchunks, 256);
+  return SegRecords(E, chunk, {acc * w, acc * w, 2 * acc * h, 2 * acc * h});
 }
 
 // VEC adjacent features of a head row, from feature d0: one 16-byte load, or element loads that read zero beyond D
@@ -156,12 +133,6 @@ __device__ __forceinline__ void at_store(T *__restrict__ head_row, int64_t d0, i
     for (int v = 0; v < VEC; ++v)
       if (d0 + v < D) head_row[d0 + v] = Traits<T>::from_acc(x[v]);
   }
-}
-
-// l of the final expression: m = +inf or NaN makes the row NaN (softmax.hip: SmForward::finish)
-template <typename A>
-__device__ __forceinline__ A at_final_l(A m, A l) {
-  return m < std::numeric_limits<A>::infinity() ? l : std::numeric_limits<A>::quiet_NaN();
 }
 
 // out = 0, lse = -inf.  out is cleared in 16-byte units of its enclosing aligned range, the two ragged ends by bytes.
@@ -198,30 +169,17 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
   __shared__ int64_t span[2];
   const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
   const int64_t e1 = e0 + kExpandTile < E ? e0 + kExpandTile : E;
-  int64_t lo, hi;
-  tile_span(ptr, nseg, e0, e1, span, &lo, &hi);
-  const int64_t S = hi - lo + 1;
-  const bool staged = S <= kExpandTile;
-  if (staged) {
-    for (int i = threadIdx.x; i <= (int)S; i += blockDim.x) sp[i] = ptr[lo + i];
-    __syncthreads();
-  }
+  const SegSlice slice = stage_slice(ptr, nseg, e0, e1, sp, span);
   const int lane = (int)(threadIdx.x & 63);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t w0 = e0 + (int64_t)wave * kAtWaveEntries;
+  const int64_t w0 = e0 + (int64_t)wave * kSegChunk;
   if (w0 >= e1) return;  // such a wave has no chunk
 
-  const int lg_lpr = lg_lph + lg_hpp;
-  const int lpr = 1 << lg_lpr, lph = 1 << lg_lph;
-  const int lg_g = 6 - lg_lpr;
-  const int g = lane >> lg_lpr;
-  const int gl = lane & (lpr - 1);  // lane of the group
-  const int hs = gl >> lg_lph;      // head slot
-  const int kl = gl & (lph - 1);    // lane of the head
-  const int64_t L = (int64_t)kAtWindows << lg_lpr;
-  const int64_t chunk = (((int64_t)blockIdx.x * kAtWaves + wave) << lg_g) + g;
-  const int64_t c0 = chunk * L;
-  const int64_t c1 = c0 + L < e1 ? c0 + L : e1;  // c0 >= e1: a group without a chunk (chunk >= nchunks)
+  const GroupGeom geo = group_geom(lg_lph + lg_hpp, wave, lane, e1);
+  const int lpr = geo.lpr, lph = 1 << lg_lph;
+  const int hs = geo.gl >> lg_lph;      // head slot
+  const int kl = geo.gl & (lph - 1);    // lane of the head
+  const int64_t chunk = geo.chunk, c0 = geo.c0;
   const int64_t W = H * D;
   const int hb = (int)blockIdx.y / fblocks, fb = (int)blockIdx.y - hb * fblocks;
   const int64_t h = ((int64_t)hb << lg_hpp) + hs;
@@ -231,7 +189,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
   const bool colok = hok && slot < slots;  // the packet route has D % VEC == 0: a packet is inside the head or outside
   const int64_t d0 = slot * VEC;
   const int64_t hoff = hok ? h * D : 0;
-  const bool scribe = gl == 0 && blockIdx.y == 0;  // writes the segment ids of the chunk's records
+  const bool scribe = geo.gl == 0 && blockIdx.y == 0;  // writes the segment ids of the chunk's records
   const bool clerk = hok && kl == 0 && fb == 0;    // writes (m, l) and lse of its head
 
   A m = kNegInf, l = A(0);
@@ -242,26 +200,15 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
   int32_t cur = -1;   // segment of the last entry taken
   int32_t qrow = -1;  // segment whose q the lane holds
 
-  for (int w = 0; w < kAtWindows; ++w) {
+  for (int w = 0; w < kSegWindows; ++w) {
     // one entry of the window per lane of the group
-    const int64_t e = c0 + (int64_t)w * lpr + gl;
-    int32_t fl_l = 0, seg_l = 0;
-    uint32_t c_l = 0;
-    if (e < c1) {
-      int64_t seg, sstart, send;
-      if (staged) {
-        const int i = segment_of_lds(sp, (int)S, e);
-        seg = lo + i;
-        sstart = sp[i];
-        send = sp[i + 1];
-      } else {
-        seg = lo + segment_of(ptr + lo, S, e);
-        sstart = ptr[seg];
-        send = ptr[seg + 1];
-      }
-      seg_l = (int32_t)seg;
-      c_l = (uint32_t)ind[e];
-      fl_l = kAtValid | (e + 1 == send ? kAtEnd : 0) | (sstart >= c0 ? kAtFresh : 0);
+    const int64_t e = c0 + (int64_t)w * lpr + geo.gl;
+    GroupEntry mine = {0, 0, 0};
+    if (e < geo.c1) {
+      const SegEntry en = slice_entry(slice, ptr, sp, e);
+      mine.seg = (int32_t)en.seg;
+      mine.col = (uint32_t)ind[e];
+      mine.fl = kSegValid | (e + 1 == en.end ? kSegEnd : 0) | (en.start >= c0 ? kSegFresh : 0);
     }
     for (int j0 = 0; j0 < lpr; j0 += kAtBatch) {  // wave-uniform: every lane answers the lane reads
       int32_t fl[kAtBatch], sg[kAtBatch];
@@ -271,15 +218,14 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
 #pragma unroll
       for (int u = 0; u < kAtBatch; ++u) {
         const int j = j0 + u;
-        const int src = (g << lg_lpr) + (j < lpr ? j : 0);
-        fl[u] = lane_read(fl_l, src);
-        if (j >= lpr) fl[u] = 0;
-        sg[u] = lane_read(seg_l, src);
-        cc[u] = lane_read(c_l, src);
+        const GroupEntry en = group_broadcast(geo, mine, j);
+        fl[u] = en.fl;
+        sg[u] = en.seg;
+        cc[u] = en.col;
         kx[u] = P();
         xv[u] = P();
         bb[u] = A(0);
-        if ((fl[u] & kAtValid) && hok) {
+        if ((fl[u] & kSegValid) && hok) {
           const uint64_t at = (uint64_t)cc[u] * (uint64_t)W + (uint64_t)hoff;
           if (colok) {
             if constexpr (!WIDE) kx[u] = at_load<T, PACKED>(k + at, d0, D);
@@ -293,7 +239,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
       }
 #pragma unroll
       for (int u = 0; u < kAtBatch; ++u) {
-        const bool valid = (fl[u] & kAtValid) != 0;
+        const bool valid = (fl[u] & kSegValid) != 0;
         A part = A(0);
         if constexpr (WIDE) {
           if (valid && hok) {
@@ -323,18 +269,16 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
           const A s = part * scale + bb[u];
           cur = sg[u];
           open = true;
-          const bool first = m >= s;  // false when either is NaN: the factor below is NaN then
-          const A mhi = first ? m : s, mlo = first ? s : m;
-          const A f = mlo == kNegInf ? A(0) : at_exp(mlo - mhi);
-          const A fa = first ? A(1) : f, fb_ = first ? f : A(1);  // weights of the state and of the entry
-          m = mhi;
+          const SoftScale<A> sc = soft_scale(m, s);
+          const A fa = sc.f_state(), fb_ = sc.f_entry();
+          m = sc.mhi;
           l = l * fa + fb_;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) acc[v] = acc[v] * fa + fb_ * Traits<T>::to_acc(xv[u].v[v]);
         }
-        if (fl[u] & kAtEnd) {
-          if (fl[u] & kAtFresh) {
-            const A lf = at_final_l(m, l);
+        if (fl[u] & kSegEnd) {
+          if (fl[u] & kSegFresh) {
+            const A lf = soft_final_l(m, l);
             if (colok) {
               A o[VEC];
 #pragma unroll
@@ -374,22 +318,16 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
       tail_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2] = m;
       tail_ml[((uint64_t)chunk * (uint64_t)H + (uint64_t)h) * 2 + 1] = l;
     }
-    if (scribe) {
-      tail_seg[chunk] = open ? (int64_t)cur : -1;
-      if (!had_head) head_seg[chunk] = -1;
-    }
+    group_record_ids(geo, scribe, open, had_head, cur, head_seg, tail_seg);
   }
 }
 
-// (m, l, a) (+) (m2, l2, a2), every piece rescaled to the larger maximum: the combine of softmax.hip with a column of
-// the accumulator row beside l
+// (m, l, a) (+) (m2, l2, a2), every piece rescaled to the larger maximum: a column of the accumulator row beside l
 template <typename A>
 __device__ __forceinline__ void at_combine(A &m, A &l, A &a, A m2, A l2, A a2) {
-  const bool first = m >= m2;
-  const A mhi = first ? m : m2, mlo = first ? m2 : m;
-  const A f = mlo == -std::numeric_limits<A>::infinity() ? A(0) : at_exp(mlo - mhi);
-  const A fa = first ? A(1) : f, fb = first ? f : A(1);
-  m = mhi;
+  const SoftScale<A> sc = soft_scale(m, m2);
+  const A fa = sc.f_state(), fb = sc.f_entry();
+  m = sc.mhi;
   l = l * fa + l2 * fb;
   a = a * fa + a2 * fb;
 }
@@ -417,7 +355,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_fixup_kernel(
     }
     const uint64_t at = ((uint64_t)b * (uint64_t)H + (uint64_t)h) * 2;
     at_combine(m, l, a, head_ml[at], head_ml[at + 1], head_acc[(uint64_t)b * (uint64_t)W + (uint64_t)col]);
-    const A lf = at_final_l(m, l);
+    const A lf = soft_final_l(m, l);
     out[(uint64_t)s * (uint64_t)W + (uint64_t)col] = Traits<T>::from_acc(a / lf);
     if (col - h * D == 0) lse[(uint64_t)s * (uint64_t)H + (uint64_t)h] = m + at_log(lf);
   }
@@ -440,16 +378,11 @@ int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, co
     TSAMD_LAUNCH_CHECK();
   }
   if (E == 0) return TSAMD_OK;
-  const int64_t nchunks = ceil_div(E, p.chunk);
-  const size_t rec = align_up(sizeof(A) * (size_t)(nchunks * W), 256);
-  const size_t mlrec = align_up(2 * sizeof(A) * (size_t)(nchunks * H), 256);
-  char *wp = reinterpret_cast<char *>(workspace);
-  A *head_acc = reinterpret_cast<A *>(wp);
-  A *tail_acc = reinterpret_cast<A *>(wp + rec);
-  A *head_ml = reinterpret_cast<A *>(wp + 2 * rec);
-  A *tail_ml = reinterpret_cast<A *>(wp + 2 * rec + mlrec);
-  int64_t *head_seg = reinterpret_cast<int64_t *>(wp + 2 * rec + 2 * mlrec);
-  int64_t *tail_seg = head_seg + align_up(sizeof(int64_t) * (size_t)nchunks, 256) / sizeof(int64_t);
+  const SegRecords rec = at_records(sizeof(A), p.chunk, H, D, E);
+  const int64_t nchunks = (int64_t)rec.nchunks;
+  A *head_acc = rec.plane<A>(workspace, 0), *tail_acc = rec.plane<A>(workspace, 1);
+  A *head_ml = rec.plane<A>(workspace, 2), *tail_ml = rec.plane<A>(workspace, 3);
+  int64_t *head_seg = rec.head_seg(workspace), *tail_seg = rec.tail_seg(workspace);
   const dim3 tiles((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)p.blocks);
   const T *bb = reinterpret_cast<const T *>(bias), *qq = reinterpret_cast<const T *>(q),
           *kk = reinterpret_cast<const T *>(k), *xx = reinterpret_cast<const T *>(v);
@@ -548,7 +481,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
         } else if (sc == -std::numeric_limits<A>::infinity()) {
           pv = dv = A(0);
         } else {
-          pv = at_exp(sc - ls);
+          pv = soft_exp(sc - ls);
           dv = pv * (pd - pl);
         }
         p_out[e * H + h] = Traits<T>::from_acc(pv);
@@ -580,12 +513,10 @@ int launch_attention_bw(const AtPlan &p, const int64_t *row, const int64_t *ptr,
 // sizes the 32-bit ids and the grids can carry
 bool at_indexable(int dtype, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E) {
   const int64_t lim = 2147483647;
-  if (nseg > lim || nsrc > lim || H > lim || D > lim) return false;
-  if (H > 0 && D > lim / H) return false;                                  // W = H * D
-  if (H > 0 && E > (int64_t)9223372036854775807LL / 16 / H) return false;  // byte offsets into [E, H] arrays
-  if (H > 0 && D > 0 && nseg > lim / 2 * 512 / (H * D)) return false;      // the fill: 16-byte units of out / 256
+  if (!heads_indexable(nseg, nsrc, H, D, E)) return false;
+  if (H > 0 && D > 0 && nseg > lim / 2 * 512 / (H * D)) return false;  // the fill: 16-byte units of out / 256
   AtPlan p;
-  at_lanes(dtype, H, D, 6, &p);
+  at_lanes(dtype, H, D, kAtFwHeads, &p);
   if (p.blocks > 65535) return false;  // column blocks are blockIdx.y
   return ceil_div(E, (int64_t)kAtWaves * kWave) <= lim;
 }
@@ -599,9 +530,9 @@ extern "C" int tsamd_attention_heads_route(int dtype, int64_t H, int64_t D, cons
                                            const void *v, const void *out, int64_t out_route[8]) {
   if (!out_route || H < 0 || D < 0) return TSAMD_ERR_INVALID;
   for (int i = 0; i < 8; ++i) out_route[i] = 0;
-  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (H > 0 && D > 2147483647 / H) return TSAMD_ERR_UNSUPPORTED;
-  const AtPlan p = at_plan(dtype, H, D, q, k, v, out);
+  const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, q, k, v, out);
   out_route[0] = p.generic;
   out_route[1] = p.vec;
   out_route[2] = (int64_t)1 << p.lg_lph;
@@ -614,11 +545,11 @@ extern "C" int tsamd_attention_heads_route(int dtype, int64_t H, int64_t D, cons
 }
 
 extern "C" size_t tsamd_attention_heads_workspace_bytes(int dtype, int64_t H, int64_t D, int64_t E) {
-  if (!at_float_dtype(dtype) || H < 0 || D < 0 || E < 0) return 0;
+  if (!is_float_dtype(dtype) || H < 0 || D < 0 || E < 0) return 0;
   if (H > 0 && D > 2147483647 / H) return 0;
   AtPlan p;
-  at_lanes(dtype, H, D, 6, &p);
-  return at_workspace_bytes(acc_size(dtype), p.chunk, H, D, E);
+  at_lanes(dtype, H, D, kAtFwHeads, &p);
+  return at_records(acc_size(dtype), p.chunk, H, D, E).bytes();
 }
 
 extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
@@ -627,7 +558,7 @@ extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int
                                      int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
   if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
   if (nseg * H * D == 0) return TSAMD_OK;  // out has no element
@@ -637,19 +568,11 @@ extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int
     if (!workspace || workspace_bytes < tsamd_attention_heads_workspace_bytes(dtype, H, D, E))
       return TSAMD_ERR_WORKSPACE;
   }
-  const AtPlan p = at_plan(dtype, H, D, q, k, v, out);
-  switch (dtype) {
-#define TSAMD_AT_CASE(code, elem_t)                                                                                  \
-  case code:                                                                                                         \
-    return launch_attention<elem_t>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D, E,       \
-                                    workspace, stream);
-    TSAMD_AT_CASE(TSAMD_F32, float)
-    TSAMD_AT_CASE(TSAMD_F64, double)
-    TSAMD_AT_CASE(TSAMD_F16, f16_t)
-    default:
-      TSAMD_AT_CASE(TSAMD_BF16, bf16_t)
-#undef TSAMD_AT_CASE
-  }
+  const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, q, k, v, out);
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    return launch_attention<scalar_t>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D, E,
+                                      workspace, stream);
+  });
 }
 
 extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
@@ -659,7 +582,7 @@ extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int
                                         int64_t D, int64_t E, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!at_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
   if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
   if (E == 0 || H == 0) return TSAMD_OK;  // p and ds have no element
@@ -667,24 +590,9 @@ extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int
   if (nseg == 0 || nsrc == 0 || !p_out || !ds_out || !col || !q || !k || !v || !out || !lse || !grad_out ||
       (!row && !rowptr))
     return TSAMD_ERR_INVALID;
-  AtPlan p;
-  const int64_t vec = 16 / (int64_t)dtype_size(dtype);
-  const bool packets = D % vec == 0 && at_aligned16(q) && at_aligned16(k) && at_aligned16(v) && at_aligned16(out) &&
-                       at_aligned16(grad_out);
-  p.generic = packets ? 0 : 1;
-  p.vec = packets ? (int)vec : 1;
-  at_lanes(dtype, H, D, 4, &p);  // at most kAtBwHeads heads side by side; H above takes passes
-  static_assert(kAtBwHeads == 16, "at_lanes(..., 4, ...) above");
-  switch (dtype) {
-#define TSAMD_AT_CASE(code, elem_t)                                                                                 \
-  case code:                                                                                                        \
-    return launch_attention_bw<elem_t>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out, scale,   \
-                                       p_out, ds_out, nseg, H, D, E, stream);
-    TSAMD_AT_CASE(TSAMD_F32, float)
-    TSAMD_AT_CASE(TSAMD_F64, double)
-    TSAMD_AT_CASE(TSAMD_F16, f16_t)
-    default:
-      TSAMD_AT_CASE(TSAMD_BF16, bf16_t)
-#undef TSAMD_AT_CASE
-  }
+  const AtPlan p = at_plan(dtype, H, D, kAtBwHeads, q, k, v, out, grad_out);
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    return launch_attention_bw<scalar_t>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out, scale,
+                                         p_out, ds_out, nseg, H, D, E, stream);
+  });
 }

@@ -248,6 +248,39 @@ static inline size_t acc_size(int dtype) {
     }                                                                         \
   }()
 
+// The four floating types only; scalar_t as above.
+#define TSAMD_DISPATCH_FLOAT(dtype, ...)                                   \
+  [&]() -> int {                                                           \
+    switch (dtype) {                                                       \
+      case TSAMD_F32: { using scalar_t = float; return __VA_ARGS__(); }    \
+      case TSAMD_F64: { using scalar_t = double; return __VA_ARGS__(); }   \
+      case TSAMD_F16: { using scalar_t = ::tsamd::f16_t; return __VA_ARGS__(); }  \
+      case TSAMD_BF16: { using scalar_t = ::tsamd::bf16_t; return __VA_ARGS__(); } \
+      default: return (int)TSAMD_ERR_UNSUPPORTED;                          \
+    }                                                                      \
+  }()
+
+static inline bool is_float_dtype(int dtype) {
+  return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
+}
+
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// smallest lg with 2^lg >= x
+static inline int lg_ceil(int64_t x) {
+  int lg = 0;
+  while (((int64_t)1 << lg) < x) ++lg;
+  return lg;
+}
+
+// [nseg | nsrc, H, D] operands and [E, H] values: the sizes 32-bit ids and 64-bit byte offsets can carry
+static inline bool heads_indexable(int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E) {
+  const int64_t lim = 2147483647;
+  if (nseg > lim || nsrc > lim || H > lim || D > lim) return false;
+  if (H > 0 && D > lim / H) return false;                                  // W = H * D
+  return !(H > 0 && E > (int64_t)9223372036854775807LL / 16 / H);          // byte offsets into [E, H] arrays
+}
+
 // --------------------------------------------------------------------------
 // wave64 cross-lane helpers.  ds_bpermute takes a byte address (lane * 4).
 // --------------------------------------------------------------------------

@@ -20,7 +20,7 @@
 // lanes to consecutive addresses: with H <= HPP and no perm a window is one run of 64 * H elements.
 // f32 / f16 / bf16 accumulate in fp32, f64 in fp64; `scale` is applied to the accumulator and the product is rounded
 // to the element type once, on the store.  Deterministic, no atomics, no workspace, no host sync, one launch.
-#include "common.h"
+#include "expand.h"
 
 namespace tsamd {
 namespace {
@@ -35,28 +35,16 @@ struct SdPlan {
   int lg_lpr;   // lanes per entry = lanes per head * heads side by side
 };
 
-int sd_lg_ceil(int64_t x) {
-  int lg = 0;
-  while (((int64_t)1 << lg) < x) ++lg;
-  return lg;
-}
-
-bool sd_float_dtype(int dtype) {
-  return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-}
-
-bool sd_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // the one place the route is decided: the driver and tsamd_sddmm_heads_route both plan through it
 SdPlan sd_plan(int dtype, int64_t H, int64_t D, const void *q, const void *k) {
   SdPlan p;
   const int64_t vec = 16 / (int64_t)dtype_size(dtype);
-  const bool packets = D > 0 && D % vec == 0 && ((D / vec) & (D / vec - 1)) == 0 && sd_aligned16(q) && sd_aligned16(k);
+  const bool packets = D > 0 && D % vec == 0 && ((D / vec) & (D / vec - 1)) == 0 && aligned16(q) && aligned16(k);
   p.generic = packets ? 0 : 1;
   p.vec = packets ? (int)vec : 1;
   const int64_t per_head = packets ? D / vec : (D > 0 ? D : 1);
-  p.lg_lph = per_head >= kWave ? 6 : sd_lg_ceil(per_head);
-  int lg_hpp = H >= kSdHeads ? 4 : sd_lg_ceil(H > 0 ? H : 1);
+  p.lg_lph = per_head >= kWave ? 6 : lg_ceil(per_head);
+  int lg_hpp = H >= kSdHeads ? 4 : lg_ceil(H > 0 ? H : 1);
   if (lg_hpp > 6 - p.lg_lph) lg_hpp = 6 - p.lg_lph;
   p.lg_lpr = p.lg_lph + lg_hpp;
   return p;
@@ -84,18 +72,7 @@ __global__ __launch_bounds__(kSdWaves *kWave) void sddmm_heads_kernel(
   if (lane < n) {
     const int64_t e = base + lane;
     c_l = (uint32_t)ind[e];
-    int64_t r;
-    if (row != nullptr) {
-      r = row[e];
-    } else {  // last r with ptr[r] <= e
-      int64_t lo = 0, hi = nseg;
-      while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ptr[mid] <= e) lo = mid; else hi = mid;
-      }
-      r = lo;
-    }
-    r_l = (uint32_t)r;
+    r_l = (uint32_t)(row != nullptr ? row[e] : segment_of(ptr, nseg, e));
     p_l = perm ? perm[e] : e;
   }
 
@@ -171,11 +148,7 @@ int launch_sddmm_heads(const SdPlan &p, const int64_t *row, const int64_t *ptr, 
 
 // sizes the 32-bit ids and the grid can carry
 bool sd_indexable(int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E) {
-  const int64_t lim = 2147483647;
-  if (nseg > lim || nsrc > lim || H > lim || D > lim) return false;
-  if (H > 0 && D > lim / H) return false;                         // H * D
-  if (H > 0 && E > (int64_t)9223372036854775807LL / 16 / H) return false;  // byte offsets into out
-  return ceil_div(E, (int64_t)kSdWaves * kWave) <= lim;
+  return heads_indexable(nseg, nsrc, H, D, E) && ceil_div(E, (int64_t)kSdWaves * kWave) <= 2147483647;
 }
 
 }  // namespace
@@ -187,7 +160,7 @@ extern "C" int tsamd_sddmm_heads_route(int dtype, int64_t H, int64_t D, const vo
                                        int64_t out[8]) {
   if (!out || H < 0 || D < 0) return TSAMD_ERR_INVALID;
   for (int i = 0; i < 8; ++i) out[i] = 0;
-  if (!sd_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   const SdPlan p = sd_plan(dtype, H, D, q, k);
   out[0] = p.generic;
   out[1] = p.vec;
@@ -205,15 +178,12 @@ extern "C" int tsamd_sddmm_heads(int dtype, const int64_t *row, const int64_t *p
                                  int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!sd_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (!sd_indexable(nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
   if (E == 0 || H == 0 || D == 0) return TSAMD_OK;
   if (nseg == 0 || nsrc == 0 || !out || !ind || !q || !k || (!row && !ptr)) return TSAMD_ERR_INVALID;
   const SdPlan p = sd_plan(dtype, H, D, q, k);
-  switch (dtype) {
-    case TSAMD_F32: return launch_sddmm_heads<float>(p, row, ptr, ind, perm, q, k, scale, out, nseg, H, D, E, stream);
-    case TSAMD_F64: return launch_sddmm_heads<double>(p, row, ptr, ind, perm, q, k, scale, out, nseg, H, D, E, stream);
-    case TSAMD_F16: return launch_sddmm_heads<f16_t>(p, row, ptr, ind, perm, q, k, scale, out, nseg, H, D, E, stream);
-    default: return launch_sddmm_heads<bf16_t>(p, row, ptr, ind, perm, q, k, scale, out, nseg, H, D, E, stream);
-  }
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    return launch_sddmm_heads<scalar_t>(p, row, ptr, ind, perm, q, k, scale, out, nseg, H, D, E, stream);
+  });
 }

@@ -5,13 +5,9 @@
 // power-law data has segments with 1e5..1e7 entries, which a thread-per-segment kernel serialises
 // (13 ms for the row sums of the 40 M-entry north-star graph).  Here the ENTRIES are split evenly:
 //
-//   tile kernel   a workgroup owns 2048 consecutive entries (4 waves x 8 windows of 64), stages the
-//                 pointer slice that intersects them in LDS (expand.h); every lane finds the
-//                 segment of its entry by an LDS binary search; a wave-level segmented inclusive scan
-//                 (6 bpermute steps, equal-segment guard) reduces the window, a wave-uniform carry
-//                 links the windows.  A lane that holds the last entry of a segment writes the result
-//                 -- unless the segment began before the wave's chunk: that piece becomes the chunk's
-//                 HEAD record; a segment still open at the end of the chunk leaves a TAIL record.
+//   tile kernel   the tiling of segtile.h with a wave-level segmented inclusive scan of every window (6 bpermute
+//                 steps, equal-segment guard) and a wave-uniform carry between the windows: a lane that holds the
+//                 last entry of a segment that began inside the wave's chunk writes the result.
 //   fix-up        one wave per chunk with a head record folds the tail records of the chunks before
 //                 it (lanes stride over them, butterfly; fp32 sums fold in fp64) and writes the row.
 //
@@ -26,8 +22,7 @@
 // EARLIER piece is associative (a NaN can only head the earliest piece, and stays); and every combine
 // -- scan, carry, fix-up -- takes its operands in entry order.  The fix-up therefore gives each lane a
 // contiguous run of tail records and reduces across lanes towards lane 0 (kSrOrdered).
-#include "common.h"
-#include "expand.h"
+#include "segtile.h"
 
 #include <type_traits>
 
@@ -35,10 +30,6 @@ namespace tsamd {
 namespace {
 
 constexpr int SR_ADD = 0, SR_MIN = 1, SR_MAX = 2;
-constexpr int kSrWindows = 8;
-constexpr int kSrChunk = kWave * kSrWindows;         // entries per wave
-constexpr int kSrWaves = kExpandTile / kSrChunk;     // waves per workgroup (4)
-static_assert(kSrWaves * kSrChunk == kExpandTile, "tile = waves x chunk");
 
 template <typename A, int RED>
 __device__ __forceinline__ A sr_combine(A a, A b) {
@@ -66,7 +57,7 @@ __device__ __forceinline__ void sr_write(T *__restrict__ out, A v, int64_t cnt, 
 }
 
 template <typename T, int RED>
-__global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void segreduce_tile_kernel(
     const T *__restrict__ value, const int64_t *__restrict__ perm, const int64_t *__restrict__ ptr,
     int64_t nseg, int64_t E, int64_t D, bool mean, T *__restrict__ out,
     typename Traits<T>::acc_t *__restrict__ head_val, typename Traits<T>::acc_t *__restrict__ tail_val,
@@ -77,19 +68,12 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
   const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
   const int64_t e1 = e0 + kExpandTile < E ? e0 + kExpandTile : E;
   const int64_t d = blockIdx.y;
-  int64_t lo, hi;
-  tile_span(ptr, nseg, e0, e1, span, &lo, &hi);
-  const int64_t S = hi - lo + 1;
-  const bool staged = S <= kExpandTile;
-  if (staged) {
-    for (int i = threadIdx.x; i <= (int)S; i += blockDim.x) sp[i] = ptr[lo + i];
-    __syncthreads();
-  }
+  const SegSlice slice = stage_slice(ptr, nseg, e0, e1, sp, span);
   const int lane = (int)(threadIdx.x & 63);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t chunk = (int64_t)blockIdx.x * kSrWaves + wave;
-  const int64_t c0 = e0 + (int64_t)wave * kSrChunk;
-  const int64_t c1 = c0 + kSrChunk < e1 ? c0 + kSrChunk : e1;
+  const int64_t chunk = (int64_t)blockIdx.x * kSegWaves + wave;
+  const int64_t c0 = e0 + (int64_t)wave * kSegChunk;
+  const int64_t c1 = c0 + kSegChunk < e1 ? c0 + kSegChunk : e1;
   if (c0 >= e1) {
     if (lane == 0 && chunk < nchunks) head_seg[chunk] = tail_seg[chunk] = -1;
     return;
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
   A cval = A(0);
   int64_t hseg = -1;  // head record of this chunk (set by at most one lane)
   A hval = A(0);
-  for (int w = 0; w < kSrWindows; ++w) {
+  for (int w = 0; w < kSegWindows; ++w) {
     const int64_t base = c0 + (int64_t)w * kWave;
     if (base >= c1) break;
     const int64_t e = base + lane;
@@ -107,16 +91,10 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
     int64_t seg = -2 - lane, sstart = 0, send = 0;  // invalid lanes never match a neighbour
     A v = A(0);
     if (valid) {
-      if (staged) {
-        const int i = segment_of_lds(sp, (int)S, e);
-        seg = lo + i;
-        sstart = sp[i];
-        send = sp[i + 1];
-      } else {
-        seg = lo + segment_of(ptr + lo, S, e);
-        sstart = ptr[seg];
-        send = ptr[seg + 1];
-      }
+      const SegEntry en = slice_entry(slice, ptr, sp, e);
+      seg = en.seg;
+      sstart = en.start;
+      send = en.end;
       v = Traits<T>::to_acc(value[(perm ? perm[e] : e) * D + d]);
       if constexpr (kSrOrdered<A, RED>) {  // a NaN after the segment's first entry never wins
         if (v != v && e != sstart)
@@ -160,7 +138,7 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_tile_kernel(
 }
 
 template <typename T, int RED>
-__global__ __launch_bounds__(kSrWaves *kWave) void segreduce_fixup_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void segreduce_fixup_kernel(
     const int64_t *__restrict__ ptr, int64_t D, bool mean, T *__restrict__ out,
     const typename Traits<T>::acc_t *__restrict__ head_val,
     const typename Traits<T>::acc_t *__restrict__ tail_val, const int64_t *__restrict__ head_seg,
@@ -169,7 +147,7 @@ __global__ __launch_bounds__(kSrWaves *kWave) void segreduce_fixup_kernel(
   // fp32 partial sums of a long segment fold in fp64 (as the SpMM fix-up does)
   using W = typename std::conditional<RED == SR_ADD && std::is_same<A, float>::value, double, A>::type;
   const int lane = (int)(threadIdx.x & 63);
-  const int64_t b = (int64_t)blockIdx.x * kSrWaves + (threadIdx.x >> 6);
+  const int64_t b = (int64_t)blockIdx.x * kSegWaves + (threadIdx.x >> 6);
   if (b >= nchunks) return;
   const int64_t s = head_seg[b];
   if (s < 0) return;
@@ -228,21 +206,16 @@ template <typename T, int RED>
 int launch_segreduce(const T *value, const int64_t *perm, const int64_t *ptr, int64_t nseg, int64_t E,
                      int64_t D, bool mean, T *out, void *workspace, hipStream_t stream) {
   using A = typename Traits<T>::acc_t;
-  const int64_t nchunks = ceil_div(E, (int64_t)kSrChunk);
-  char *p = reinterpret_cast<char *>(workspace);
-  A *head_val = reinterpret_cast<A *>(p);
-  p += align_up(sizeof(A) * (size_t)(D * nchunks), 256);
-  A *tail_val = reinterpret_cast<A *>(p);
-  p += align_up(sizeof(A) * (size_t)(D * nchunks), 256);
-  int64_t *head_seg = reinterpret_cast<int64_t *>(p);
-  p += align_up(sizeof(int64_t) * (size_t)nchunks, 256);
-  int64_t *tail_seg = reinterpret_cast<int64_t *>(p);
+  const SegRecords rec(E, kSegChunk, {sizeof(A) * (size_t)D, sizeof(A) * (size_t)D});
+  const int64_t nchunks = (int64_t)rec.nchunks;
+  A *head_val = rec.plane<A>(workspace, 0), *tail_val = rec.plane<A>(workspace, 1);
+  int64_t *head_seg = rec.head_seg(workspace), *tail_seg = rec.tail_seg(workspace);
   const dim3 grid((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)D);
-  hipLaunchKernelGGL((segreduce_tile_kernel<T, RED>), grid, dim3(kSrWaves * kWave), 0, stream, value, perm, ptr,
+  hipLaunchKernelGGL((segreduce_tile_kernel<T, RED>), grid, dim3(kSegWaves * kWave), 0, stream, value, perm, ptr,
                      nseg, E, D, mean, out, head_val, tail_val, head_seg, tail_seg, nchunks);
   TSAMD_LAUNCH_CHECK();
-  const dim3 grid2((unsigned int)ceil_div(nchunks, (int64_t)kSrWaves), (unsigned int)D);
-  hipLaunchKernelGGL((segreduce_fixup_kernel<T, RED>), grid2, dim3(kSrWaves * kWave), 0, stream, ptr, D, mean,
+  const dim3 grid2((unsigned int)ceil_div(nchunks, (int64_t)kSegWaves), (unsigned int)D);
+  hipLaunchKernelGGL((segreduce_fixup_kernel<T, RED>), grid2, dim3(kSegWaves * kWave), 0, stream, ptr, D, mean,
                      out, (const A *)head_val, (const A *)tail_val, (const int64_t *)head_seg,
                      (const int64_t *)tail_seg, nchunks);
   TSAMD_LAUNCH_CHECK();
@@ -255,9 +228,8 @@ int launch_segreduce(const T *value, const int64_t *perm, const int64_t *ptr, in
 using namespace tsamd;
 
 extern "C" size_t tsamd_segment_reduce_balanced_workspace_bytes(int dtype, int64_t E, int64_t D) {
-  const size_t nchunks = (size_t)ceil_div(E > 0 ? E : 1, (int64_t)kSrChunk);
-  const size_t d = (size_t)(D > 0 ? D : 1);
-  return 2 * align_up(acc_size(dtype) * d * nchunks, 256) + 2 * align_up(sizeof(int64_t) * nchunks, 256);
+  const size_t plane = acc_size(dtype) * (size_t)(D > 0 ? D : 1);
+  return SegRecords(E, kSegChunk, {plane, plane}).bytes();
 }
 
 extern "C" int tsamd_segment_reduce_balanced(int dtype, int reduce, const void *value,

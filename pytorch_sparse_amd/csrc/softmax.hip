@@ -4,16 +4,15 @@
 //              rowptr, the columns through csr2csc / colptr);
 //   backward   gv[p(i)] = y[p(i)] * (g[p(i)] - dot_j),  dot_j = sum of g * y over the segment.
 //
-// Both are a segmented reduction followed by a per-entry normalisation, so they share the tiling of segreduce.hip
-// (2048-entry tile, 4 waves x 8 windows of 64, pointer slice staged in LDS by expand.h) and differ only in the MODE
-// below: what a lane keeps of its entry, the scanned quantity and its combine, and the final expression.
+// Both are a segmented reduction followed by a per-entry normalisation, on the tiling of segtile.h with the scan of
+// segreduce.hip; they differ only in the MODE below: what a lane keeps of its entry, the scanned quantity and its
+// combine, and the final expression.
 //
 //   tile kernel   segmented inclusive scan of every window, wave-uniform carry between the windows of a chunk.  The
-//                 lane that holds the LAST entry of a segment that began inside the chunk leaves the segment's total
-//                 in the wave's LDS slot of that entry; after the last window every lane fetches the total of its
+//                 lane that holds the LAST entry of a segment that began inside the chunk leaves the segment's
+//                 total in the wave's LDS slot of that entry; after the last window every lane fetches the total of its
 //                 segment from there and writes its result -- the inputs are read once.  A segment cut by a chunk
-//                 boundary writes nothing here: the piece that ends in the chunk becomes the chunk's HEAD record, the
-//                 piece still open at its end the TAIL record (the same records as segreduce.hip, of totals).
+//                 boundary writes nothing here; its records hold totals.
 //   fix-up        one wave per chunk with a head record: the tail records of the chunks [ptr[s] / 512, b) are folded
 //                 64 per round (lane l takes records l, l + 64, ... in entry order, then a xor butterfly), combined
 //                 with the head record and left as the chunk's FINAL record.
@@ -21,8 +20,8 @@
 //                 entries of the head piece [c0, ptr[hs + 1]) and of the tail piece [max(ptr[ts], c0), c1), takes the
 //                 final record of the chunk where the segment ends and writes the result.
 //
-// The forward scans the pair (m, s) with the online-softmax combine
-//   (m1, s1) (+) (m2, s2) = (max, s_hi + s_lo * exp(m_lo - m_hi)),   exp(-inf - x) taken as 0 also for x = -inf,
+// The forward scans the pair (m, s) with the online-softmax combine (segtile.h)
+//   (m1, s1) (+) (m2, s2) = (max, s_hi + s_lo * exp(m_lo - m_hi)),
 // which is bitwise commutative, so the butterfly leaves the same bits in every lane.  An entry is (v, 1).  Non-finite
 // inputs follow torch.softmax of the segment alone: a NaN entry makes s NaN (exp(NaN)) and a NaN s stays NaN through
 // every later combine, so the whole segment is NaN; a segment that holds +inf ends with m = +inf, which the final
@@ -30,22 +29,14 @@
 // the final expression; -inf beside finite entries gives exp(-inf) = 0.
 // Accumulation is fp32 (fp64 for double); the result is rounded to the element type once, on the store.
 // Deterministic (fixed combine tree), no atomics, no host sync.  Heads (D > 1) are blockIdx.y.
-#include "common.h"
-#include "expand.h"
+#include "segtile.h"
 
 #include <type_traits>
 
 namespace tsamd {
 namespace {
 
-constexpr int kSmWindows = 8;
-constexpr int kSmChunk = kWave * kSmWindows;      // entries per wave
-constexpr int kSmWaves = kExpandTile / kSmChunk;  // waves per workgroup (4)
-constexpr int kSmFold = kWave;                    // tail records one fix-up round folds
-static_assert(kSmWaves * kSmChunk == kExpandTile, "tile = waves x chunk");
-
-__device__ __forceinline__ float sm_exp(float x) { return __expf(x); }
-__device__ __forceinline__ double sm_exp(double x) { return exp(x); }
+constexpr int kSmFold = kWave;  // tail records one fix-up round folds
 
 template <typename T>
 struct SmForward {
@@ -62,16 +53,15 @@ struct SmForward {
   }
   __device__ static __forceinline__ Acc lift(In in) { return {in.v, A(1)}; }
   __device__ static __forceinline__ Acc combine(Acc a, Acc b) {
-    const bool first = a.m >= b.m;  // false when either is NaN: the factor below is NaN then, and so is s
-    const A hi = first ? a.m : b.m, lo = first ? b.m : a.m;
-    const A f = lo == -std::numeric_limits<A>::infinity() ? A(0) : sm_exp(lo - hi);
-    return {hi, first ? a.s + b.s * f : a.s * f + b.s};
+    const SoftScale<A> c = soft_scale(a.m, b.m);
+    return {c.mhi, c.first ? a.s + b.s * c.f : a.s * c.f + b.s};  // not s * f_state + s2 * f_entry: segtile.h
   }
   __device__ static __forceinline__ Acc read(Acc a, int src) { return {lane_read(a.m, src), lane_read(a.s, src)}; }
   __device__ static __forceinline__ A finish(In in, Acc t) {
-    // m = +inf: torch's sum holds exp(inf - inf) = NaN, so the finite entries are 0 / NaN, not 0 / s
+    // m = +inf: torch's sum holds exp(inf - inf) = NaN, so the finite entries are 0 / NaN, not 0 / s.  Not
+    // soft_final_l: a NaN maximum keeps s here (NaN already, with its own sign and payload)
     const A s = t.m == std::numeric_limits<A>::infinity() ? std::numeric_limits<A>::quiet_NaN() : t.s;
-    return sm_exp(in.v - t.m) / s;
+    return soft_exp(in.v - t.m) / s;
   }
 };
 
@@ -96,7 +86,7 @@ struct SmBackward {
 
 // a, b: (value, unused) forward, (y, grad) backward
 template <typename T, typename M>
-__global__ __launch_bounds__(kSmWaves *kWave) void softmax_tile_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void softmax_tile_kernel(
     const T *__restrict__ a, const T *__restrict__ b, const int64_t *__restrict__ perm,
     const int64_t *__restrict__ ptr, int64_t nseg, int64_t E, int64_t D, T *__restrict__ out,
     typename M::Acc *__restrict__ head_val, typename M::Acc *__restrict__ tail_val, int64_t *__restrict__ head_seg,
@@ -109,31 +99,24 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_tile_kernel(
   const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
   const int64_t e1 = e0 + kExpandTile < E ? e0 + kExpandTile : E;
   const int64_t d = blockIdx.y;
-  int64_t lo, hi;
-  tile_span(ptr, nseg, e0, e1, span, &lo, &hi);
-  const int64_t S = hi - lo + 1;
-  const bool staged = S <= kExpandTile;
-  if (staged) {
-    for (int i = threadIdx.x; i <= (int)S; i += blockDim.x) sp[i] = ptr[lo + i];
-    __syncthreads();
-  }
+  const SegSlice slice = stage_slice(ptr, nseg, e0, e1, sp, span);
   const int lane = (int)(threadIdx.x & 63);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t chunk = (int64_t)blockIdx.x * kSmWaves + wave;
-  const int64_t c0 = e0 + (int64_t)wave * kSmChunk;
-  const int64_t c1 = c0 + kSmChunk < e1 ? c0 + kSmChunk : e1;
+  const int64_t chunk = (int64_t)blockIdx.x * kSegWaves + wave;
+  const int64_t c0 = e0 + (int64_t)wave * kSegChunk;
+  const int64_t c1 = c0 + kSegChunk < e1 ? c0 + kSegChunk : e1;
   if (c0 >= e1) return;  // such a wave has no chunk: chunk >= nchunks
-  Acc *mine = totals + wave * kSmChunk;
+  Acc *mine = totals + wave * kSegChunk;
 
   int64_t cseg = -1;  // wave-uniform carry: the segment still open at the end of the last window
   Acc cval = M::identity();
   int64_t hseg = -1;  // head record of this chunk (set by at most one lane)
   Acc hval = M::identity();
-  In in[kSmWindows];
-  int64_t at[kSmWindows];  // element index of the lane's entry in window w
-  int endl[kSmWindows];    // chunk-local slot of its segment's last entry; -1: not finished here
+  In in[kSegWindows];
+  int64_t at[kSegWindows];  // element index of the lane's entry in window w
+  int endl[kSegWindows];    // chunk-local slot of its segment's last entry; -1: not finished here
 #pragma unroll
-  for (int w = 0; w < kSmWindows; ++w) {
+  for (int w = 0; w < kSegWindows; ++w) {
     const int64_t base = c0 + (int64_t)w * kWave;
     endl[w] = -1;
     at[w] = 0;
@@ -144,16 +127,10 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_tile_kernel(
       int64_t seg = -2 - lane, sstart = 0, send = 0;  // invalid lanes never match a neighbour
       Acc x = M::identity();
       if (valid) {
-        if (staged) {
-          const int i = segment_of_lds(sp, (int)S, e);
-          seg = lo + i;
-          sstart = sp[i];
-          send = sp[i + 1];
-        } else {
-          seg = lo + segment_of(ptr + lo, S, e);
-          sstart = ptr[seg];
-          send = ptr[seg + 1];
-        }
+        const SegEntry en = slice_entry(slice, ptr, sp, e);
+        seg = en.seg;
+        sstart = en.start;
+        send = en.end;
         at[w] = (perm ? perm[e] : e) * D + d;
         in[w] = M::load(a, b, at[w]);
         x = M::lift(in[w]);
@@ -199,24 +176,24 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_tile_kernel(
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-  for (int w = 0; w < kSmWindows; ++w) {
+  for (int w = 0; w < kSegWindows; ++w) {
     if (endl[w] >= 0) out[at[w]] = Traits<T>::from_acc(M::finish(in[w], mine[endl[w]]));
   }
 }
 
 template <typename T, typename M>
-__global__ __launch_bounds__(kSmWaves *kWave) void softmax_fixup_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void softmax_fixup_kernel(
     const int64_t *__restrict__ ptr, const typename M::Acc *__restrict__ head_val,
     const typename M::Acc *__restrict__ tail_val, const int64_t *__restrict__ head_seg,
     typename M::Acc *__restrict__ final_val, int64_t nchunks) {
   using Acc = typename M::Acc;
   const int lane = (int)(threadIdx.x & 63);
-  const int64_t b = (int64_t)blockIdx.x * kSmWaves + (threadIdx.x >> 6);
+  const int64_t b = (int64_t)blockIdx.x * kSegWaves + (threadIdx.x >> 6);
   if (b >= nchunks) return;
   const int64_t s = head_seg[b];
   if (s < 0) return;
   const int64_t d = blockIdx.y;
-  const int64_t first = ptr[s] / kSmChunk;  // every chunk in [first, b) ended inside s: its tail record is a piece of s
+  const int64_t first = ptr[s] / kSegChunk;  // every chunk in [first, b) ended inside s: its tail record is a piece
   const Acc *tv = tail_val + d * nchunks;
   Acc acc = M::identity();
   for (int64_t i = first + lane; i < b; i += kSmFold) acc = M::combine(acc, tv[i]);
@@ -226,20 +203,20 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_fixup_kernel(
 }
 
 template <typename T, typename M>
-__global__ __launch_bounds__(kSmWaves *kWave) void softmax_finish_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void softmax_finish_kernel(
     const T *__restrict__ a, const T *__restrict__ b, const int64_t *__restrict__ perm,
     const int64_t *__restrict__ ptr, int64_t E, int64_t D, T *__restrict__ out,
     const typename M::Acc *__restrict__ final_val, const int64_t *__restrict__ head_seg,
     const int64_t *__restrict__ tail_seg, int64_t nchunks) {
   using Acc = typename M::Acc;
   const int lane = (int)(threadIdx.x & 63);
-  const int64_t c = (int64_t)blockIdx.x * kSmWaves + (threadIdx.x >> 6);
+  const int64_t c = (int64_t)blockIdx.x * kSegWaves + (threadIdx.x >> 6);
   if (c >= nchunks) return;
   const int64_t hs = head_seg[c], ts = tail_seg[c];
   if (hs < 0 && ts < 0) return;  // every segment of this chunk was finished by the tile kernel
   const int64_t d = blockIdx.y;
-  const int64_t c0 = c * kSmChunk;
-  const int64_t c1 = c0 + kSmChunk < E ? c0 + kSmChunk : E;
+  const int64_t c0 = c * kSegChunk;
+  const int64_t c1 = c0 + kSegChunk < E ? c0 + kSegChunk : E;
   int64_t hend = c0, tbeg = c1;  // head piece [c0, hend), tail piece [tbeg, c1)
   Acc ht = M::identity(), tt = M::identity();
   if (hs >= 0) {
@@ -249,7 +226,7 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_finish_kernel(
   if (ts >= 0) {
     const int64_t ps = ptr[ts];
     tbeg = ps > c0 ? ps : c0;
-    tt = final_val[d * nchunks + (ptr[ts + 1] - 1) / kSmChunk];  // the chunk where ts ends
+    tt = final_val[d * nchunks + (ptr[ts + 1] - 1) / kSegChunk];  // the chunk where ts ends
   }
   for (int64_t e = c0 + lane; e < c1; e += kWave) {
     const bool head = e < hend;
@@ -260,11 +237,10 @@ __global__ __launch_bounds__(kSmWaves *kWave) void softmax_finish_kernel(
   }
 }
 
-template <typename A>
-size_t sm_workspace_bytes(int64_t E, int64_t D) {
-  const size_t nchunks = (size_t)ceil_div(E > 0 ? E : 1, (int64_t)kSmChunk);
-  const size_t d = (size_t)(D > 0 ? D : 1);
-  return 3 * align_up(2 * sizeof(A) * d * nchunks, 256) + 2 * align_up(sizeof(int64_t) * nchunks, 256);
+// head, tail and final records: at most the pair (m, s) each
+SegRecords sm_records(size_t acc, int64_t E, int64_t D) {
+  const size_t plane = 2 * acc * (size_t)(D > 0 ? D : 1);
+  return SegRecords(E, kSegChunk, {plane, plane, plane});
 }
 
 template <typename T, typename M>
@@ -273,17 +249,14 @@ int launch_softmax(const T *a, const T *b, const int64_t *perm, const int64_t *p
   using A = typename Traits<T>::acc_t;
   using Acc = typename M::Acc;
   static_assert(sizeof(Acc) <= 2 * sizeof(A), "a record is at most the pair (m, s)");
-  const int64_t nchunks = ceil_div(E, (int64_t)kSmChunk);
-  const size_t rec = align_up(2 * sizeof(A) * (size_t)(D * nchunks), 256);
-  char *p = reinterpret_cast<char *>(workspace);
-  Acc *head_val = reinterpret_cast<Acc *>(p);
-  Acc *tail_val = reinterpret_cast<Acc *>(p + rec);
-  Acc *final_val = reinterpret_cast<Acc *>(p + 2 * rec);
-  int64_t *head_seg = reinterpret_cast<int64_t *>(p + 3 * rec);
-  int64_t *tail_seg = head_seg + align_up(sizeof(int64_t) * (size_t)nchunks, 256) / sizeof(int64_t);
-  const dim3 block(kSmWaves * kWave);
+  const SegRecords rec = sm_records(sizeof(A), E, D);
+  const int64_t nchunks = (int64_t)rec.nchunks;
+  Acc *head_val = rec.plane<Acc>(workspace, 0), *tail_val = rec.plane<Acc>(workspace, 1);
+  Acc *final_val = rec.plane<Acc>(workspace, 2);
+  int64_t *head_seg = rec.head_seg(workspace), *tail_seg = rec.tail_seg(workspace);
+  const dim3 block(kSegWaves * kWave);
   const dim3 tiles((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)D);
-  const dim3 chunks((unsigned int)ceil_div(nchunks, (int64_t)kSmWaves), (unsigned int)D);
+  const dim3 chunks((unsigned int)ceil_div(nchunks, (int64_t)kSegWaves), (unsigned int)D);
   hipLaunchKernelGGL((softmax_tile_kernel<T, M>), tiles, block, 0, stream, a, b, perm, ptr, nseg, E, D, out, head_val,
                      tail_val, head_seg, tail_seg, nchunks);
   TSAMD_LAUNCH_CHECK();
@@ -296,35 +269,21 @@ int launch_softmax(const T *a, const T *b, const int64_t *perm, const int64_t *p
   return TSAMD_OK;
 }
 
-bool sm_float_dtype(int dtype) {
-  return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-}
-
 // a, b: (value, NULL) forward, (y, grad) backward
 template <bool BW>
 int sm_entry(int dtype, const void *a, const void *b, const int64_t *perm, const int64_t *seg_ptr, int64_t nseg,
              int64_t E, int64_t D, void *out, void *workspace, size_t workspace_bytes, hipStream_t stream) {
   if (nseg < 0 || E < 0 || D < 0) return TSAMD_ERR_INVALID;
-  if (!sm_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (D > 65535) return TSAMD_ERR_UNSUPPORTED;
   if (E == 0 || D == 0) return TSAMD_OK;
   if (nseg == 0 || !out || !seg_ptr || !a || (BW && !b)) return TSAMD_ERR_INVALID;
   if (!workspace || workspace_bytes < tsamd_segment_softmax_workspace_bytes(dtype, E, D)) return TSAMD_ERR_WORKSPACE;
-  switch (dtype) {
-#define TSAMD_SM_CASE(code, elem_t)                                                                            \
-  case code: {                                                                                                 \
-    using M = typename std::conditional<BW, SmBackward<elem_t>, SmForward<elem_t>>::type;                      \
-    return launch_softmax<elem_t, M>(reinterpret_cast<const elem_t *>(a), reinterpret_cast<const elem_t *>(b), \
-                                     perm, seg_ptr, nseg, E, D, reinterpret_cast<elem_t *>(out), workspace,    \
-                                     stream);                                                                  \
-  }
-    TSAMD_SM_CASE(TSAMD_F32, float)
-    TSAMD_SM_CASE(TSAMD_F64, double)
-    TSAMD_SM_CASE(TSAMD_F16, f16_t)
-    TSAMD_SM_CASE(TSAMD_BF16, bf16_t)
-#undef TSAMD_SM_CASE
-    default: return TSAMD_ERR_UNSUPPORTED;
-  }
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    using M = typename std::conditional<BW, SmBackward<scalar_t>, SmForward<scalar_t>>::type;
+    return launch_softmax<scalar_t, M>(reinterpret_cast<const scalar_t *>(a), reinterpret_cast<const scalar_t *>(b),
+                                       perm, seg_ptr, nseg, E, D, reinterpret_cast<scalar_t *>(out), workspace, stream);
+  });
 }
 
 }  // namespace
@@ -335,7 +294,7 @@ using namespace tsamd;
 extern "C" int tsamd_segment_softmax_route(int64_t out[8]) {
   if (!out) return TSAMD_ERR_INVALID;
   for (int i = 0; i < 8; ++i) out[i] = 0;
-  out[0] = kSmChunk;
+  out[0] = kSegChunk;
   out[1] = kExpandTile;
   out[2] = kExpandTile;  // a tile stages its pointer slice when it meets at most this many segments
   out[3] = kSmFold;
@@ -343,8 +302,8 @@ extern "C" int tsamd_segment_softmax_route(int64_t out[8]) {
 }
 
 extern "C" size_t tsamd_segment_softmax_workspace_bytes(int dtype, int64_t E, int64_t D) {
-  if (!sm_float_dtype(dtype)) return 0;
-  return dtype == TSAMD_F64 ? sm_workspace_bytes<double>(E, D) : sm_workspace_bytes<float>(E, D);
+  if (!is_float_dtype(dtype)) return 0;
+  return sm_records(acc_size(dtype), E, D).bytes();
 }
 
 extern "C" int tsamd_segment_softmax(int dtype, const void *value, const int64_t *perm, const int64_t *seg_ptr,

@@ -7,20 +7,16 @@
 // and every list element contributes  w[t] * gC[find(row, col)]  with one of (row, col) fixed per segment and
 // the other read from the list.  One kernel family, templated on the side and the value type.
 //
-// Balanced by PRODUCTS (expand.h), not by segments: ptr[S + 1] = exclusive scan of the list lengths
-// (tsamd_spspmm_bw_plan), a workgroup owns kExpandTile consecutive products, stages the slice of ptr that
-// intersects them in LDS together with, per staged segment, the start of its list and its fixed index (one
-// binary search over the row pointers per SEGMENT, not per product).  The list arrays are read coalesced: lanes
-// with consecutive products of one segment read consecutive list elements.
+// Balanced by PRODUCTS on the tiling of segtile.h: ptr[S + 1] = exclusive scan of the list lengths
+// (tsamd_spspmm_bw_plan) is the segmented order.  Beside the slice of ptr a tile stages, per staged segment, the start
+// of its list and its fixed index (one binary search over the row pointers per SEGMENT, not per product).  The list
+// arrays are read coalesced: lanes with consecutive products of one segment read consecutive list elements.
 //
-//   tile kernel   4 waves x 8 windows of 64 products.  A lane finds its segment by an LDS binary search, loads
-//                 (index, weight) of its list element, finds the entry of C by a binary search over the sorted
-//                 row of C (64-bit compares: column ids go up to 2^32 - 3) and forms the term.  Wave-level
-//                 segmented inclusive scan (registers / bpermute), a wave-uniform carry links the windows; the
-//                 lane that holds a segment's last product writes the sum.  Pieces of segments that cross a
-//                 wave's chunk go to LDS, where one thread links the four waves in order; what crosses the TILE
-//                 becomes the tile's HEAD record (the segment began before the tile and ends in it) and TAIL
-//                 record (the segment is still open at the end of the tile): two records per tile.
+//   tile kernel   a lane loads (index, weight) of its list element, finds the entry of C by a binary search over the
+//                 sorted row of C (64-bit compares: column ids go up to 2^32 - 3) and forms the term; the lane that
+//                 holds a segment's last product writes the sum.  Pieces of segments that cross a wave's chunk go to
+//                 LDS, where one thread links the four waves in order; what crosses the TILE becomes the tile's HEAD
+//                 and TAIL record: two records per tile.
 //   fix-up        one wave per tile with a head record folds the tail records of the tiles before it (fixed
 //                 strides and butterfly; fp32 pieces fold in fp64) and writes the segment.
 //
@@ -30,17 +26,11 @@
 //
 // Routes (tsamd_spspmm_bw_route): a tile that intersects more than kExpandTile segments (long runs of segments
 // with empty lists) does not stage; its lanes search the global arrays instead.
-#include "common.h"
-#include "expand.h"
 #include "scan.h"
+#include "segtile.h"
 
 namespace tsamd {
 namespace {
-
-constexpr int kBwWindows = 8;
-constexpr int kBwChunk = kWave * kBwWindows;        // products per wave
-constexpr int kBwWaves = kExpandTile / kBwChunk;    // waves per workgroup (4)
-static_assert(kBwWaves * kBwChunk == kExpandTile, "tile = waves x chunk");
 
 // List length of segment s (the row of entry s of a CSR pattern is the last r with rowptr[r] <= s:
 // segment_of).  SIDE 0: the list is row colA[s] of B.  SIDE 1: column (row of s in B) of A.
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256) void spspmm_bw_len_kernel(const int64_t *__res
 __global__ void spspmm_bw_stats_kernel(const int64_t *__restrict__ total, int64_t acc_bytes,
                                        int64_t *__restrict__ stats) {
   const int64_t P = *total;
-  const int64_t ntiles = ((P > 0 ? P : 1) + kExpandTile - 1) / kExpandTile;  // as bw_workspace_bytes counts them
+  const int64_t ntiles = ((P > 0 ? P : 1) + kExpandTile - 1) / kExpandTile;  // as bw_records counts them
   const int64_t per = (ntiles * acc_bytes + 255) / 256 * 256 + (ntiles * 8 + 255) / 256 * 256;
   stats[0] = 2 * per;
   stats[1] = P;
@@ -83,7 +73,7 @@ __device__ __forceinline__ int64_t find_in_row(const int64_t *__restrict__ rowpt
 }
 
 template <typename T, int SIDE>
-__global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void spspmm_bw_tile_kernel(
     const int64_t *__restrict__ ptr, int64_t nseg, int64_t P, const int64_t *__restrict__ segptr, int64_t nrows,
     const int64_t *__restrict__ segind, const int64_t *__restrict__ listptr, const int64_t *__restrict__ list_ind,
     const T *__restrict__ list_val, const int64_t *__restrict__ rowptrC, const int64_t *__restrict__ colC,
@@ -93,20 +83,17 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
   __shared__ int64_t sl[kExpandTile];       // start of the segment's list
   __shared__ uint32_t sf[kExpandTile];      // its fixed index: row of C (SIDE 0, < 2^31) | column of C (SIDE 1, < 2^32)
   __shared__ int64_t span[2];
-  __shared__ int64_t wh_seg[kBwWaves], wt_seg[kBwWaves];
-  __shared__ int32_t wh_in[kBwWaves];       // the head segment of the wave began inside this tile
-  __shared__ T wh_val[kBwWaves], wt_val[kBwWaves];
+  __shared__ int64_t wh_seg[kSegWaves], wt_seg[kSegWaves];
+  __shared__ int32_t wh_in[kSegWaves];       // the head segment of the wave began inside this tile
+  __shared__ T wh_val[kSegWaves], wt_val[kSegWaves];
   const int64_t e0 = (int64_t)blockIdx.x * kExpandTile;
   const int64_t e1 = e0 + kExpandTile < P ? e0 + kExpandTile : P;
-  int64_t lo, hi;
-  tile_span(ptr, nseg, e0, e1, span, &lo, &hi);
-  const int64_t S = hi - lo + 1;
-  const bool staged = S <= kExpandTile;
-  if (staged) {
-    for (int i = threadIdx.x; i <= (int)S; i += blockDim.x) {
-      const int64_t s = lo + i;
+  const SegSlice slice = slice_bounds(ptr, nseg, e0, e1, span);
+  if (slice.staged) {
+    for (int i = threadIdx.x; i <= (int)slice.S; i += blockDim.x) {
+      const int64_t s = slice.lo + i;
       sp[i] = ptr[s];
-      if (i < (int)S) {
+      if (i < (int)slice.S) {
         const int64_t r = segment_of(segptr, nrows, s), c = segind[s];
         sl[i] = listptr[SIDE == 0 ? c : r];
         sf[i] = (uint32_t)(SIDE == 0 ? r : c);
@@ -121,15 +108,15 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
     wh_val[wave] = wt_val[wave] = T(0);
   }
   __syncthreads();
-  const int64_t c0 = e0 + (int64_t)wave * kBwChunk;
-  const int64_t c1 = c0 + kBwChunk < e1 ? c0 + kBwChunk : e1;
+  const int64_t c0 = e0 + (int64_t)wave * kSegChunk;
+  const int64_t c1 = c0 + kSegChunk < e1 ? c0 + kSegChunk : e1;
 
   int64_t cseg = -1;  // wave-uniform carry: the segment still open at the end of the last window
   T cval = T(0);
   int64_t hseg = -1;  // the segment that began before this chunk and ends in it (set by at most one lane)
   T hval = T(0);
   int32_t hin = 0;
-  for (int w = 0; w < kBwWindows; ++w) {
+  for (int w = 0; w < kSegWindows; ++w) {
     const int64_t base = c0 + (int64_t)w * kWave;
     if (base >= c1) break;
     const int64_t t = base + lane;
@@ -138,15 +125,15 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
     T v = T(0);
     if (valid) {
       int64_t lstart, fixed;
-      if (staged) {
-        const int i = segment_of_lds(sp, (int)S, t);
-        seg = lo + i;
+      if (slice.staged) {
+        const int i = segment_of_lds(sp, (int)slice.S, t);
+        seg = slice.lo + i;
         sstart = sp[i];
         send = sp[i + 1];
         lstart = sl[i];
         fixed = (int64_t)sf[i];
       } else {
-        seg = lo + segment_of(ptr + lo, S, t);
+        seg = slice.lo + segment_of(ptr + slice.lo, slice.S, t);
         sstart = ptr[seg];
         send = ptr[seg + 1];
         const int64_t r = segment_of(segptr, nrows, seg), c = segind[seg];
@@ -197,7 +184,7 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
   if (threadIdx.x == 0) {  // link the waves in product order
     int64_t oseg = -1, ths = -1;
     T oval = T(0), thv = T(0);
-    for (int w = 0; w < kBwWaves; ++w) {
+    for (int w = 0; w < kSegWaves; ++w) {
       if (wh_seg[w] != -1) {
         const T v = oseg == wh_seg[w] ? oval + wh_val[w] : wh_val[w];
         if (wh_in[w]) {
@@ -215,7 +202,7 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
           oseg = wt_seg[w];
           oval = wt_val[w];
         }
-      } else if (w * kBwChunk < e1 - e0) {
+      } else if (w * kSegChunk < e1 - e0) {
         oseg = -1;
       }
     }
@@ -227,13 +214,13 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_tile_kernel(
 }
 
 template <typename T>
-__global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_fixup_kernel(
+__global__ __launch_bounds__(kSegWaves *kWave) void spspmm_bw_fixup_kernel(
     T *__restrict__ out, const T *__restrict__ head_val, const T *__restrict__ tail_val,
     const int64_t *__restrict__ head_seg, const int64_t *__restrict__ tail_seg, int64_t ntiles) {
   // fp32 pieces of a long segment fold in fp64 (as the SpMM and segment-reduce fix-ups do)
   using W = double;
   const int lane = (int)(threadIdx.x & 63);
-  const int64_t b = (int64_t)blockIdx.x * kBwWaves + (threadIdx.x >> 6);
+  const int64_t b = (int64_t)blockIdx.x * kSegWaves + (threadIdx.x >> 6);
   if (b >= ntiles) return;
   const int64_t s = head_seg[b];
   if (s < 0) return;
@@ -252,37 +239,25 @@ __global__ __launch_bounds__(kBwWaves *kWave) void spspmm_bw_fixup_kernel(
   if (lane == 0) out[s] = (T)(acc + (W)head_val[b]);
 }
 
-struct BwWorkspace {
-  void *head_val, *tail_val;
-  int64_t *head_seg, *tail_seg;
-};
-
-size_t bw_workspace_bytes(size_t elem, int64_t P) {
-  const size_t ntiles = (size_t)ceil_div(P > 0 ? P : 1, (int64_t)kExpandTile);
-  return 2 * (align_up(elem * ntiles, 256) + align_up(sizeof(int64_t) * ntiles, 256));
-}
+// two records per tile
+SegRecords bw_records(size_t elem, int64_t P) { return SegRecords(P, kExpandTile, {elem, elem}); }
 
 template <typename T, int SIDE>
 int launch_bw(const int64_t *ptr, int64_t nseg, int64_t P, const int64_t *segptr, int64_t nrows,
               const int64_t *segind, const int64_t *listptr, const int64_t *list_ind, const void *list_val,
               const int64_t *rowptrC, const int64_t *colC, const void *gC, void *out, void *workspace,
               hipStream_t stream) {
-  const int64_t ntiles = ceil_div(P, (int64_t)kExpandTile);
-  char *p = reinterpret_cast<char *>(workspace);
-  T *head_val = reinterpret_cast<T *>(p);
-  p += align_up(sizeof(T) * (size_t)ntiles, 256);
-  T *tail_val = reinterpret_cast<T *>(p);
-  p += align_up(sizeof(T) * (size_t)ntiles, 256);
-  int64_t *head_seg = reinterpret_cast<int64_t *>(p);
-  p += align_up(sizeof(int64_t) * (size_t)ntiles, 256);
-  int64_t *tail_seg = reinterpret_cast<int64_t *>(p);
-  hipLaunchKernelGGL((spspmm_bw_tile_kernel<T, SIDE>), dim3((unsigned int)ntiles), dim3(kBwWaves * kWave), 0, stream,
+  const SegRecords rec = bw_records(sizeof(T), P);
+  const int64_t ntiles = (int64_t)rec.nchunks;
+  T *head_val = rec.plane<T>(workspace, 0), *tail_val = rec.plane<T>(workspace, 1);
+  int64_t *head_seg = rec.head_seg(workspace), *tail_seg = rec.tail_seg(workspace);
+  hipLaunchKernelGGL((spspmm_bw_tile_kernel<T, SIDE>), dim3((unsigned int)ntiles), dim3(kSegWaves * kWave), 0, stream,
                      ptr, nseg, P, segptr, nrows, segind, listptr, list_ind, reinterpret_cast<const T *>(list_val),
                      rowptrC, colC, reinterpret_cast<const T *>(gC), reinterpret_cast<T *>(out), head_val, tail_val,
                      head_seg, tail_seg);
   TSAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((spspmm_bw_fixup_kernel<T>), dim3((unsigned int)ceil_div(ntiles, (int64_t)kBwWaves)),
-                     dim3(kBwWaves * kWave), 0, stream, reinterpret_cast<T *>(out), (const T *)head_val,
+  hipLaunchKernelGGL((spspmm_bw_fixup_kernel<T>), dim3((unsigned int)ceil_div(ntiles, (int64_t)kSegWaves)),
+                     dim3(kSegWaves * kWave), 0, stream, reinterpret_cast<T *>(out), (const T *)head_val,
                      (const T *)tail_val, (const int64_t *)head_seg, (const int64_t *)tail_seg, ntiles);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
@@ -299,7 +274,7 @@ extern "C" int tsamd_spspmm_bw_route(int dtype, int64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = kExpandTile;  // products per tile
   out[1] = kExpandTile;  // a tile that intersects more segments than this searches global memory
-  out[2] = kBwChunk;     // products per wave (pieces are linked in LDS across the waves of a tile)
+  out[2] = kSegChunk;     // products per wave (pieces are linked in LDS across the waves of a tile)
   out[3] = 2;            // carry records per tile
   return TSAMD_OK;
 }
@@ -309,7 +284,7 @@ extern "C" size_t tsamd_spspmm_bw_plan_workspace_bytes(int64_t nseg) {
 }
 
 extern "C" size_t tsamd_spspmm_bw_workspace_bytes(int dtype, int64_t P) {
-  return bw_workspace_bytes(dtype == TSAMD_F64 ? 8 : 4, P);
+  return bw_records(dtype == TSAMD_F64 ? 8 : 4, P).bytes();
 }
 
 extern "C" int tsamd_spspmm_bw_plan(int dtype, int side, const int64_t *segptr, int64_t nrows,
@@ -354,7 +329,7 @@ extern "C" int tsamd_spspmm_value_bw(int dtype, int side, const int64_t *ptr, in
   if (P == 0) return TSAMD_OK;
   if (!ptr || !segptr || !segind || !listptr || !list_ind || !rowptrC || !colC || !gC) return TSAMD_ERR_INVALID;
   if (ceil_div(P, (int64_t)kExpandTile) >= ((int64_t)1 << 31)) return TSAMD_ERR_UNSUPPORTED;
-  if (!workspace || workspace_bytes < bw_workspace_bytes(elem, P)) return TSAMD_ERR_WORKSPACE;
+  if (!workspace || workspace_bytes < bw_records(elem, P).bytes()) return TSAMD_ERR_WORKSPACE;
   if (dtype == TSAMD_F32) {
     if (side == 0)
       return launch_bw<float, 0>(ptr, nseg, P, segptr, nrows, segind, listptr, list_ind, list_val, rowptrC, colC,
