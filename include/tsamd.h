@@ -634,6 +634,60 @@ int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowpt
                              void *ds_out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
                              void *stream);
 
+/* ------------------------------------------------------------------------
+ * Fused additive (GAT) attention over a pattern (csrc/attention.hip, the kernels above in their additive score
+ * mode): the score of an entry is a sum of one scalar per node and head inside a leaky ReLU, not a dot product.
+ * (rowptr, col) is the CSR order of the E entries; a_dst [nseg, H], a_src [nsrc, H], v [nsrc, H, D], out
+ * [nseg, H, D], lse [nseg, H] in the accumulator type A (float, double for float64); nseg != nsrc is allowed.  bias
+ * is NULL or holds one element of the operands' dtype per entry (bias_heads = 1) or per entry and head (bias_heads =
+ * H, [E, H]).  All arrays are contiguous and share one dtype (float32, float64, float16, bfloat16).
+ *
+ *   tsamd_gat_attention_heads     for the entries i of row r and head h, in A:
+ *                                   z(i, h) = a_dst[r, h] + a_src[col[i], h] (+ bias[i] or bias[i, h])
+ *                                   s(i, h) = z > 0 ? z : negative_slope * z     (torch's leaky_relu, also at z == 0
+ *                                                                                 and for NaN)
+ *                                   out[r, h, :] = sum_i softmax_i(s(., h)) * v[col[i], h, :]
+ *                                   lse[r, h]    = log sum_i exp(s(i, h)).
+ *                                 The bias goes INSIDE the activation (where GATConv puts its edge term), unlike the
+ *                                 bias of tsamd_attention_heads, which is added to the finished score.
+ *                                 negative_slope is any finite double (0.2 in GATConv).  Rows without entries are
+ *                                 zeros with lse = -inf.  Non-finite scores as in tsamd_attention_heads: a NaN or
+ *                                 +inf score makes its row and head NaN (lse NaN), a row of -inf scores only is NaN
+ *                                 with lse = -inf, -inf beside finite scores weighs zero.  A -inf bias masks its
+ *                                 entry only for negative_slope > 0: with a slope of 0 the IEEE product 0 * -inf is
+ *                                 NaN (and a negative slope turns it into +inf); this is not special-cased.
+ *                                 a_dst and a_src are read by element loads and need no alignment; the packet route
+ *                                 needs D * itemsize a multiple of 16 and v and out on a 16-byte boundary.  Lane
+ *                                 map, chunk, records and workspace are those of tsamd_attention_heads:
+ *                                 tsamd_attention_heads_route(dtype, H, D, NULL, NULL, v, out, route) and
+ *                                 tsamd_attention_heads_workspace_bytes(dtype, H, D, E) serve this call.  Three
+ *                                 launches (fill, tile, fix-up), deterministic, no atomics, no host sync, nothing
+ *                                 of size E written.
+ *   tsamd_gat_attention_heads_bw  per entry i of row r and head h, from the forward's out and lse:
+ *                                   p  = e(s(i, h) - lse[r, h])
+ *                                   ds = p * (<grad_out[r, h], v[col[i], h]> - <grad_out[r, h], out[r, h]>)
+ *                                   dz = ds * (z > 0 ? 1 : negative_slope)
+ *                                 p and dz are stored as [E, H] of the operands' dtype in storage order.  lse[r, h]
+ *                                 not finite: p = dz = NaN; s = -inf: p = dz = 0.  row [E] holds the row ids or is
+ *                                 NULL (then they are searched in rowptr; not both NULL).  One launch, no workspace.
+ *                                 The gradients follow: grad_a_dst[r, h] = the sum of dz over the row, grad_a_src[n,
+ *                                 h] = the sum of dz over the column (tsamd_segment_reduce), grad_bias = dz (summed
+ *                                 over the heads for a [E] bias), grad_v = spmm(columns; p, grad_out)
+ *                                 (tsamd_spmm_heads).
+ *
+ * Status: as tsamd_attention_heads and tsamd_attention_heads_bw, case for case and in their order, with a_dst for
+ * q and a_src for k.  Every one is decided on the host before the first device call.
+ * ------------------------------------------------------------------------ */
+int tsamd_gat_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                              int64_t bias_heads, const void *a_dst, const void *a_src, const void *v,
+                              double negative_slope, void *out, void *lse, int64_t nseg, int64_t nsrc, int64_t H,
+                              int64_t D, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_gat_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                 const void *bias, int64_t bias_heads, const void *a_dst, const void *a_src,
+                                 const void *v, const void *out, const void *lse, const void *grad_out,
+                                 double negative_slope, void *p_out, void *dz_out, int64_t nseg, int64_t nsrc,
+                                 int64_t H, int64_t D, int64_t E, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):

@@ -8,7 +8,7 @@ Drop-in surface (same names and argument meaning as ``torch_sparse``):
 
 and, widening along SURVEY.md section 8f (the callers either side of that path):
 
-    sum / mean / min / max, softmax (rows / columns, differentiable), sddmm / matmul_heads (multi-head attention scores and aggregation, differentiable), attention (scores, softmax and aggregation fused in one pass, differentiable), mul / add (+ _ / _nnz variants), remove_diag / set_diag / fill_diag / get_diag,
+    sum / mean / min / max, softmax (rows / columns, differentiable), sddmm / matmul_heads (multi-head attention scores and aggregation, differentiable), attention (scores, softmax and aggregation fused in one pass, differentiable), gat_attention (the same pass for additive GAT scores, differentiable), mul / add (+ _ / _nnz variants), remove_diag / set_diag / fill_diag / get_diag,
     narrow, select, index_select(_nnz), masked_select(_nnz), permute, cat, SparseTensor.__getitem__,
     sample, sample_adj, random_walk, saint_subgraph, reverse_cuthill_mckee, eye, spadd, converters
     torch.ops.torch_sparse.{non_diag_mask, sample_adj, neighbor_sample, random_walk, saint_subgraph,
@@ -61,7 +61,7 @@ from .spspmm import spspmm  # noqa: E402
 from .reduce import sum, mean, min, max  # noqa: E402,A004
 from .softmax import softmax  # noqa: E402
 from .segment import segment_softmax  # noqa: E402
-from .attention import sddmm, matmul_heads, attention  # noqa: E402
+from .attention import sddmm, matmul_heads, attention, gat_attention  # noqa: E402
 from .mul import mul, mul_, mul_nnz, mul_nnz_, add, add_, add_nnz, add_nnz_  # noqa: E402
 from .select import (narrow, __narrow_diag__, select, index_select, index_select_nnz,  # noqa: E402
                      masked_select, masked_select_nnz, permute)
@@ -76,7 +76,7 @@ from .convert import to_torch_sparse, from_torch_sparse, to_scipy, from_scipy, e
 
 __all__ = [
     'SparseStorage', 'SparseTensor', 't', 'transpose', 'matmul', 'coalesce', 'spmm', 'spspmm',
-    'sum', 'mean', 'min', 'max', 'softmax', 'segment_softmax', 'sddmm', 'matmul_heads', 'attention', 'mul', 'mul_', 'mul_nnz', 'mul_nnz_', 'add', 'add_', 'add_nnz',
+    'sum', 'mean', 'min', 'max', 'softmax', 'segment_softmax', 'sddmm', 'matmul_heads', 'attention', 'gat_attention', 'mul', 'mul_', 'mul_nnz', 'mul_nnz_', 'add', 'add_', 'add_nnz',
     'add_nnz_', 'narrow', '__narrow_diag__', 'select', 'index_select', 'index_select_nnz',
     'masked_select', 'masked_select_nnz', 'permute', 'cat', 'remove_diag', 'set_diag', 'fill_diag',
     'get_diag', 'sample', 'sample_adj', 'random_walk', 'saint_subgraph', 'reverse_cuthill_mckee', 'partition', 'to_torch_sparse', 'from_torch_sparse', 'to_scipy', 'from_scipy', 'eye', 'spadd',

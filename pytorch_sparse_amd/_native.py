@@ -33,6 +33,7 @@ SYMBOLS = [
     'tsamd_segment_softmax_route', 'tsamd_segment_softmax_workspace_bytes', 'tsamd_segment_softmax', 'tsamd_segment_softmax_bw',
     'tsamd_sddmm_heads_route', 'tsamd_sddmm_heads', 'tsamd_spmm_heads_route', 'tsamd_spmm_heads_workspace_bytes', 'tsamd_spmm_heads',
     'tsamd_attention_heads_route', 'tsamd_attention_heads_workspace_bytes', 'tsamd_attention_heads', 'tsamd_attention_heads_bw',
+    'tsamd_gat_attention_heads', 'tsamd_gat_attention_heads_bw',
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
     'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
     'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
@@ -108,6 +109,8 @@ def lib():
         L.tsamd_attention_heads_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_attention_heads.argtypes = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
         L.tsamd_attention_heads_bw.argtypes = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
+        L.tsamd_gat_attention_heads.argtypes = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
+        L.tsamd_gat_attention_heads_bw.argtypes = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
         L.tsamd_select_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_tiles_workspace_bytes.restype = ctypes.c_size_t

@@ -20,6 +20,12 @@ in one pass over the entries, so the forward writes nothing of size ``nnz``.  It
 ``lse = log sum exp(score)`` for the backward, where one kernel (``tsamd::attention_heads_bw``) recomputes the
 probabilities ``p`` and the score gradients ``ds = p * (<grad_out, v> - <grad_out, out>)`` per entry and
 ``tsamd::spmm_heads`` turns them into ``grad_q``, ``grad_k`` and ``grad_v``; ``ds`` itself is the gradient of the bias.
+
+``gat_attention(adj, a_dst, a_src, v, negative_slope=0.2, bias=False)`` is the same fused pass for the additive score
+of a graph attention network (``tsamd::gat_attention_heads``): ``leaky_relu(a_dst[row] + a_src[col] (+ the edge
+term))`` with one scalar per node and head, so no ``[nnz, H]`` gather, add, activation or softmax array is written.
+Its backward kernel (``tsamd::gat_attention_heads_bw``) gives ``p`` and ``dz``, the gradient of the pre-activation;
+``tsamd::segment_reduce`` sums ``dz`` over the rows into ``grad_a_dst`` and over the columns into ``grad_a_src``.
 """
 from typing import Optional
 
@@ -137,6 +143,48 @@ class _AttentionHeads(torch.autograd.Function):
         return grad_q, grad_k, grad_v, grad_bias, None, None, None, None, None, None, None
 
 
+class _GatAttentionHeads(torch.autograd.Function):
+    """out = tsamd::gat_attention_heads; backward: (p, dz) = tsamd::gat_attention_heads_bw, then grad_a_dst = the sum of dz
+    over the rows, grad_a_src = the sum of dz over the columns (tsamd::segment_reduce), grad_v = spmm_heads(columns; p,
+    grad_out), grad_bias = dz"""
+
+    @staticmethod
+    def forward(ctx, a_dst: Tensor, a_src: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor],
+                rowptr: Tensor, col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor],
+                csr2csc: Optional[Tensor], negative_slope: float):
+        b = None if bias is None else bias.detach()
+        out, lse = torch.ops.tsamd.gat_attention_heads(rowptr, col, b, a_dst.detach(), a_src.detach(), v.detach(),
+                                                       negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
+        ctx.save_for_backward(*([a_dst, a_src, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
+                                ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        a_dst, a_src, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        bias = rest.pop(0) if ctx.has_bias else None
+        row = rest.pop(0) if ctx.has_row else None
+        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
+        p, dz = torch.ops.tsamd.gat_attention_heads_bw(row, rowptr, col, bias, a_dst, a_src, v, out, lse, g,
+                                                       ctx.negative_slope)
+        grad_dst = grad_src = grad_v = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_dst = torch.ops.tsamd.segment_reduce(dz, None, rowptr, a_dst.size(0), 'sum', True)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            colptr, row_csc, csr2csc = rest
+            if ctx.needs_input_grad[1]:
+                grad_src = torch.ops.tsamd.segment_reduce(dz, csr2csc, colptr, a_src.size(0), 'sum', True)
+            if ctx.needs_input_grad[2]:
+                grad_v = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, p, g, v.size(0))
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            grad_bias = dz if bias.dim() == 2 else dz.sum(1, dtype=lse.dtype).to(dz.dtype)
+        return grad_dst, grad_src, grad_v, grad_bias, None, None, None, None, None, None, None
+
+
 def _check_operand(t: Tensor, name: str, rows: int, what: str) -> None:
     if not isinstance(t, Tensor):
         raise TypeError('%s must be a Tensor' % name)
@@ -252,6 +300,67 @@ def attention(adj: SparseTensor, q: Tensor, k: Tensor, v: Tensor, scale: Optiona
     return out.squeeze(1) if flat else out
 
 
+def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, negative_slope: float = 0.2,
+                  bias: bool = False) -> Tensor:
+    """Additive (graph attention network) attention over the pattern of ``adj`` in one fused pass: for row ``m`` and head
+    ``h`` the score of a stored entry ``(m, n)`` is ``leaky_relu(a_dst[m, h] + a_src[n, h] + b, negative_slope)``, where
+    ``b`` is, with ``bias=True``, the entry's own value (``[nnz]`` shared by the heads or ``[nnz, H]``) and zero without;
+    ``out[m, h] = sum_n softmax_n(score) * v[n, h]``.  ``a_dst [M, H]``, ``a_src [N, H]``, ``v [N, H, D]`` -> ``[M, H, D]``;
+    1-D ``a_dst`` / ``a_src`` with a 2-D ``v`` mean one head.  Rows without entries are zeros.
+
+    The bias goes INSIDE the activation, where ``GATConv`` puts its edge term -- unlike the bias of ``attention``, which
+    is added to the finished score.  So a ``-inf`` value masks its entry only for ``negative_slope > 0``: with a slope
+    of ``0`` the product ``0 * -inf`` is NaN (IEEE) and the row is NaN; this is not special-cased.
+
+    Differentiable (once) w.r.t. ``a_dst``, ``a_src``, ``v`` and, with ``bias=True``, the values; the derivative of the
+    activation at ``z == 0`` is ``negative_slope``, as torch has it."""
+    for t, name in ((a_dst, 'a_dst'), (a_src, 'a_src'), (v, 'v')):
+        if not isinstance(t, Tensor):
+            raise TypeError('%s must be a Tensor' % name)
+    if not (a_dst.dim() == a_src.dim() == v.dim() - 1) or v.dim() not in (2, 3):
+        raise ValueError('a_dst, a_src and v must be [rows], [columns] and [columns, D] or [rows, H], [columns, H] and '
+                         '[columns, H, D], got %d, %d and %d dimensions' % (a_dst.dim(), a_src.dim(), v.dim()))
+    _check_operand(a_dst, 'a_dst', adj.sparse_size(0), 'rows')
+    _check_operand(a_src, 'a_src', adj.sparse_size(1), 'columns')
+    _check_operand(v, 'v', adj.sparse_size(1), 'columns')
+    if a_dst.dtype != a_src.dtype or a_dst.dtype != v.dtype:
+        raise ValueError('a_dst, a_src and v differ in dtype: %s, %s and %s' % (a_dst.dtype, a_src.dtype, v.dtype))
+    flat = v.dim() == 2
+    if flat:
+        a_dst, a_src, v = a_dst.unsqueeze(1), a_src.unsqueeze(1), v.unsqueeze(1)
+    H, D = v.size(1), v.size(2)
+    if a_dst.size(1) != H or a_src.size(1) != H:
+        raise ValueError('a_dst has %d heads, a_src has %d, v has %d: the heads must agree'
+                         % (a_dst.size(1), a_src.size(1), H))
+    if D == 0:
+        raise ValueError('gat_attention needs at least one feature per head')
+    negative_slope = float(negative_slope)
+    if negative_slope != negative_slope or negative_slope in (float('inf'), float('-inf')):
+        raise ValueError('negative_slope must be finite, got %r' % negative_slope)
+    b = None
+    if bias:
+        b = adj.storage.value()
+        if b is None:
+            raise ValueError('bias=True needs a SparseTensor with values, this one has none')
+        if not b.is_floating_point():
+            raise ValueError('the bias must be floating point, got %s values' % b.dtype)
+        if b.dim() not in (1, 2) or (b.dim() == 2 and b.size(1) != H):
+            raise ValueError('the bias must be [nnz] or [nnz, %d] values (v has %d heads), got %s'
+                             % (H, H, tuple(b.shape)))
+        b = b.to(v.dtype)
+    st = adj.storage
+    rowptr, col = st.rowptr(), st.col()
+    grad = torch.is_grad_enabled()
+    if grad and (a_dst.requires_grad or a_src.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
+        csc = _csc_side(st) if a_src.requires_grad or v.requires_grad else (None, None, None)
+        out = _GatAttentionHeads.apply(a_dst, a_src, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], negative_slope)
+    else:
+        out = torch.ops.tsamd.gat_attention_heads(rowptr, col, b, a_dst, a_src, v, negative_slope)[0]
+    return out.squeeze(1) if flat else out
+
+
+SparseTensor.gat_attention = (lambda self, a_dst, a_src, v, negative_slope=0.2, bias=False:
+                              gat_attention(self, a_dst, a_src, v, negative_slope, bias))
 SparseTensor.attention = lambda self, q, k, v, scale=None, bias=False: attention(self, q, k, v, scale, bias)
 SparseTensor.sddmm = lambda self, q, k, scale=1.0: sddmm(self, q, k, scale)
 SparseTensor.matmul_heads = lambda self, x: matmul_heads(self, x)

@@ -44,6 +44,16 @@
 // lanes per head, heads and entries side by side.  An entry's ids are read once; three dot products share the
 // butterfly: s = scale * <q, k> + bias, dp = <grad_out[row], v[col]>, delta = <grad_out[row], out[row]>.  It stores
 // p = e(s - lse[row]) and ds = p * (dp - delta) as [E, H]; lse not finite: NaN both; s = -inf: 0 both.  One launch.
+//
+// Additive (GAT) scores (tsamd_gat_attention_heads, MODE = kAtAdditive of the same two kernels): one scalar per node
+// and head instead of a dot product,
+//   z(i, h) = a_dst[r, h] + a_src[col[i], h] (+ bias inside the activation),   s = z > 0 ? z : negative_slope * z.
+// The kernels take a_dst for q, a_src for k and the slope for scale.  No q / k packets and no butterfly: the LPH lanes
+// of head h all load the element a_src[col * H + h], in the batch of kAtBatch gathers beside the v packets; a_dst[row
+// * H + h] is reloaded where the segment changes (the qrow logic); every feature block of a WIDE head forms the score
+// itself.  a_dst / a_src are element loads of any alignment: the packet route is decided by v, out and D.  Lane map,
+// chunk, records, fix-up, fill and workspace are those above.  The backward keeps two dot products (dp, delta) in the
+// butterfly and stores p and dz = ds * (z > 0 ? 1 : negative_slope).
 #include "segtile.h"
 
 #include <type_traits>
@@ -55,6 +65,8 @@ constexpr int kAtWaves = kSegWaves;
 constexpr int kAtBatch = 4;     // entries whose gathers are in flight
 constexpr int kAtFwHeads = 64;  // heads side by side at most: forward (a whole wave),
 constexpr int kAtBwHeads = 16;  // backward (H above takes passes)
+constexpr int kAtDot = 0;       // score modes: scale * <q, k> + bias,
+constexpr int kAtAdditive = 1;  // leaky_relu(a_dst + a_src + bias)
 
 struct AtPlan {
   int generic;
@@ -68,6 +80,12 @@ struct AtPlan {
 
 __device__ __forceinline__ float at_log(float x) { return logf(x); }
 __device__ __forceinline__ double at_log(double x) { return log(x); }
+
+// torch's leaky_relu: z > 0 ? z : z * slope, also at z == 0 and for NaN
+template <typename A>
+__device__ __forceinline__ A at_leaky(A z, A slope) {
+  return z > A(0) ? z : z * slope;
+}
 
 // the lane map: a function of (dtype, H, D) alone
 void at_lanes(int dtype, int64_t H, int64_t D, int max_heads, AtPlan *p) {
@@ -153,7 +171,7 @@ __global__ __launch_bounds__(256) void attention_fill_kernel(unsigned char *__re
   if (i < nlse) lse[i] = -std::numeric_limits<A>::infinity();
 }
 
-template <typename T, bool PACKED, bool WIDE>
+template <typename T, bool PACKED, bool WIDE, int MODE>
 __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
     const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind, const T *__restrict__ bias, int64_t bias_heads,
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ x, typename Traits<T>::acc_t scale,
@@ -214,7 +232,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
       int32_t fl[kAtBatch], sg[kAtBatch];
       uint32_t cc[kAtBatch];
       P kx[kAtBatch], xv[kAtBatch];
-      A bb[kAtBatch];
+      A bb[kAtBatch], sa[kAtBatch];
 #pragma unroll
       for (int u = 0; u < kAtBatch; ++u) {
         const int j = j0 + u;
@@ -225,10 +243,13 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
         kx[u] = P();
         xv[u] = P();
         bb[u] = A(0);
+        sa[u] = A(0);
         if ((fl[u] & kSegValid) && hok) {
           const uint64_t at = (uint64_t)cc[u] * (uint64_t)W + (uint64_t)hoff;
+          if constexpr (MODE == kAtAdditive)  // a_src[col, h]: the lanes of the head read one address
+            sa[u] = Traits<T>::to_acc(k[(uint64_t)cc[u] * (uint64_t)H + (uint64_t)h]);
           if (colok) {
-            if constexpr (!WIDE) kx[u] = at_load<T, PACKED>(k + at, d0, D);
+            if constexpr (!WIDE && MODE == kAtDot) kx[u] = at_load<T, PACKED>(k + at, d0, D);
             xv[u] = at_load<T, PACKED>(x + at, d0, D);
           }
           if (bias) {
@@ -241,7 +262,13 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
       for (int u = 0; u < kAtBatch; ++u) {
         const bool valid = (fl[u] & kSegValid) != 0;
         A part = A(0);
-        if constexpr (WIDE) {
+        if constexpr (MODE == kAtAdditive) {
+          if (valid && sg[u] != qrow) {  // the segment changes: a_dst[row, h]
+            qrow = sg[u];
+            qa[0] = hok ? Traits<T>::to_acc(q[(uint64_t)qrow * (uint64_t)H + (uint64_t)h]) : A(0);
+          }
+          if (valid) part = qa[0] + sa[u];
+        } else if constexpr (WIDE) {
           if (valid && hok) {
             const T *qr = q + (uint64_t)sg[u] * (uint64_t)W + (uint64_t)hoff;
             const T *kr = k + (uint64_t)cc[u] * (uint64_t)W + (uint64_t)hoff;
@@ -264,9 +291,12 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
             for (int v = 0; v < VEC; ++v) part += qa[v] * Traits<T>::to_acc(kx[u].v[v]);
           }
         }
-        for (int off = lph >> 1; off > 0; off >>= 1) part += lane_xor(part, off);  // inside the head: off < lph
+        if constexpr (MODE == kAtDot)
+          for (int off = lph >> 1; off > 0; off >>= 1) part += lane_xor(part, off);  // inside the head: off < lph
         if (valid) {  // an entry beyond the chunk adds nothing
-          const A s = part * scale + bb[u];
+          A s;
+          if constexpr (MODE == kAtAdditive) s = at_leaky(part + bb[u], scale);  // the bias inside the activation
+          else s = part * scale + bb[u];
           cur = sg[u];
           open = true;
           const SoftScale<A> sc = soft_scale(m, s);
@@ -361,7 +391,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_fixup_kernel(
   }
 }
 
-template <typename T>
+template <typename T, int MODE>
 int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, const void *bias, int64_t bias_heads,
                      const void *q, const void *k, const void *v, double scale, void *out, void *lse, int64_t nseg,
                      int64_t H, int64_t D, int64_t E, void *workspace, hipStream_t stream) {
@@ -387,9 +417,9 @@ int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, co
   const T *bb = reinterpret_cast<const T *>(bias), *qq = reinterpret_cast<const T *>(q),
           *kk = reinterpret_cast<const T *>(k), *xx = reinterpret_cast<const T *>(v);
 #define TSAMD_AT_LAUNCH(PACKED, WIDE)                                                                              \
-  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE>), tiles, block, 0, stream, ptr, ind, bb, bias_heads, \
-                     qq, kk, xx, (A)scale, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg, tail_seg, nseg, \
-                     E, H, D, p.lg_lph, p.lg_hpp, p.fblocks)
+  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE, MODE>), tiles, block, 0, stream, ptr, ind, bb,        \
+                     bias_heads, qq, kk, xx, (A)scale, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg,     \
+                     tail_seg, nseg, E, H, D, p.lg_lph, p.lg_hpp, p.fblocks)
   if (p.fblocks > 1) {
     if (p.generic) TSAMD_AT_LAUNCH(false, true); else TSAMD_AT_LAUNCH(true, true);
   } else {
@@ -405,7 +435,7 @@ int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, co
 }
 
 // ---- backward: p and ds per entry and head ---------------------------------------------------------------------------
-template <typename T, bool PACKED>
+template <typename T, bool PACKED, int MODE>
 __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
     const int64_t *__restrict__ row, const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind,
     const T *__restrict__ bias, int64_t bias_heads, const T *__restrict__ q, const T *__restrict__ k,
@@ -453,20 +483,31 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
         const uint64_t ar = (uint64_t)r * (uint64_t)W + (uint64_t)(h * D);
         const uint64_t ac = (uint64_t)c * (uint64_t)W + (uint64_t)(h * D);
         for (int64_t sl = kl; sl < slots; sl += lph) {
-          const P qv = at_load<T, PACKED>(q + ar, sl * VEC, D), kv = at_load<T, PACKED>(k + ac, sl * VEC, D);
-          const P xv = at_load<T, PACKED>(x + ac, sl * VEC, D), gv = at_load<T, PACKED>(go + ar, sl * VEC, D);
-          const P ov = at_load<T, PACKED>(o + ar, sl * VEC, D);
+          if constexpr (MODE == kAtDot) {
+            const P qv = at_load<T, PACKED>(q + ar, sl * VEC, D), kv = at_load<T, PACKED>(k + ac, sl * VEC, D);
+            const P xv = at_load<T, PACKED>(x + ac, sl * VEC, D), gv = at_load<T, PACKED>(go + ar, sl * VEC, D);
+            const P ov = at_load<T, PACKED>(o + ar, sl * VEC, D);
 #pragma unroll
-          for (int j = 0; j < VEC; ++j) {
-            const A gj = Traits<T>::to_acc(gv.v[j]);
-            ps += Traits<T>::to_acc(qv.v[j]) * Traits<T>::to_acc(kv.v[j]);
-            pd += gj * Traits<T>::to_acc(xv.v[j]);
-            pl += gj * Traits<T>::to_acc(ov.v[j]);
+            for (int j = 0; j < VEC; ++j) {
+              const A gj = Traits<T>::to_acc(gv.v[j]);
+              ps += Traits<T>::to_acc(qv.v[j]) * Traits<T>::to_acc(kv.v[j]);
+              pd += gj * Traits<T>::to_acc(xv.v[j]);
+              pl += gj * Traits<T>::to_acc(ov.v[j]);
+            }
+          } else {  // the score needs no features
+            const P xv = at_load<T, PACKED>(x + ac, sl * VEC, D), gv = at_load<T, PACKED>(go + ar, sl * VEC, D);
+            const P ov = at_load<T, PACKED>(o + ar, sl * VEC, D);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              const A gj = Traits<T>::to_acc(gv.v[j]);
+              pd += gj * Traits<T>::to_acc(xv.v[j]);
+              pl += gj * Traits<T>::to_acc(ov.v[j]);
+            }
           }
         }
       }
       for (int off = lph >> 1; off > 0; off >>= 1) {  // inside the head: off < lph
-        ps += lane_xor(ps, off);
+        if constexpr (MODE == kAtDot) ps += lane_xor(ps, off);
         pd += lane_xor(pd, off);
         pl += lane_xor(pl, off);
       }
@@ -474,6 +515,12 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
         const int64_t e = base + idx;
         A sc = ps * scale;
         if (bias) sc += Traits<T>::to_acc(bias[bias_heads > 1 ? e * bias_heads + h : e]);
+        if constexpr (MODE == kAtAdditive) {  // ps is zero in this mode: sc holds the bias alone, ps takes d s / d z
+          sc = (Traits<T>::to_acc(q[(uint64_t)r * (uint64_t)H + (uint64_t)h]) +
+                Traits<T>::to_acc(k[(uint64_t)c * (uint64_t)H + (uint64_t)h])) + sc;  // z: the bias inside
+          ps = sc > A(0) ? A(1) : scale;
+          sc = at_leaky(sc, scale);
+        }
         const A ls = lse[(uint64_t)r * (uint64_t)H + (uint64_t)h];
         A pv, dv;
         if (!(ls - ls == A(0))) {  // -inf, +inf or NaN: the row is NaN in the forward
@@ -483,6 +530,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
         } else {
           pv = soft_exp(sc - ls);
           dv = pv * (pd - pl);
+          if constexpr (MODE == kAtAdditive) dv *= ps;  // dz
         }
         p_out[e * H + h] = Traits<T>::from_acc(pv);
         ds_out[e * H + h] = Traits<T>::from_acc(dv);
@@ -491,7 +539,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
   }
 }
 
-template <typename T>
+template <typename T, int MODE>
 int launch_attention_bw(const AtPlan &p, const int64_t *row, const int64_t *ptr, const int64_t *ind, const void *bias,
                         int64_t bias_heads, const void *q, const void *k, const void *v, const void *out,
                         const void *lse, const void *go, double scale, void *p_out, void *ds_out, int64_t nseg,
@@ -499,7 +547,7 @@ int launch_attention_bw(const AtPlan &p, const int64_t *row, const int64_t *ptr,
   using A = typename Traits<T>::acc_t;
   const dim3 grid((unsigned int)ceil_div(E, (int64_t)kAtWaves * kWave)), block(kAtWaves * kWave);
 #define TSAMD_AT_BW(PACKED)                                                                                         \
-  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED>), grid, block, 0, stream, row, ptr, ind,                       \
+  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED, MODE>), grid, block, 0, stream, row, ptr, ind,                 \
                      reinterpret_cast<const T *>(bias), bias_heads, reinterpret_cast<const T *>(q),                 \
                      reinterpret_cast<const T *>(k), reinterpret_cast<const T *>(v), reinterpret_cast<const T *>(out), \
                      reinterpret_cast<const A *>(lse), reinterpret_cast<const T *>(go), (A)scale,                   \
@@ -570,8 +618,8 @@ extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int
   }
   const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, q, k, v, out);
   return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention<scalar_t>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D, E,
-                                      workspace, stream);
+    return launch_attention<scalar_t, kAtDot>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D,
+                                              E, workspace, stream);
   });
 }
 
@@ -592,7 +640,54 @@ extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int
     return TSAMD_ERR_INVALID;
   const AtPlan p = at_plan(dtype, H, D, kAtBwHeads, q, k, v, out, grad_out);
   return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention_bw<scalar_t>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out, scale,
-                                         p_out, ds_out, nseg, H, D, E, stream);
+    return launch_attention_bw<scalar_t, kAtDot>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out,
+                                                 scale, p_out, ds_out, nseg, H, D, E, stream);
+  });
+}
+
+// ---- additive (GAT) scores: the same kernels in MODE = kAtAdditive, a_dst for q, a_src for k, the slope for scale -------
+extern "C" int tsamd_gat_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                                         int64_t bias_heads, const void *a_dst, const void *a_src, const void *v,
+                                         double negative_slope, void *out, void *lse, int64_t nseg, int64_t nsrc,
+                                         int64_t H, int64_t D, int64_t E, void *workspace, size_t workspace_bytes,
+                                         void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
+  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
+  if (nseg * H * D == 0) return TSAMD_OK;  // out has no element
+  if (!out || !lse) return TSAMD_ERR_INVALID;
+  if (E > 0) {
+    if (nsrc == 0 || !rowptr || !col || !a_dst || !a_src || !v) return TSAMD_ERR_INVALID;
+    if (!workspace || workspace_bytes < tsamd_attention_heads_workspace_bytes(dtype, H, D, E))
+      return TSAMD_ERR_WORKSPACE;
+  }
+  const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, nullptr, nullptr, v, out);  // a_dst / a_src: element loads
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    return launch_attention<scalar_t, kAtAdditive>(p, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope,
+                                                   out, lse, nseg, H, D, E, workspace, stream);
+  });
+}
+
+extern "C" int tsamd_gat_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                            const void *bias, int64_t bias_heads, const void *a_dst, const void *a_src,
+                                            const void *v, const void *out, const void *lse, const void *grad_out,
+                                            double negative_slope, void *p_out, void *dz_out, int64_t nseg,
+                                            int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
+  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
+  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
+  if (E == 0 || H == 0) return TSAMD_OK;  // p and dz have no element
+  if (D == 0) return TSAMD_ERR_INVALID;   // the forward defines no lse for D = 0
+  if (nseg == 0 || nsrc == 0 || !p_out || !dz_out || !col || !a_dst || !a_src || !v || !out || !lse || !grad_out ||
+      (!row && !rowptr))
+    return TSAMD_ERR_INVALID;
+  const AtPlan p = at_plan(dtype, H, D, kAtBwHeads, nullptr, nullptr, v, out, grad_out);
+  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
+    return launch_attention_bw<scalar_t, kAtAdditive>(p, row, rowptr, col, bias, bias_heads, a_dst, a_src, v, out, lse,
+                                                      grad_out, negative_slope, p_out, dz_out, nseg, H, D, E, stream);
   });
 }

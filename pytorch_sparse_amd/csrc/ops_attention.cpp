@@ -1,5 +1,6 @@
 // torch operator glue, part 7: sparse attention -- the multi-head SDDMM (csrc/sddmm.hip) and the multi-head SpMM over
-// [nnz, H] values (csrc/spmm_heads.hip), and the fused call with its backward kernel (csrc/attention.hip).  See ops_spmm.cpp for the conventions; pytorch_sparse_amd/attention.py holds
+// [nnz, H] values (csrc/spmm_heads.hip), and the fused calls -- dot-product and additive (GAT) scores -- with their
+// backward kernels (csrc/attention.hip).  See ops_spmm.cpp for the conventions; pytorch_sparse_amd/attention.py holds
 // the autograd pair.  (ptr, ind, perm) is a segmented order of the entries: (rowptr, col, None) or
 // (colptr, row, csr2csc).
 #include "ops_common.h"
@@ -198,6 +199,123 @@ std::tuple<Tensor, Tensor> attention_heads_bw(OptTensor row, Tensor rowptr, Tens
   return std::make_tuple(p, ds);
 }
 
+// the checks both additive operators share -> the bias made contiguous (undefined without one)
+Tensor check_gat_attention(const Tensor &rowptr, const Tensor &col, const OptTensor &bias, const Tensor &a_dst,
+                           const Tensor &a_src, const Tensor &v, double negative_slope) {
+  check_index(rowptr, "rowptr");
+  check_index(col, "col");
+  check_gpu(a_dst, "a_dst");
+  check_gpu(a_src, "a_src");
+  check_heads_operand(v, "v");
+  TORCH_CHECK(a_dst.dim() == 2, "a_dst must be [rows, heads], got ", a_dst.dim(), " dimension(s)");
+  TORCH_CHECK(a_src.dim() == 2, "a_src must be [columns, heads], got ", a_src.dim(), " dimension(s)");
+  TORCH_CHECK(a_dst.scalar_type() == v.scalar_type() && a_src.scalar_type() == v.scalar_type(),
+              "a_dst, a_src and v differ in dtype: ", a_dst.scalar_type(), ", ", a_src.scalar_type(), " and ",
+              v.scalar_type());
+  TORCH_CHECK(a_dst.get_device() == v.get_device() && a_src.get_device() == v.get_device() &&
+                  v.get_device() == col.get_device(),
+              "a_dst, a_src, v and the pattern must be on one device");
+  TORCH_CHECK(a_dst.size(1) == v.size(1), "a_dst has ", a_dst.size(1), " heads, v has ", v.size(1));
+  TORCH_CHECK(a_src.size(1) == v.size(1), "a_src has ", a_src.size(1), " heads, v has ", v.size(1));
+  TORCH_CHECK(a_src.size(0) == v.size(0), "a_src has ", a_src.size(0), " rows, v has ", v.size(0));
+  TORCH_CHECK(rowptr.numel() == a_dst.size(0) + 1, "rowptr has ", rowptr.numel(), " elements, a_dst has ",
+              a_dst.size(0), " rows");
+  TORCH_CHECK(std::isfinite(negative_slope), "negative_slope must be finite, got ", negative_slope);
+  Tensor b;
+  if (bias.has_value()) {
+    b = bias.value();
+    check_gpu(b, "bias");
+    const int64_t E = col.numel(), H = v.size(1);
+    TORCH_CHECK(b.dim() == 1 || b.dim() == 2, "bias must be [nnz] or [nnz, heads], got ", b.dim(), " dimension(s)");
+    TORCH_CHECK(b.size(0) == E, "bias has ", b.size(0), " rows, the pattern has ", E, " entries");
+    TORCH_CHECK(b.dim() == 1 || b.size(1) == H, "bias has ", b.dim() == 2 ? b.size(1) : 1, " heads, v has ", H);
+    TORCH_CHECK(b.scalar_type() == v.scalar_type(), "bias and v differ in dtype: ", b.scalar_type(), " and ",
+                v.scalar_type());
+    TORCH_CHECK(b.get_device() == v.get_device(), "bias and v must be on one device");
+    b = b.contiguous();
+  }
+  return b;
+}
+
+// fused additive (GAT) scores -> softmax over the row -> aggregation (csrc/attention.hip)
+// -> (out [M, H, D], lse [M, H])
+std::tuple<Tensor, Tensor> gat_attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor a_dst, Tensor a_src,
+                                               Tensor v, double negative_slope) {
+  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
+  const int64_t M = a_dst.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
+  c10::hip::HIPGuard guard(v.get_device());
+  a_dst = a_dst.contiguous();
+  a_src = a_src.contiguous();
+  v = v.contiguous();
+  rowptr = rowptr.contiguous();
+  col = col.contiguous();
+  Tensor out = torch::empty({M, H, D}, v.options().requires_grad(false));
+  const auto acc = v.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  Tensor lse = torch::empty({M, H}, v.options().dtype(acc).requires_grad(false));
+  if (out.numel() == 0) {
+    TORCH_CHECK(D > 0 || lse.numel() == 0, "gat_attention_heads needs at least one feature per head");
+    return std::make_tuple(out, lse);
+  }
+  const int dt = dtype_code(v);
+  Tensor ws = workspace(tsamd_attention_heads_workspace_bytes(dt, H, D, E), v);
+  check_status(tsamd_gat_attention_heads(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
+                                         b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
+                                         a_dst.data_ptr(), a_src.data_ptr(), v.data_ptr(), negative_slope,
+                                         out.data_ptr(), lse.data_ptr(), M, N, H, D, E, ws.data_ptr(),
+                                         (size_t)ws.numel(), current_stream(v)),
+               "tsamd_gat_attention_heads");
+  return std::make_tuple(out, lse);
+}
+
+// p = e(s - lse[row]) and dz = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>) * (z > 0 ? 1 : negative_slope)
+// -> two [E, H] arrays
+std::tuple<Tensor, Tensor> gat_attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias,
+                                                  Tensor a_dst, Tensor a_src, Tensor v, Tensor out, Tensor lse,
+                                                  Tensor grad_out, double negative_slope) {
+  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
+  if (row.has_value()) check_index(row.value(), "row");
+  check_heads_operand(out, "out");
+  check_heads_operand(grad_out, "grad_out");
+  check_gpu(lse, "lse");
+  const int64_t M = a_dst.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == M && out.size(1) == H && out.size(2) == D,
+              "out must be [rows, heads, features] = [", M, ", ", H, ", ", D, "], got ", out.sizes());
+  TORCH_CHECK(grad_out.sizes() == out.sizes(), "grad_out must have the shape of out, got ", grad_out.sizes(), " and ",
+              out.sizes());
+  TORCH_CHECK(out.scalar_type() == v.scalar_type() && grad_out.scalar_type() == v.scalar_type(),
+              "out, grad_out and v differ in dtype: ", out.scalar_type(), ", ", grad_out.scalar_type(), " and ",
+              v.scalar_type());
+  const auto acc = v.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == M && lse.size(1) == H && lse.scalar_type() == acc,
+              "lse must be [rows, heads] of ", acc, ", got ", lse.sizes(), " of ", lse.scalar_type());
+  TORCH_CHECK(out.get_device() == v.get_device() && grad_out.get_device() == v.get_device() &&
+                  lse.get_device() == v.get_device(),
+              "out, lse, grad_out and v must be on one device");
+  TORCH_CHECK(!row.has_value() || row.value().numel() == E, "row and col differ in length");
+  TORCH_CHECK(D > 0 || E == 0 || H == 0, "gat_attention_heads_bw needs at least one feature per head");
+  c10::hip::HIPGuard guard(v.get_device());
+  a_dst = a_dst.contiguous();
+  a_src = a_src.contiguous();
+  v = v.contiguous();
+  out = out.contiguous();
+  lse = lse.contiguous();
+  grad_out = grad_out.contiguous();
+  rowptr = rowptr.contiguous();
+  col = col.contiguous();
+  Tensor r = row.has_value() ? row.value().contiguous() : Tensor();
+  Tensor p = torch::empty({E, H}, v.options().requires_grad(false));
+  Tensor dz = torch::empty({E, H}, v.options().requires_grad(false));
+  if (p.numel() == 0) return std::make_tuple(p, dz);
+  check_status(tsamd_gat_attention_heads_bw(dtype_code(v), row.has_value() ? r.data_ptr<int64_t>() : nullptr,
+                                            rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
+                                            b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
+                                            a_dst.data_ptr(), a_src.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                            lse.data_ptr(), grad_out.data_ptr(), negative_slope, p.data_ptr(),
+                                            dz.data_ptr(), M, N, H, D, E, current_stream(v)),
+               "tsamd_gat_attention_heads_bw");
+  return std::make_tuple(p, dz);
+}
+
 }  // namespace
 }  // namespace tsamd_ops
 
@@ -215,4 +333,11 @@ static auto registry_attention =
             &attention_heads)
         .op("tsamd::attention_heads_bw(Tensor? row, Tensor rowptr, Tensor col, Tensor? bias, Tensor q, Tensor k, "
             "Tensor v, Tensor out, Tensor lse, Tensor grad_out, float scale) -> (Tensor, Tensor)",
-            &attention_heads_bw);
+            &attention_heads_bw)
+        .op("tsamd::gat_attention_heads(Tensor rowptr, Tensor col, Tensor? bias, Tensor a_dst, Tensor a_src, Tensor v, "
+            "float negative_slope) -> (Tensor, Tensor)",
+            &gat_attention_heads)
+        .op("tsamd::gat_attention_heads_bw(Tensor? row, Tensor rowptr, Tensor col, Tensor? bias, Tensor a_dst, "
+            "Tensor a_src, Tensor v, Tensor out, Tensor lse, Tensor grad_out, float negative_slope) -> "
+            "(Tensor, Tensor)",
+            &gat_attention_heads_bw);
