@@ -229,6 +229,31 @@ int tsamd_spmm_cached(int dtype, int reduce, const int64_t *rowptr, const int64_
                       int64_t K, int64_t E, void *workspace, size_t workspace_bytes, void *cache,
                       size_t cache_bytes, int cache_valid, void *stream);
 
+/* Pattern hints.  Most of what tsamd_spmm does in front of its merge kernel depends on (rowptr, col) alone: the
+ * probe's verdict, which 64-id blocks are hot and their ranks, the slot -> partition map of the column order.  A caller
+ * that multiplies by the same pattern again keeps those in a device buffer of tsamd_spmm_hints_bytes() bytes (256-byte
+ * aligned; 0 = the call is out of scope: only the shapes of the hot-block route -- sum / mean, B = 1, N >= 65536 -- are
+ * in it, TSAMD_ERR_UNSUPPORTED otherwise).
+ *   state = 1  build: the kernels of tsamd_spmm, writing those arrays into `hints`;
+ *   state = 2  reuse: the partition kernel (the table only), the copy of the hot blocks (it reads `mat`), the merge
+ *              kernel and the fix-up.  No probe, mark, bits, scatter or rank kernel and no memset.
+ * The hints are ADVISORY: they choose addresses and the order of execution, never a value.  `hints` must have been
+ * filled by a state-1 call with the same dtype, reduce class, B, M, N, K and E -- that alone makes it fit (block words
+ * for N ids, a permutation of the P partitions); what rowptr / col held then, or hold now, does not matter: results are
+ * bit-identical to tsamd_spmm with ANY such buffer, a stale one only costs time.  Nothing on the device re-validates it.
+ * A build call that takes neither route (narrow packets, column order switched off, verification mode) leaves the
+ * verdict "no" for the route it did not build.  Workspace: tsamd_spmm_workspace_bytes, unchanged.
+ *   tsamd_spmm_hints_layout (inspection and tests; no device work): 0 out of scope, else 1 and layout[0..7] = byte
+ *   offsets in `hints` of the probe's four int counters, the order header (as tsamd_spmm_order_layout, layout[0]), the
+ *   128 chunk totals, the block words (as tsamd_spmm_hot_blocks_layout), the per-chunk lists of selected blocks and the
+ *   slot -> partition map; then P and the size in bytes. */
+size_t tsamd_spmm_hints_bytes(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E);
+int tsamd_spmm_hints_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                            int64_t *layout);
+int tsamd_spmm_hinted(int dtype, int reduce, const int64_t *rowptr, const int64_t *col, const void *value,
+                      const void *mat, void *out, int64_t *arg_out, int64_t B, int64_t M, int64_t N, int64_t K,
+                      int64_t E, void *workspace, size_t workspace_bytes, void *hints, int state, void *stream);
+
 /* Measurement aid (bench.py): same as tsamd_spmm, but brackets the three
  * kernels of the launch sequence (merge-path partition, merge, carry fix-up)
  * with hipEvents on `stream`, waits for the last one and writes their

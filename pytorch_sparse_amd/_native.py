@@ -18,6 +18,7 @@ SYMBOLS = [
     'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm_route', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_column_order', 'tsamd_spmm_order_layout', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
     'tsamd_spmm_partial_workspace_bytes', 'tsamd_spmm_partial',
     'tsamd_spmm_operand_cache_bytes', 'tsamd_spmm_cached_workspace_bytes', 'tsamd_spmm_cached',
+    'tsamd_spmm_hints_bytes', 'tsamd_spmm_hints_layout', 'tsamd_spmm_hinted',
     'tsamd_spmm_minmax_arg32', 'tsamd_spmm_minmax_bw_csc_arg32',
     'tsamd_spmm_minmax_records_in_forward', 'tsamd_spmm_minmax_records_bytes', 'tsamd_spmm_minmax_records_workspace_bytes', 'tsamd_spmm_minmax_records',
     'tsamd_spmm_minmax_winrec', 'tsamd_spmm_minmax_bw_csc_records_workspace_bytes', 'tsamd_spmm_minmax_bw_csc_records',
@@ -91,6 +92,7 @@ def lib():
         L.tsamd_spspmm_bw_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_exclusive_scan_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_partial_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_spmm_hints_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_csc_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_records_bytes.restype = ctypes.c_size_t
@@ -235,6 +237,41 @@ def spmm_order_layout(dtype, reduce, B, M, N, K, E, mat, out, workspace):
     r = dict(zip(SPMM_ORDER_FIELDS, (int(x) for x in words)))
     r['mode'] = int(mode)
     return r
+
+
+SPMM_HINTS_FIELDS = ('flags_off', 'hdr_off', 'totals_off', 'words_off', 'lists_off', 'order_off', 'P', 'bytes')
+
+
+def spmm_hints_bytes(dtype, reduce, B, M, N, K, E):
+    """C-ABI ``tsamd_spmm_hints_bytes``: the size of a pattern's hints buffer, 0 when the call is out of scope."""
+    return int(lib().tsamd_spmm_hints_bytes(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)))
+
+
+def spmm_hints_layout(dtype, reduce, B, M, N, K, E):
+    """C-ABI ``tsamd_spmm_hints_layout`` (host arithmetic): None when the call is out of scope, else a dict of
+    SPMM_HINTS_FIELDS."""
+    words = (ctypes.c_int64 * 8)()
+    if lib().tsamd_spmm_hints_layout(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), words) == 0:
+        return None
+    return dict(zip(SPMM_HINTS_FIELDS, (int(x) for x in words)))
+
+
+def spmm_hinted(rowptr, col, value, mat, reduce, hints, state, ws=None):
+    """C-ABI ``tsamd_spmm_hinted`` on one [N, K] matrix: ``hints`` a uint8 device tensor of ``spmm_hints_bytes``,
+    ``state`` 1 builds it, 2 reuses it.  Returns out."""
+    require_gpu(rowptr, col, value, mat, hints)
+    red, dt = REDUCES[reduce], dtype_code(mat.dtype)
+    M, E, N, K = rowptr.numel() - 1, col.numel(), mat.size(0), mat.size(1)
+    out = torch.empty((M, K), dtype=mat.dtype, device=mat.device)
+    L = lib()
+    if ws is None:
+        ws = workspace(L.tsamd_spmm_workspace_bytes(dt, red, _i64(1), _i64(M), _i64(N), _i64(K), _i64(E)), mat.device)
+    with torch.cuda.device(mat.device):
+        st = L.tsamd_spmm_hinted(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(None), _i64(1),
+                                 _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws), ctypes.c_size_t(ws.numel()), _ptr(hints),
+                                 ctypes.c_int(int(state)), stream_ptr(mat.device))
+    check(st, 'tsamd_spmm_hinted')
+    return out
 
 
 def spmm_partial(rowptr, col, value, mat, reduce, out, arg_out=None, arg_map=None, arg_none=0, accumulate=True,

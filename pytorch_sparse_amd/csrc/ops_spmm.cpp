@@ -18,6 +18,8 @@
 // no CPU branch: tensors must live on the GPU, anything else raises.
 #include "ops_common.h"
 
+#include <array>
+
 namespace tsamd_ops {
 namespace {
 
@@ -111,7 +113,9 @@ std::vector<int64_t> operand_cache_ctl(bool enable) {
 // Only the `tsamd::spmm_sum_owned` / `tsamd::spmm_mean_owned` ops consult it -- the ones SparseTensor.matmul
 // calls with arrays that its SparseStorage owns (immutable by the storage's contract, exactly like the
 // reference's own storage-level caches rowcount / colptr / csr2csc).  The bare reference ops
-// `torch_sparse::spmm_sum / spmm_mean` keep NO state between calls.
+// `torch_sparse::spmm_sum / spmm_mean` keep no state THAT A RESULT CAN DEPEND ON between calls: not this cache, not the
+// operand cache unless the caller opts in.  (They do keep pattern hints, below: advisory state, which moves addresses and
+// the order of execution and which no value can depend on -- a stale hint is at worst a slower call.)
 struct PatternCache {
   std::mutex mu;
   bool enabled = true;
@@ -206,6 +210,105 @@ Tensor csc_values(const Tensor &value, const Tensor &csr2csc) {
     ++pc.value_fills;
   }
   return pc.value_t;
+}
+
+// ---- pattern hints (include/tsamd.h: tsamd_spmm_hinted) ---------------------------------------------------
+// What the forward works out from (rowptr, col) alone -- the camping probe's verdict, the hot 64-id blocks and their
+// ranks, the slot -> partition map of the column order -- is kept per pattern and reused by the later calls with the
+// same pattern: the same tensors in every layer and every epoch.  ON by default and without a switch, for the bare
+// reference ops too, because the ops keep no state THAT A RESULT CAN DEPEND ON: the hints are advisory (they choose
+// addresses and the order of execution, never a value), a call with stale hints -- `col.data` overwritten in place,
+// which no version counter sees -- returns the bits of a call without any, only more slowly.  That is the difference to
+// the operand cache above, which keeps a copy of X: there a stale entry is a wrong result, hence opt-in.
+// Four entries, least recently used out (forward and transposed pattern of a training step, times two graphs).  Key:
+// the identities of rowptr and col plus every size the buffer's layout depends on (M, N, E, row bytes, dtype, reduction
+// class, B), the device, the stream (the entry's buffer is allocated, written and read on that stream only, so
+// replacing an entry is stream-ordered) and the column-order setting in force.  Inference tensors (no version counter),
+// non-contiguous inputs, capturing streams and the verification mode go without.
+struct PatternHints {
+  struct Entry {
+    TensorIdentity rowptr, col;
+    std::array<int64_t, 9> key{};
+    void *stream = nullptr;
+    Tensor buf;  // undefined: the slot is free
+    uint64_t used = 0;
+  };
+  std::mutex mu;
+  std::array<Entry, 4> entries;
+  uint64_t clock = 0;
+  int64_t builds = 0, reuses = 0;
+};
+
+PatternHints &pattern_hints_state() {
+  static PatternHints h;
+  return h;
+}
+
+// torch.ops.tsamd.pattern_hints() -> [entries, calls that built hints, calls that reused them]; drops every entry
+// (tests only: the counters only grow)
+std::vector<int64_t> pattern_hints_ctl() {
+  PatternHints &h = pattern_hints_state();
+  std::lock_guard<std::mutex> lock(h.mu);
+  int64_t n = 0;
+  for (auto &e : h.entries) {
+    n += e.buf.defined() ? 1 : 0;
+    e.buf = Tensor();
+    e.rowptr.forget();
+    e.col.forget();
+  }
+  return {n, h.builds, h.reuses};
+}
+
+// The hints buffer of this call's pattern and what to do with it (1 build, 2 reuse), or state 0: the call goes without.
+// `like`: a tensor on the call's device (the buffer is allocated under the current stream).
+std::pair<Tensor, int> pattern_hints_for(const Tensor &rowptr, const Tensor &col, int dt, int red, int64_t B, int64_t M,
+                                         int64_t N, int64_t K, int64_t E, const Tensor &like, void *stream) {
+  const size_t bytes = tsamd_spmm_hints_bytes(dt, red, B, M, N, K, E);
+  if (bytes == 0 || rowptr.is_inference() || col.is_inference() || !rowptr.is_contiguous() || !col.is_contiguous() ||
+      tsamd_spmm_reference_order(-1) != 0 || stream_is_capturing(stream))
+    return {Tensor(), 0};
+  const std::array<int64_t, 9> key = {M, N, E, K * (int64_t)like.element_size(), dt,
+                                      (red == TSAMD_MIN || red == TSAMD_MAX) ? 1 : 0, B, (int64_t)like.get_device(),
+                                      (int64_t)tsamd_spmm_column_order(-1)};
+  PatternHints &h = pattern_hints_state();
+  std::lock_guard<std::mutex> lock(h.mu);
+  PatternHints::Entry *same = nullptr, *victim = &h.entries[0];
+  for (auto &e : h.entries) {
+    if (e.buf.defined() && e.key == key && e.stream == stream && (size_t)e.buf.numel() >= bytes) {
+      if (e.rowptr.matches(rowptr) && e.col.matches(col)) {
+        e.used = ++h.clock;
+        ++h.reuses;
+        return {e.buf, 2};
+      }
+      // the same arrays after a recorded write: the entry is built anew in place
+      if (e.rowptr.ptr == rowptr.data_ptr() && e.col.ptr == col.data_ptr()) same = &e;
+    }
+    if (victim->buf.defined() && (!e.buf.defined() || e.used < victim->used)) victim = &e;
+  }
+  PatternHints::Entry &e = same != nullptr ? *same : *victim;
+  if (same == nullptr) {
+    e.buf = Tensor();  // release before the new allocation
+    e.buf = workspace(bytes, like);
+  }
+  e.rowptr.rearm(rowptr);
+  e.col.rearm(col);
+  e.key = key;
+  e.stream = stream;
+  e.used = ++h.clock;
+  ++h.builds;
+  return {e.buf, 1};
+}
+
+// a build call failed: its entry holds nothing a later call may reuse
+void pattern_hints_drop(const Tensor &buf) {
+  PatternHints &h = pattern_hints_state();
+  std::lock_guard<std::mutex> lock(h.mu);
+  for (auto &e : h.entries)
+    if (e.buf.defined() && e.buf.data_ptr() == buf.data_ptr()) {
+      e.buf = Tensor();
+      e.rowptr.forget();
+      e.col.forget();
+    }
 }
 
 // ---- the forward's arguments, once ----------------------------------------------------------------------
@@ -304,9 +407,19 @@ std::tuple<Tensor, OptTensor> spmm_run(const Tensor &rowptr, const Tensor &col, 
                                    s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, cbuf, cbytes, copy_valid ? 1 : 0, stream),
                  "tsamd_spmm_cached");
   } else {
-    check_status(tsamd_spmm(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
-                            s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, stream),
-                 "tsamd_spmm");
+    // the plain product: with the pattern's hints where it keeps any (built at the first sighting, reused from then on)
+    const auto hints = pattern_hints_for(rowptr, col, s.dt, red, s.B, s.M, s.N, s.K, s.E, s.mat, stream);
+    if (hints.second != 0) {
+      const int st = tsamd_spmm_hinted(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
+                                       s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, hints.first.data_ptr(), hints.second,
+                                       stream);
+      if (st != TSAMD_OK && hints.second == 1) pattern_hints_drop(hints.first);
+      check_status(st, "tsamd_spmm_hinted");
+    } else {
+      check_status(tsamd_spmm(s.dt, red, s.rp(), s.cp(), ptr_or_null(s.value), s.mat.data_ptr(), s.out.data_ptr(),
+                              s.arg64(), s.B, s.M, s.N, s.K, s.E, w, wb, stream),
+                   "tsamd_spmm");
+    }
   }
   return std::make_tuple(s.out, s.arg_out);
 }
@@ -906,6 +1019,7 @@ static auto registry_spmm = torch::RegisterOperators()
                            .op("tsamd::operand_cache", &operand_cache_ctl)
                            .op("tsamd::pattern_cache", &pattern_cache_ctl)
                            .op("tsamd::pattern_cache_stats", &pattern_cache_stats)
+                           .op("tsamd::pattern_hints", &pattern_hints_ctl)
                            .op("tsamd::relabel_ids", &relabel_ids)
                            .op("tsamd::gather_rows", &gather_rows)
                            .op("tsamd::spmm_relabelled", &spmm_relabelled);

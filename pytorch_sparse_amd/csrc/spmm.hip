@@ -210,6 +210,41 @@ extern "C" int tsamd_spmm_cached(int dtype, int reduce, const int64_t *rowptr, c
   return spmm_run(c);
 }
 
+// ---------------------------------------------------------------------------
+// pattern hints: see include/tsamd.h and spmm_kernels.h, section 1c
+// ---------------------------------------------------------------------------
+extern "C" size_t tsamd_spmm_hints_bytes(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E) {
+  HintsLayout hl;
+  return hints_layout(dtype, reduce, B, M, N, K, E, &hl) ? hl.bytes : 0;
+}
+
+extern "C" int tsamd_spmm_hints_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
+                                       int64_t *layout) {
+  HintsLayout hl;
+  if (!layout || !hints_layout(dtype, reduce, B, M, N, K, E, &hl)) return 0;
+  layout[0] = (int64_t)hl.flags;
+  layout[1] = (int64_t)hl.order_hdr;
+  layout[2] = (int64_t)hl.blk_total;
+  layout[3] = (int64_t)hl.blk_word;
+  layout[4] = (int64_t)hl.blk_list;
+  layout[5] = (int64_t)hl.order;
+  layout[6] = hl.P;
+  layout[7] = (int64_t)hl.bytes;
+  return 1;
+}
+
+extern "C" int tsamd_spmm_hinted(int dtype, int reduce, const int64_t *rowptr, const int64_t *col, const void *value,
+                                 const void *mat, void *out, int64_t *arg_out, int64_t B, int64_t M, int64_t N,
+                                 int64_t K, int64_t E, void *workspace, size_t workspace_bytes_given, void *hints,
+                                 int state, void *stream_) {
+  if (!hints || (state != 1 && state != 2)) return TSAMD_ERR_INVALID;
+  SpmmCall c{dtype, reduce, rowptr, col, value, mat, out, arg_out, B, M, N, K, E, workspace,
+             workspace_bytes_given, reinterpret_cast<hipStream_t>(stream_)};
+  c.hints = hints;
+  c.hints_state = state;
+  return spmm_run(c);
+}
+
 // min / max with the winners as 32-bit entry ids (include/tsamd.h); cache == nullptr: stateless
 extern "C" int tsamd_spmm_minmax_arg32(int dtype, int reduce, const int64_t *rowptr, const int64_t *col,
                                        const void *value, const void *mat, void *out, int32_t *arg_out32, int64_t B,

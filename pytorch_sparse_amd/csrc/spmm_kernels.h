@@ -178,6 +178,8 @@ struct SpmmCall {
   const int64_t *deg_rowptr = nullptr;
   bool arg32 = false;           // tsamd_spmm_minmax_arg32
   uint32_t *rec_out = nullptr;  // tsamd_spmm_minmax_records
+  void *hints = nullptr;        // tsamd_spmm_hinted: the pattern's hints buffer (section 1c) ...
+  int hints_state = 0;          // ... 1 build it, 2 reuse it
 };
 
 namespace {
@@ -564,8 +566,9 @@ __device__ __forceinline__ uint32_t order_bucket(uint32_t key, uint32_t shift) {
   return b < (uint32_t)kOrderBuckets ? b : (uint32_t)kOrderBuckets - 1u;
 }
 
+// `classify` = 0: the table only (a call that reuses pattern hints, section 1c: its order is already built).
 __global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, const int64_t *__restrict__ col, int64_t M,
-                                      int64_t E, Workspace ws) {
+                                      int64_t E, Workspace ws, int classify) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p > ws.P) return;
   int64_t d = p * ws.items;
@@ -588,7 +591,7 @@ __global__ void spmm_partition_kernel(const int64_t *__restrict__ rowptr, const 
   ws.table[p] = Coord{lo, e};
   // column order: classify the partition while both coordinates are at hand.  The next boundary lies in the same row
   // exactly when the search at the next diagonal would stop at `lo` again, which is one comparison.
-  if (ws.order == nullptr || p >= ws.P) return;
+  if (ws.order == nullptr || classify == 0 || p >= ws.P) return;
   uint32_t key = kOrderPad;
   if (lo < M && e > rowptr[lo]) {
     int64_t d1 = d + ws.items;
@@ -2062,6 +2065,56 @@ size_t order_clear_bytes(int64_t P) {
   return sizeof(uint32_t) * (size_t)(kOrderHdrWords + 2 * kOrderBuckets + ceil_div(P, (int64_t)1 << kOrderChunkLg));
 }
 
+// hot blocks: the shapes whose calls take that route (carve; a call also needs full-width packets: launch_spmm)
+bool hot_block_shape(int dtype, int reduce, int64_t B, int64_t N, int64_t K, int64_t E) {
+  const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
+  return relabel_possible(dtype, reduce, N, K, E) && !minmax && B == 1 && N >= kHotBlockMinN && N < ((int64_t)1 << 31);
+}
+
+// ---------------------------------------------------------------------------
+// 1c. pattern hints.  Of the prologue, only the table (results depend on it) and the copy of the hot blocks (it reads X)
+//    depend on anything but (rowptr, col).  The rest -- the probe's verdict, which blocks are hot and their ranks, the
+//    slot -> partition map -- is the same in every call with one pattern, and it is ADVISORY: it moves addresses and the
+//    order of execution, never a value (sections 0b and 1b).  tsamd_spmm_hinted keeps it in a small caller-owned buffer:
+//      state 1 (build)   tsamd_spmm's kernels, writing those arrays into the buffer instead of the workspace;
+//      state 2 (reuse)   partition kernel (table only), hot-block copy, merge, fix-up.  No probe, mark, bits, scatter or
+//                        rank kernel and no memset.
+//    Any buffer that a build call of the same SIZES filled is safe, whatever (rowptr, col) held then or hold now: the
+//    block words cover N ids and name blocks the copy kernel fills from the lists it was built with, the map is a
+//    permutation of [0, P).  A stale buffer is at worst a slower call.  A build call that does not take one of the two
+//    routes (packet width, column-order switch, verification mode) leaves the verdict "no" for it.
+//    Scope: the shapes of the hot-block route.  Layout, 256-byte aligned parts:
+//      flags [4] int | order_hdr [kOrderHdrWords] | blk_total [kHotChunks] | blk_word [words] | blk_list [words] | order [P]
+// ---------------------------------------------------------------------------
+struct HintsLayout {
+  size_t flags, order_hdr, blk_total, blk_word, blk_list, order, bytes;
+  int64_t P;
+};
+[[maybe_unused]] bool hints_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, HintsLayout *h) {
+  if (dtype_size(dtype) == 0 || B < 0 || M <= 0 || N < 0 || K <= 0 || E < 0) return false;
+  if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return false;  // kHotable
+  if (reduce < TSAMD_SUM || reduce > TSAMD_MAX || !hot_block_shape(dtype, reduce, B, N, K, E)) return false;
+  int64_t P, items;
+  plan_partition(M, E, K * (int64_t)dtype_size(dtype), &P, &items);
+  if (P < 2 || P >= ((int64_t)1 << 31)) return false;
+  const size_t words = (size_t)ceil_div(N, (int64_t)64);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += align_up(bytes, 256);
+    return at;
+  };
+  h->P = P;
+  h->flags = take(4 * sizeof(int));
+  h->order_hdr = take(sizeof(uint32_t) * kOrderHdrWords);
+  h->blk_total = take(sizeof(uint32_t) * kHotChunks);
+  h->blk_word = take(sizeof(uint32_t) * words);
+  h->blk_list = take(sizeof(uint32_t) * words);
+  h->order = take(sizeof(uint32_t) * (size_t)P);
+  h->bytes = off;
+  return true;
+}
+
 size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K,
              int64_t E, Workspace *ws, bool relabelled = false, bool masked = false) {
   int64_t P, items;
@@ -2090,7 +2143,7 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   // whole number of rows from `mat`
   const bool hot_scope = !relabelled && relabel_possible(dtype, reduce, N, K, E) && !minmax && B == 1 && N < ((int64_t)1 << 31);
   // hot blocks: the same scope from N = kHotBlockMinN on; 64 more rows, for a table of every block whose last one is partial
-  const bool blk_scope = hot_scope && N >= kHotBlockMinN;
+  const bool blk_scope = !relabelled && hot_block_shape(dtype, reduce, B, N, K, E);
   w.xperm = (!relabelled && relabel_possible(dtype, reduce, N, K, E))
                 ? take(dtype_size(dtype) * (size_t)B * N * K + (hot_scope ? dtype_size(dtype) * (size_t)K * (blk_scope ? 65 : 1) : 0))
                 : nullptr;
@@ -2238,6 +2291,9 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   const uint32_t ktiles = lay.ktiles;
   const int lgG = lay.lgG;
   const unsigned int threads = kWavesPerBlock * kWave;
+  int hints_state = c.hints != nullptr ? c.hints_state : 0;  // 0 none (or not for this call), 1 build, 2 reuse
+  HintsLayout hl{};
+  char *hb = nullptr;
 
   // hot rows: floating-point sums with full-width packets (the shapes relabel_possible admits have no others)
   constexpr bool kHotable = !kPartial && RED == RED_ADD && VEC == kMaxVec<T> &&
@@ -2262,8 +2318,25 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
                              &ws.hot_side_row);  // (the block table ends at most 64 rows further from `mat`)
     }
     if (!hot) ws.hot_flag = nullptr;
+    // pattern hints (section 1c): the probe's words, the block words, lists and totals live in the caller's buffer.  A
+    // call that does not take the hot-block route runs as tsamd_spmm; a build then leaves both verdicts "no".
+    if (hints_state != 0) {
+      if (!hints_layout(c.dtype, c.reduce, B, M, N, K, E, &hl)) return TSAMD_ERR_UNSUPPORTED;  // (spmm_entry checked)
+      hb = reinterpret_cast<char *>(c.hints);
+      if (hot && ws.blk_word != nullptr) {
+        ws.relabel_flag = reinterpret_cast<int *>(hb + hl.flags);
+        ws.blk_total = reinterpret_cast<uint32_t *>(hb + hl.blk_total);
+        ws.blk_word = reinterpret_cast<uint32_t *>(hb + hl.blk_word);
+        ws.blk_list = reinterpret_cast<uint32_t *>(hb + hl.blk_list);
+      } else {
+        if (hints_state == 1) TSAMD_HIP_TRY(hipMemsetAsync(hb + hl.flags, 0, hl.blk_total - hl.flags, stream));
+        hints_state = 0;
+      }
+    }
+    const bool reuse = hints_state == 2;
     const bool cached = ws.cache_state != 0 && mode != 0;
-    if (mode == 2 && !(cached && ws.cache_state == 2)) {  // (a reused cache keeps the verdict of its first call)
+    // (a reused cache keeps the verdict of its first call, and so do reused hints)
+    if (mode == 2 && !(cached && ws.cache_state == 2) && !reuse) {
       TSAMD_HIP_TRY(hipMemsetAsync(ws.relabel_flag, 0, 4 * sizeof(int), stream));
       hipLaunchKernelGGL(spmm_probe_kernel, dim3(kProbeBlocks), dim3(256), 0, stream, col, E,
                          ws.relabel_flag);
@@ -2274,13 +2347,17 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
       const uint32_t pslots = (uint32_t)(K * sizeof(T) / 16);
       int lgL = 0;
       while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
-      TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
-      hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
-      TSAMD_LAUNCH_CHECK();
+      if (!reuse) {
+        TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
+        hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
+        TSAMD_LAUNCH_CHECK();
+      }
       if (ws.blk_word != nullptr) {  // hot blocks: select and compact, then copy; no scan launches
         const int lgS = ilog2_ceil(pslots);  // (exact: the rows that relabel_possible admits are powers of two)
-        hipLaunchKernelGGL(spmm_hot_block_bits_kernel, dim3(kHotChunks), dim3(256), 0, stream, N, ws);
-        TSAMD_LAUNCH_CHECK();
+        if (!reuse) {  // (reused hints hold the words, the lists and the totals: the copy is all that reads X)
+          hipLaunchKernelGGL(spmm_hot_block_bits_kernel, dim3(kHotChunks), dim3(256), 0, stream, N, ws);
+          TSAMD_LAUNCH_CHECK();
+        }
         hipLaunchKernelGGL(spmm_hot_block_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, kHotBlocks)), dim3(256), 0,
                            stream, reinterpret_cast<const void *>(mat), N, lgS, ws);
         TSAMD_LAUNCH_CHECK();
@@ -2322,16 +2399,25 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   }
   // column order (section 1b): the partition kernel classifies, two more launches build the slot -> partition map
   const int order_mode = !kPartial && RED == RED_ADD ? order_mode_of(ws, c.dtype, c.reduce, N, K, E, lgG) : 0;
+  const bool reuse_order = hints_state == 2 && order_mode != 0;
   if (order_mode == 0) {
     ws.order = nullptr;
+    // (hints built with the order switched off say "not in force" to a later call that has it on)
+    if (hints_state == 1) TSAMD_HIP_TRY(hipMemsetAsync(hb + hl.order_hdr, 0, sizeof(uint32_t) * kOrderHdrWords, stream));
   } else {
     ws.order_mode = order_mode;
-    TSAMD_HIP_TRY(hipMemsetAsync(ws.order_hdr, 0, order_clear_bytes(ws.P), stream));
+    // the counters stay in the workspace and are cleared there; with hints, only the header and the map move: the
+    // scatter kernel writes the header's three words in every call that builds
+    if (!reuse_order) TSAMD_HIP_TRY(hipMemsetAsync(ws.order_hdr, 0, order_clear_bytes(ws.P), stream));
+    if (hints_state != 0) {
+      ws.order_hdr = reinterpret_cast<uint32_t *>(hb + hl.order_hdr);
+      ws.order = reinterpret_cast<uint32_t *>(hb + hl.order);
+    }
   }
   hipLaunchKernelGGL(spmm_partition_kernel, dim3((unsigned int)ceil_div(ws.P + 1, 256)), dim3(256),
-                     0, stream, rowptr, col, M, E, ws);
+                     0, stream, rowptr, col, M, E, ws, reuse_order ? 0 : 1);
   TSAMD_LAUNCH_CHECK();
-  if (order_mode != 0) {
+  if (order_mode != 0 && !reuse_order) {
     hipLaunchKernelGGL(spmm_order_scatter_kernel, dim3((unsigned int)ceil_div(ws.P, (int64_t)1024)), dim3(1024), 0, stream,
                        ws);
     TSAMD_LAUNCH_CHECK();
@@ -2445,10 +2531,21 @@ int spmm_entry(const SpmmCall &c, Launch launch) {
   if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31 || B >= 65536) return TSAMD_ERR_UNSUPPORTED;
   if (B * ceil_div(K, 64) >= 65536) return TSAMD_ERR_UNSUPPORTED;  // gridDim.y = B * feature tiles
   const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
+  // pattern hints (tsamd_spmm_hinted): the plain product of a shape in their scope, nothing else
+  HintsLayout hl{};
+  if (c.hints_state != 0) {
+    if (c.hints == nullptr || (c.hints_state != 1 && c.hints_state != 2) || ((uintptr_t)c.hints % 256) != 0) return TSAMD_ERR_INVALID;
+    if (c.relabelled || c.perm != nullptr || c.wmask != nullptr || c.cache != nullptr || c.partial || c.arg32 ||
+        !hints_layout(dtype, reduce, B, M, N, K, E, &hl))
+      return TSAMD_ERR_UNSUPPORTED;
+  }
   if (B * M * K == 0) return TSAMD_OK;  // nothing to write
   if (!c.rowptr || !c.out || (E > 0 && (!c.col || !c.mat)) || (minmax && !c.arg_out))
     return TSAMD_ERR_INVALID;
   // verification mode (tsamd_spmm_reference_order): the plain product in the reference's order of operations
+  // (hints: it builds none -- both verdicts "no" -- and reads none)
+  if (spmm_reference_order_on() && c.hints_state == 1)
+    TSAMD_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(c.hints) + hl.flags, 0, hl.blk_total - hl.flags, c.stream));
   if (spmm_reference_order_on() && !c.relabelled && c.perm == nullptr && c.wmask == nullptr && !c.partial)
     return spmm_reference_order_run(dtype, reduce, c.rowptr, c.col, c.value, c.mat, c.out, c.arg_out, c.arg32, B, M, N, K, E,
                                     c.stream);
