@@ -110,9 +110,11 @@ int tsamd_spmm_hot_blocks_layout(int dtype, int reduce, int64_t B, int64_t M, in
 int tsamd_spmm_hot_block_min(void);
 
 /* tsamd_spmm_route (inspection and tests): what tsamd_spmm -- with arg32 != 0: tsamd_spmm_minmax_arg32 -- decides for
- * these operands before it launches anything.  Host arithmetic only -- no HIP call, no device -- through the very
- * functions the driver plans with.  Pointers count for their alignment and for the offsets only; mat / out / arg_out ==
- * NULL mean "aligned", workspace == NULL leaves the four offsets 0.
+ * these operands before it launches anything.  Host arithmetic only -- no HIP call, no device: the driver plans every
+ * call as one piece of data (plan_spmm, csrc/spmm_kernels.h) and then launches what that plan names; this entry, the two
+ * layouts above and tsamd_spmm_order_layout make the same plan and copy words out of it.  Pointers count for their
+ * alignment and for the offsets only; mat / out / arg_out == NULL mean "aligned", workspace == NULL leaves the four
+ * offsets 0.
  *   route[0] family   merge instantiation: 0 nothing is launched (B * M * K == 0), 1 short rows side by side (lgG >= 3),
  *                     2 cooperative, 3 cooperative over the hot-row table, 4 over the hot-block table, 5 / 6 = 1 / 2 with
  *                     int32 winner ids, 7 the reference-order mode (tsamd_spmm_reference_order; nothing else is filled)
@@ -480,8 +482,10 @@ int tsamd_spmm_minmax_bw_csc_records(int dtype, const int64_t *rowptr, const int
  *   route[14] items, route[15] P, route[16] fixup, route[17] relabel, route[18] copy, route[19] vec, route[20] lpr,
  *   route[21] lgG, route[22] ktiles, route[24] family   pull only: the words of tsamd_spmm_route for the masked sum --
  *                     the SUM of the transposed problem (N rows, M columns, `grad_out` gathered, `grad_mat` written)
- *                     with relabel 1 in place of 2: no probe of the ids, the copy of grad_out wherever it is possible
- *   route[23]         pull only: the entry's workspace bytes; the other words are 0.
+ *                     with relabel 1 in place of 2: no probe of the ids, the copy of grad_out wherever it is possible.
+ *                     family is what is launched: 2 (cooperative) at every lgG, also where the plain sum would say 1
+ *                     (lgG >= 3) -- the masked kernel has no side-by-side form
+ *   route[23]       pull only: the entry's workspace bytes; the other words are 0.
  * TSAMD_ERR_INVALID for route == NULL or winners outside 0 .. 3, TSAMD_OK otherwise. */
 int tsamd_spmm_minmax_bw_route(int winners, int dtype, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                                int want_value, int want_mat, const void *mat, const void *grad_out, const void *grad_mat,

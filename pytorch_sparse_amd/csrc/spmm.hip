@@ -9,11 +9,22 @@ using namespace tsamd;
 
 // sum / mean are instantiated here, min / max in spmm_min.hip / spmm_max.hip
 static int spmm_run(const SpmmCall &c) {
-  return spmm_entry(c, [&](int vec, const Workspace &ws) -> int {
-    if (c.reduce == TSAMD_MIN) return spmm_launch_min(vec, c, ws);
-    if (c.reduce == TSAMD_MAX) return spmm_launch_max(vec, c, ws);
-    return TSAMD_DISPATCH_DTYPE_ALL(c.dtype, [&]() -> int { return dispatch_spmm<scalar_t, RED_ADD>(vec, c, ws); });
+  return spmm_entry(c, [&](const SpmmPlan &p) -> int {
+    if (c.reduce == TSAMD_MIN) return spmm_launch_min(c, p);
+    if (c.reduce == TSAMD_MAX) return spmm_launch_max(c, p);
+    return TSAMD_DISPATCH_DTYPE_ALL(c.dtype, [&]() -> int { return dispatch_spmm<scalar_t, RED_ADD>(c, p); });
   });
+}
+
+// The inspection entries (include/tsamd.h) plan the call they are asked about as the driver does and copy words out:
+// plan_spmm's query mode.  `masked`: the call is spmm_masked_sum's (the pull of the min / max backward).
+static SpmmPlan query_plan(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, const void *mat,
+                           const void *out, const void *arg_out, bool arg32, void *workspace, bool masked) {
+  SpmmCall c{dtype, reduce, nullptr, nullptr, nullptr, mat, const_cast<void *>(out),
+             reinterpret_cast<int64_t *>(const_cast<void *>(arg_out)), B, M, N, K, E, workspace, 0, nullptr};
+  c.arg32 = arg32;
+  if (masked) c.wmask = reinterpret_cast<const uint32_t *>(&c);  // present; never dereferenced
+  return plan_spmm(c, true);
 }
 
 extern "C" size_t tsamd_spmm_workspace_bytes(int dtype, int reduce, int64_t B, int64_t M,
@@ -30,27 +41,18 @@ extern "C" int tsamd_spmm(int dtype, int reduce, const int64_t *rowptr, const in
                            workspace_bytes_given, reinterpret_cast<hipStream_t>(stream_)});
 }
 
-// hot rows / hot blocks (include/tsamd.h): the host-side half of launch_spmm's decision, for callers that look into the
-// workspace.  `blocks` says which of the two routes is asked about; a call takes at most one of them.
+// hot rows / hot blocks (include/tsamd.h), for callers that look into the workspace.  `blocks` says which of the two
+// routes is asked about; a call takes at most one of them.
 static int hot_layout(bool blocks, int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                       const void *mat, const void *out, void *workspace, int64_t *layout) {
-  if (!layout || !workspace || !mat || dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return 0;
-  if (spmm_reference_order_on() || (uintptr_t)workspace % 256 != 0) return 0;
-  Workspace ws;
-  carve(workspace, dtype, reduce, B, M, N, K, E, &ws);
-  if ((ws.blk_word != nullptr) != blocks) return 0;
-  const size_t es = dtype_size(dtype);
-  const size_t packet = (es <= 2 ? 4 : 16 / es) * es;  // full-width packets (spmm_entry)
-  if ((K * es) % packet != 0 || (uintptr_t)mat % packet != 0 || (uintptr_t)out % packet != 0) return 0;
-  void *side = nullptr;
-  int32_t side_row = 0;
-  if (!hot_rows_place(ws, mat, blocks ? N + 64 : N, (uint64_t)K * es, &side, &side_row)) return 0;
+  if (!layout || !workspace || !mat) return 0;
+  const SpmmPlan p = query_plan(dtype, reduce, B, M, N, K, E, mat, out, nullptr, false, workspace, false);
+  if (p.status != TSAMD_OK || p.what != SpmmPlan::Run || p.copy != (blocks ? 3 : 2)) return 0;
   const char *base = reinterpret_cast<const char *>(workspace);
-  layout[0] = reinterpret_cast<const char *>(ws.hot_flag) - base;
-  layout[1] = reinterpret_cast<const char *>(blocks ? ws.blk_word : ws.hot_word) - base;
-  layout[2] = reinterpret_cast<const char *>(side) - base;
-  layout[3] = side_row;
+  layout[0] = reinterpret_cast<const char *>(p.ws.hot_flag) - base;
+  layout[1] = reinterpret_cast<const char *>(blocks ? p.ws.blk_word : p.ws.hot_word) - base;
+  layout[2] = reinterpret_cast<const char *>(p.ws.hot_side) - base;
+  layout[3] = p.ws.hot_side_row;
   return 1;
 }
 
@@ -81,97 +83,57 @@ extern "C" int tsamd_spmm_column_order(int set) {
 
 extern "C" int tsamd_spmm_order_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E,
                                        const void *mat, const void *out, void *workspace, int64_t *layout) {
-  if (!layout || !workspace || dtype_size(dtype) == 0 || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return 0;
-  if (reduce != TSAMD_SUM && reduce != TSAMD_MEAN) return 0;
-  if (B * M * K == 0 || spmm_reference_order_on() || (uintptr_t)workspace % 256 != 0) return 0;
-  Workspace ws;
-  carve(workspace, dtype, reduce, B, M, N, K, E, &ws);
-  const int mode = order_mode_of(ws, dtype, reduce, N, K, E, lane_layout(K, packet_width(dtype, false, false, K, mat, out, nullptr)).lgG);
-  if (mode == 0) return 0;
+  if (!layout || !workspace) return 0;
+  const SpmmPlan p = query_plan(dtype, reduce, B, M, N, K, E, mat, out, nullptr, false, workspace, false);
+  if (p.status != TSAMD_OK || p.what != SpmmPlan::Run || p.order_mode == 0) return 0;
   const char *base = reinterpret_cast<const char *>(workspace);
-  layout[0] = reinterpret_cast<const char *>(ws.order_hdr) - base;
-  layout[1] = reinterpret_cast<const char *>(ws.order) - base;
-  layout[2] = ws.P;
-  layout[3] = reinterpret_cast<const char *>(ws.order_cls) - base;
-  layout[4] = ws.order_shift;
+  layout[0] = reinterpret_cast<const char *>(p.ws.order_hdr) - base;
+  layout[1] = reinterpret_cast<const char *>(p.ws.order) - base;
+  layout[2] = p.ws.P;
+  layout[3] = reinterpret_cast<const char *>(p.ws.order_cls) - base;
+  layout[4] = p.ws.order_shift;
   layout[5] = kOrderMinSingles;
   layout[6] = kOrderBucketMax;
   layout[7] = 0;
-  return mode;
+  return p.order_mode;
 }
 
-// min / max with int32 ids: which record-writing instantiation tsamd_spmm_minmax_records takes for these operands
-// (0 = none: the records come from the ids)
-static bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64_t E, const void *mat, const void *out);
-
-// What a forward call decides before it launches (include/tsamd.h): spmm_entry's checks in their order, then the
-// planning functions of spmm_kernels.h and the instantiation chain of launch_spmm restated on the host.
-// `masked`: the call is spmm_masked_sum's (the pull of the min / max backward) -- no reference-order mode, no probe of
-// `col` (launch_spmm turns relabel mode 2 into 1 there) and hence no hot table.
+// The words of tsamd_spmm_route (include/tsamd.h) out of the call's plan.  Family: the merge instantiation, by the name of
+// its shape -- the masked sum's is cooperative at every width, the record writers' are arg32_cooperative.
 int tsamd::spmm_route_words(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, const void *mat,
                             const void *out, const void *arg_out, int arg32, void *workspace, bool masked,
                             int64_t route[24]) {
-  if (!route || B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
+  const SpmmPlan p = query_plan(dtype, reduce, B, M, N, K, E, mat, out, arg_out, arg32 != 0, workspace, masked);
+  if (!route || p.status == TSAMD_ERR_INVALID) return TSAMD_ERR_INVALID;  // (a query's only INVALID: a negative size)
   for (int i = 0; i < 24; ++i) route[i] = 0;
-  if (reduce < TSAMD_SUM || reduce > TSAMD_MAX) return TSAMD_ERR_UNSUPPORTED;
-  if (dtype_size(dtype) == 0) return TSAMD_ERR_UNSUPPORTED;
-  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31 || B >= 65536) return TSAMD_ERR_UNSUPPORTED;
-  if (B * ceil_div(K, 64) >= 65536) return TSAMD_ERR_UNSUPPORTED;
-  const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
-  const bool floating = dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
-  if (arg32 && !minmax) return TSAMD_ERR_UNSUPPORTED;  // (tsamd_spmm_minmax_arg32)
-  if (B * M * K == 0) return TSAMD_OK;                 // family 0: nothing is launched
-  if (spmm_reference_order_on() && !masked) {
+  if (p.status != TSAMD_OK || p.what == SpmmPlan::Nothing) return p.status;  // family 0: nothing is launched
+  if (p.what == SpmmPlan::ReferenceOrder) {
     route[0] = 7;
     return TSAMD_OK;
   }
-  if ((uintptr_t)workspace % 256 != 0) return TSAMD_ERR_WORKSPACE;
-  if (arg32 && (E >= (int64_t)1 << 31 || !floating)) return TSAMD_ERR_UNSUPPORTED;
-  // pointers count for their alignment and their distances only; without a workspace the layout is that of one that
-  // starts at the first 256-byte boundary behind `mat`
-  char *base = reinterpret_cast<char *>(workspace);
-  if (!base) base = reinterpret_cast<char *>(align_up((size_t)(uintptr_t)mat + 1, 4096));
-  if (!mat) mat = base;
-  Workspace ws;
-  route[18] = (int64_t)carve(base, dtype, reduce, B, M, N, K, E, &ws, false, masked);
-  const int vec = packet_width(dtype, minmax, arg32 != 0, K, mat, out, arg_out);
-  const LaneLayout lay = lane_layout(K, vec);
-  const size_t es = dtype_size(dtype);
-  const int max_vec = es <= 2 ? 4 : (int)(16 / es);
-  int mode = ws.xperm != nullptr && vec > 1 ? 2 : 0;
-  if (mode == 2 && masked) mode = 1;
-  int copy = mode != 0 ? 1 : 0;
-  if (mode == 2 && floating && !minmax && vec == max_vec && lay.lgG < 3) {  // kHotable, and launch_spmm's condition
-    void *side = nullptr;
-    int32_t side_row = 0;
-    if (hot_rows_place(ws, mat, ws.blk_word != nullptr ? N + 64 : N, (uint64_t)K * es, &side, &side_row))
-      copy = ws.blk_word != nullptr ? 3 : 2;
-  }
-  int family;
-  if (arg32) family = lay.lgG >= 3 ? 5 : 6;
-  else if (lay.lgG >= 3) family = 1;
-  else family = copy == 2 ? 3 : (copy == 3 ? 4 : 2);
-  route[0] = family;
-  route[1] = vec;
-  route[2] = lay.slots;
-  route[3] = lay.lpr;
-  route[4] = lay.lgG;
-  route[5] = lay.ktiles;
+  const Workspace &ws = p.ws;
+  route[0] = p.merge == kMergeMasked ? kMergeCoop : (p.merge > kMergeMasked ? kMergeArg32Coop : p.merge);
+  route[1] = p.vec;
+  route[2] = p.lay.slots;
+  route[3] = p.lay.lpr;
+  route[4] = p.lay.lgG;
+  route[5] = p.lay.ktiles;
   route[6] = ws.P;
   route[7] = ws.items;
-  route[8] = minmax ? snap_items(ws.items) : 0;
-  route[9] = mode;
-  route[10] = copy;
-  route[11] = ws.P > 1 ? 1 : 0;
+  route[8] = ws.snap;
+  route[9] = ws.relabel_mode;
+  route[10] = p.copy;
+  route[11] = p.fixup != kFixupNone ? 1 : 0;
   if (workspace) {
-    route[12] = reinterpret_cast<char *>(ws.table) - base;
-    route[13] = reinterpret_cast<char *>(ws.tail_row) - base;
-    route[14] = reinterpret_cast<char *>(ws.head_row) - base;
-    route[15] = reinterpret_cast<char *>(ws.relabel_flag) - base;
+    const char *base = reinterpret_cast<const char *>(workspace);
+    route[12] = reinterpret_cast<const char *>(ws.table) - base;
+    route[13] = reinterpret_cast<const char *>(ws.tail_row) - base;
+    route[14] = reinterpret_cast<const char *>(ws.head_row) - base;
+    route[15] = reinterpret_cast<const char *>(ws.relabel_flag) - base;
   }
-  if (arg32 && E > 0 && vec == 4 && spmm_emits_records(dtype, B, M, K, E, mat, out))
-    route[16] = ceil_div(K, 32) == 4 && win_record_stride(K) == 8u ? 1 : 2;
-  route[17] = B * (int64_t)lay.ktiles;
+  route[16] = p.merge == kMergeRecords1 ? 1 : (p.merge == kMergeRecords2 ? 2 : 0);
+  route[17] = B * (int64_t)p.lay.ktiles;
+  route[18] = (int64_t)p.need;
   return TSAMD_OK;
 }
 
@@ -264,16 +226,7 @@ extern "C" int tsamd_spmm_minmax_arg32(int dtype, int reduce, const int64_t *row
 // min / max whose forward leaves the winner RECORDS of the pull backward instead of the winner ids (include/tsamd.h).
 // The merge kernel writes the records of the rows it finishes by itself (Workspace::rec_out) when the row shape allows
 // it; the rows cut between partitions -- or every row, when it does not -- get theirs from the ids
-// (minmax_winrec_kernel, csrc/spmm_bw.hip), which only live in the workspace.
-static bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64_t E, const void *mat, const void *out) {
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return false;
-  if (K <= 32 || K > 256 || K % 4 != 0 || E >= (int64_t)1 << 31 || M >= (int64_t)1 << 32 || B < 1) return false;
-  if (dtype == TSAMD_F32 && K <= 64) return false;  // measured even (profiles/r06_ab_fwd_winrec.md): the ids stay
-  const size_t packet = 4 * dtype_size(dtype);  // the four-element packets the record writer's lane layout assumes
-  if (mat != nullptr && (((uintptr_t)mat % packet) != 0 || ((uintptr_t)out % packet) != 0)) return false;
-  return !spmm_reference_order_on();
-}
-
+// (minmax_winrec_kernel, csrc/spmm_bw.hip), which only live in the workspace.  spmm_emits_records (spmm_kernels.h) says which.
 static size_t records_arg_bytes(int64_t B, int64_t M, int64_t K) { return align_up(sizeof(int32_t) * (size_t)(B * M * K), 256); }
 
 extern "C" int tsamd_spmm_minmax_records_in_forward(int dtype, int64_t B, int64_t M, int64_t K, int64_t E) {

@@ -7,12 +7,12 @@
 
 namespace tsamd {
 
-// One SpMM call and its carved workspace (csrc/spmm_kernels.h), and the launchers of the min / max instantiations
-// (csrc/spmm_min.hip, csrc/spmm_max.hip) that the entry points of csrc/spmm.hip call.
+// One SpMM call and its host plan (csrc/spmm_kernels.h), and the launchers of the min / max instantiations
+// (csrc/spmm_min.hip, csrc/spmm_max.hip) that the entry points of csrc/spmm.hip run such a plan with.
 struct SpmmCall;
-struct Workspace;
-int spmm_launch_min(int vec, const SpmmCall &c, const Workspace &ws);
-int spmm_launch_max(int vec, const SpmmCall &c, const Workspace &ws);
+struct SpmmPlan;
+int spmm_launch_min(const SpmmCall &c, const SpmmPlan &p);
+int spmm_launch_max(const SpmmCall &c, const SpmmPlan &p);
 
 // Winner records of the pull-formulated min/max backward (csrc/spmm_bw.hip writes them, the masked
 // merge kernel of csrc/spmm_kernels.h and the masked SDDMM read them).  One record per (batch, CSR entry e),
@@ -30,7 +30,7 @@ static inline uint32_t win_record_stride(int64_t K) {
 }
 
 // Whether the masked sum reads word W + 3 of a record as the non-zero-word bitmap: the padding must leave that word, and
-// the bitmap has 32 bits (wider masks are read whole).  spmm_entry and tsamd_spmm_minmax_bw_route both ask here.
+// the bitmap has 32 bits (wider masks are read whole).  plan_spmm and tsamd_spmm_minmax_bw_route both ask here.
 static inline int win_record_masked_has_z(uint32_t W) { return (W <= 32u && ((W + 3u) & 3u) != 0u) ? 1 : 0; }
 
 // The words of tsamd_spmm_route (include/tsamd.h); `masked`: as spmm_masked_sum runs the product (csrc/spmm.hip).

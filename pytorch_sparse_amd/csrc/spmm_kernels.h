@@ -38,10 +38,14 @@
 //
 // This header is the whole forward: four translation units include it and instantiate one part each, so that its ~200
 // merge-kernel instantiations compile side by side (176 s in one unit):
-//   spmm.hip          every entry point but tsamd_spmm_partial*; the sum / mean instantiations and the masked sum
-//   spmm_min.hip      the min instantiations, reached through tsamd::spmm_launch_min (spmm_internal.h)
-//   spmm_max.hip      the max instantiations, reached through tsamd::spmm_launch_max
+//   spmm.hip          every entry point but tsamd_spmm_partial*, the inspection entries; the sum / mean instantiations and
+//                     the masked sum
+//   spmm_min.hip      the min instantiations: tsamd::spmm_launch_min (spmm_internal.h) runs a plan with them
+//   spmm_max.hip      the max instantiations: tsamd::spmm_launch_max
 //   spmm_partial.hip  tsamd_spmm_partial*: all three families with the partial-product row sink, floating point only
+// Every entry point is plan, then run (spmm_entry): plan_spmm -- host arithmetic, no HIP call -- checks the arguments,
+// carves the workspace and writes down every decision as an SpmmPlan; run_spmm<T, VEC, RED> of the unit that owns the
+// family launches what the plan names.  The inspection entries of spmm.hip make the same plan and copy words out of it.
 // The including unit defines TSAMD_SPMM_PARTIAL_BUILD first: 1 in spmm_partial.hip, 0 in the others -- their kernels
 // carry no trace of the partial-product mode (a run-time switch cost the north-star instantiation a wave per SIMD).
 #pragma once
@@ -180,6 +184,47 @@ struct SpmmCall {
   uint32_t *rec_out = nullptr;  // tsamd_spmm_minmax_records
   void *hints = nullptr;        // tsamd_spmm_hinted: the pattern's hints buffer (section 1c) ...
   int hints_state = 0;          // ... 1 build it, 2 reuse it
+};
+
+// How the 64 lanes of a wave share a row of K features in packets of `vec` elements: `slots` packets per row, groups of
+// `lpr` lanes (a power of two, 64 at most) -> 2^lgG rows side by side, `ktiles` feature tiles of 64 packets on gridDim.y.
+struct LaneLayout {
+  uint32_t slots, lpr;
+  int lgG;
+  uint32_t ktiles;
+};
+struct HintsLayout {  // byte offsets into a pattern's hints buffer (section 1c)
+  size_t flags, order_hdr, blk_total, blk_word, blk_list, order, bytes;
+  int64_t P;
+};
+
+// The host plan of one call: everything the forward decides before it launches, once, as data.  plan_spmm (below) fills it
+// and makes no HIP call; run_spmm issues the memsets, launches and events it names and decides nothing but enum ->
+// instantiation; the inspection entries of csrc/spmm.hip copy words out of the same plan.
+// (the first six merge values are the family words of tsamd_spmm_route)
+enum SpmmMerge { kMergeNone, kMergeShort, kMergeCoop, kMergeHotRows, kMergeHotBlocks, kMergeArg32Short, kMergeArg32Coop,
+                 kMergeMasked, kMergeRecords1, kMergeRecords2 };
+enum SpmmFixup { kFixupNone, kFixupPlain, kFixupArg32, kFixupRecords1, kFixupRecords2 };
+struct SpmmPlan {
+  int status = TSAMD_OK;
+  enum { Run, Nothing, ReferenceOrder } what = Run;  // Nothing: TSAMD_OK without a launch; ReferenceOrder: verification mode
+  size_t need = 0;                                   // workspace bytes
+  int vec = 1;
+  LaneLayout lay{};
+  Workspace ws{};  // as the kernels get it: every host-side rewrite is in
+  HintsLayout hl{};
+  bool probe = false;  // clear the sample counters and sample `col`
+  int copy = 0;        // 0 none, 1 full (relabelled), 2 hot rows, 3 hot blocks
+  int cached = 0;      // the full copy goes through the operand cache: 1 fill it, 2 reuse it while the fingerprint matches
+  int hints = 0;       // pattern hints in force: 0 none (or not for this call), 1 build, 2 reuse
+  // a build that takes no route leaves the verdict "no": 1 clear flags and order header (in front of the probe), 2 the order
+  // header alone (in front of the partition kernel: hints built with the order switched off say "not in force")
+  int hint_clear = 0;
+  int order_mode = 0;        // column order: 0 identity, 1 the device decides from the count of single-row partitions, 2 forced
+  bool reuse_order = false;  // the slot -> partition map comes from the hints: no clear, no scatter, no rank ...
+  int classify = 1;          // ... and the partition kernel writes the table only
+  SpmmMerge merge = kMergeNone;
+  SpmmFixup fixup = kFixupNone;
 };
 
 namespace {
@@ -1327,7 +1372,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, (kMinWavesPerEU<RED, SHORT, 
   auto hot_ids = [&](int64_t base) -> uint32_t {
     const int64_t e = base + lane;
     uint32_t c = 0;
-    if (e < e1) c = (uint32_t)col[e];  // (no entry permutation in this instantiation: launch_spmm)
+    if (e < e1) c = (uint32_t)col[e];  // (no entry permutation in this instantiation: plan_spmm)
     return c;
   };
   auto hot_weights = [&](int64_t base) -> A {
@@ -2065,7 +2110,7 @@ size_t order_clear_bytes(int64_t P) {
   return sizeof(uint32_t) * (size_t)(kOrderHdrWords + 2 * kOrderBuckets + ceil_div(P, (int64_t)1 << kOrderChunkLg));
 }
 
-// hot blocks: the shapes whose calls take that route (carve; a call also needs full-width packets: launch_spmm)
+// hot blocks: the shapes whose calls take that route (carve; a call also needs full-width packets: plan_spmm)
 bool hot_block_shape(int dtype, int reduce, int64_t B, int64_t N, int64_t K, int64_t E) {
   const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
   return relabel_possible(dtype, reduce, N, K, E) && !minmax && B == 1 && N >= kHotBlockMinN && N < ((int64_t)1 << 31);
@@ -2086,10 +2131,6 @@ bool hot_block_shape(int dtype, int reduce, int64_t B, int64_t N, int64_t K, int
 //    Scope: the shapes of the hot-block route.  Layout, 256-byte aligned parts:
 //      flags [4] int | order_hdr [kOrderHdrWords] | blk_total [kHotChunks] | blk_word [words] | blk_list [words] | order [P]
 // ---------------------------------------------------------------------------
-struct HintsLayout {
-  size_t flags, order_hdr, blk_total, blk_word, blk_list, order, bytes;
-  int64_t P;
-};
 [[maybe_unused]] bool hints_layout(int dtype, int reduce, int64_t B, int64_t M, int64_t N, int64_t K, int64_t E, HintsLayout *h) {
   if (dtype_size(dtype) == 0 || B < 0 || M <= 0 || N < 0 || K <= 0 || E < 0) return false;
   if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return false;  // kHotable
@@ -2160,7 +2201,7 @@ size_t carve(void *base, int dtype, int reduce, int64_t B, int64_t M, int64_t N,
   // spmm_masked_sum_workspace_bytes).  Behind everything else: no earlier offset moves.
   const bool order_scope = !relabelled && !masked && !minmax && K * (int64_t)dtype_size(dtype) >= 256 && N < ((int64_t)1 << 31) &&
                            P < ((int64_t)1 << 31);
-  // (header, bucket counts, cursors and chunk counts are one span: launch_spmm clears it with one memset)
+  // (header, bucket counts, cursors and chunk counts are one span: run_spmm clears it with one memset)
   w.order_hdr = order_scope ? reinterpret_cast<uint32_t *>(take(order_clear_bytes(P))) : nullptr;
   w.order_hist = order_scope ? w.order_hdr + kOrderHdrWords : nullptr;
   w.order_chunk = order_scope ? w.order_hist + 2 * kOrderBuckets : nullptr;
@@ -2227,31 +2268,11 @@ bool hot_rows_place(const Workspace &ws, const void *mat, int64_t N, uint64_t ro
   return true;
 }
 
-// column order: the host half of the decision -- 0 identity order, 1 the device decides from the count of single-row
-// partitions, 2 forced.  launch_spmm and tsamd_spmm_order_layout both ask here.  Auto is for the calls whose size makes
-// the relabelled copy possible: smaller ones would only pay the builder's launches.
-[[maybe_unused]] int order_mode_of(const Workspace &ws, int dtype, int reduce, int64_t N, int64_t K, int64_t E, int lgG) {
-  if (ws.order == nullptr || lgG >= 3 || ws.wmask != nullptr || ws.perm != nullptr || ws.out_relabel || ws.partial ||
-      ws.cache_state != 0 || ws.arg32 || ws.P < 2)
-    return 0;
-  const int sw = spmm_column_order_mode();
-  if (sw == 2) return 2;
-  return sw == 1 && relabel_possible(dtype, reduce, N, K, E) ? 1 : 0;
-}
-
 // `vec` = elements per lane packet, chosen by the caller: the largest power of two <= kMaxVec<T>
 // that divides K and matches the pointers' alignment.
 template <typename T>
 constexpr int kMaxVec = sizeof(T) <= 2 ? 4 : 16 / (int)sizeof(T);
 
-// How the 64 lanes of a wave share a row of K features in packets of `vec` elements: `slots` packets per row, groups of
-// `lpr` lanes (a power of two, 64 at most) -> 2^lgG rows side by side, `ktiles` feature tiles of 64 packets on gridDim.y.
-// launch_spmm and tsamd_spmm_route (csrc/spmm.hip) both take their numbers from here.
-struct LaneLayout {
-  uint32_t slots, lpr;
-  int lgG;
-  uint32_t ktiles;
-};
 LaneLayout lane_layout(int64_t K, int vec) {
   LaneLayout l;
   l.slots = (uint32_t)((K + vec - 1) / vec);  // feature packets per row
@@ -2263,9 +2284,8 @@ LaneLayout lane_layout(int64_t K, int vec) {
 
 // Elements per lane packet: the widest for the type (see dispatch_spmm), halved until it divides K and every pointer the
 // kernel moves packets through is aligned to it -- arg_out (min / max only) in packets of `vec` 8-byte ids, 4-byte with
-// arg32.  spmm_entry and tsamd_spmm_route both ask here.
-[[maybe_unused]] int packet_width(int dtype, bool minmax, bool arg32, int64_t K, const void *mat, const void *out,
-                                  const void *arg_out) {
+// arg32.
+int packet_width(int dtype, bool minmax, bool arg32, int64_t K, const void *mat, const void *out, const void *arg_out) {
   const size_t es = dtype_size(dtype);
   int vec = es <= 2 ? 4 : (int)(16 / es);
   while (vec > 1 && !((K % vec) == 0 && ((uintptr_t)mat % (vec * es)) == 0 && ((uintptr_t)out % (vec * es)) == 0 &&
@@ -2275,10 +2295,186 @@ LaneLayout lane_layout(int64_t K, int vec) {
 }
 
 // min / max and the record-writing forward: how far a partition boundary snaps back to a row start (spmm_partition_kernel)
-[[maybe_unused]] int64_t snap_items(int64_t items) { return TSAMD_RECORD_SNAP < items / 2 ? TSAMD_RECORD_SNAP : items / 2; }
+int64_t snap_items(int64_t items) { return TSAMD_RECORD_SNAP < items / 2 ? TSAMD_RECORD_SNAP : items / 2; }
 
+// min / max with int32 ids: whether the merge kernel writes the winner records of tsamd_spmm_minmax_records itself for
+// these operands (the single predicate of that window; mat == nullptr: the shape alone)
+[[maybe_unused]] bool spmm_emits_records(int dtype, int64_t B, int64_t M, int64_t K, int64_t E, const void *mat, const void *out) {
+  if (dtype != TSAMD_F32 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return false;
+  if (K <= 32 || K > 256 || K % 4 != 0 || E >= (int64_t)1 << 31 || M >= (int64_t)1 << 32 || B < 1) return false;
+  if (dtype == TSAMD_F32 && K <= 64) return false;  // measured even (profiles/r06_ab_fwd_winrec.md): the ids stay
+  const size_t packet = 4 * dtype_size(dtype);  // the four-element packets the record writer's lane layout assumes
+  if (mat != nullptr && (((uintptr_t)mat % packet) != 0 || ((uintptr_t)out % packet) != 0)) return false;
+  return !spmm_reference_order_on();
+}
+
+// The plan half (SpmmPlan, above).  No HIP call in here.  The checks, their order and their status codes are part of the
+// C-ABI.  `query` (the inspection entries): arrays the caller did not pass count as present, pointers count for their
+// alignment and their distances only, and without a workspace the layout is that of one that starts at the first
+// 4096-byte boundary behind `mat`.
+SpmmPlan plan_spmm(const SpmmCall &c, bool query) {
+  SpmmPlan p;
+  auto answer = [&p](int status) { return p.status = status, p; };
+  const int dtype = c.dtype, reduce = c.reduce;
+  const int64_t B = c.B, M = c.M, N = c.N, K = c.K, E = c.E;
+  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return answer(TSAMD_ERR_INVALID);
+  if (reduce < TSAMD_SUM || reduce > TSAMD_MAX) return answer(TSAMD_ERR_UNSUPPORTED);
+  if (dtype_size(dtype) == 0) return answer(TSAMD_ERR_UNSUPPORTED);
+  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31 || B >= 65536) return answer(TSAMD_ERR_UNSUPPORTED);
+  if (B * ceil_div(K, 64) >= 65536) return answer(TSAMD_ERR_UNSUPPORTED);  // gridDim.y = B * feature tiles
+  const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
+  const bool floating = dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
+  // pattern hints (tsamd_spmm_hinted): the plain product of a shape in their scope, nothing else
+  if (c.hints_state != 0) {
+    if (c.hints == nullptr || (c.hints_state != 1 && c.hints_state != 2) || ((uintptr_t)c.hints % 256) != 0)
+      return answer(TSAMD_ERR_INVALID);
+    if (c.relabelled || c.perm != nullptr || c.wmask != nullptr || c.cache != nullptr || c.partial || c.arg32 ||
+        !hints_layout(dtype, reduce, B, M, N, K, E, &p.hl))
+      return answer(TSAMD_ERR_UNSUPPORTED);
+  }
+  if (c.arg32 && !minmax) return answer(TSAMD_ERR_UNSUPPORTED);  // (what the entry points with int32 ids say first themselves)
+  if (B * M * K == 0) return p.what = SpmmPlan::Nothing, p;      // nothing to write
+  if (!query && (!c.rowptr || !c.out || (E > 0 && (!c.col || !c.mat)) || (minmax && !c.arg_out)))
+    return answer(TSAMD_ERR_INVALID);
+  // verification mode (tsamd_spmm_reference_order): the plain product in the reference's order of operations
+  // (hints: it builds none -- both verdicts "no" -- and reads none)
+  if (spmm_reference_order_on() && !c.relabelled && c.perm == nullptr && c.wmask == nullptr && !c.partial) {
+    p.hint_clear = c.hints_state == 1 ? 1 : 0;
+    return p.what = SpmmPlan::ReferenceOrder, p;
+  }
+  // operand cache: the relabelled copy and the probe verdict live in the caller's buffer, not in the workspace
+  const size_t cache_need = operand_cache_bytes(dtype, reduce, B, N, K, E);
+  const bool use_cache = c.cache != nullptr && !c.relabelled && cache_need > 0 && c.cache_bytes >= cache_need &&
+                         ((uintptr_t)c.cache % 256) == 0 && ((uintptr_t)c.mat % 16) == 0;
+  const bool no_xperm_in_ws = c.relabelled || use_cache || c.partial;
+  p.need = carve(nullptr, dtype, reduce, B, M, N, K, E, nullptr, no_xperm_in_ws, c.wmask != nullptr);
+  if (!query && (!c.workspace || c.workspace_bytes < p.need)) return answer(TSAMD_ERR_WORKSPACE);
+  if ((uintptr_t)c.workspace % 256 != 0) return answer(TSAMD_ERR_WORKSPACE);
+  char *base = reinterpret_cast<char *>(c.workspace);
+  if (!base) base = reinterpret_cast<char *>(align_up((size_t)(uintptr_t)c.mat + 1, 4096));
+  const void *mat = query && c.mat == nullptr ? base : c.mat;
+  Workspace &ws = p.ws;
+  carve(base, dtype, reduce, B, M, N, K, E, &ws, no_xperm_in_ws, c.wmask != nullptr);
+  p.vec = packet_width(dtype, minmax, c.arg32, K, mat, c.out, c.arg_out);
+  p.lay = lane_layout(K, p.vec);
+  const int lgG = p.lay.lgG;
+  if (use_cache) {
+    char *cb = reinterpret_cast<char *>(c.cache);
+    ws.relabel_flag = reinterpret_cast<int *>(cb);
+    ws.cache_fp = reinterpret_cast<unsigned long long *>(cb + 256);
+    ws.xperm = cb + kOperandCacheHeader;
+    ws.cache_state = c.cache_valid ? 2 : 1;
+  }
+  if (c.relabelled) {
+    if (M >= (int64_t)1 << 32) return answer(TSAMD_ERR_UNSUPPORTED);
+    ws.out_relabel = 1;
+  }
+  ws.perm = c.perm;
+  bool records = false;
+  if (c.arg32) {  // E itself ("no winner") must fit a non-negative int32; the instantiations are the floating types'
+    if (c.partial || E >= (int64_t)1 << 31 || !floating) return answer(TSAMD_ERR_UNSUPPORTED);
+    ws.arg32 = 1;
+    // (tsamd_spmm_minmax_records checked the shape before it passed rec_out; a query asks the same predicate)
+    records = c.rec_out != nullptr || (query && E > 0 && p.vec == 4 && spmm_emits_records(dtype, B, M, K, E, mat, c.out));
+    if (records) {  // four-element packets, 4-byte accumulators, 33..256 features
+      if (p.vec != 4 || acc_size(dtype) != 4 || lgG > 2 || p.lay.ktiles != 1) return answer(TSAMD_ERR_UNSUPPORTED);
+      ws.rec_out = c.rec_out;
+      ws.rec_value = c.value;
+      ws.rec_stride = win_record_stride(K);
+      ws.rec_meta = (uint32_t)ceil_div(K, 32);
+      ws.rec_has_z = ((ws.rec_meta + 3u) & 3u) != 0u ? 1 : 0;
+    }
+  }
+  // min / max: partition boundaries snap to row starts (spmm_partition_kernel) -- fewer cut rows, fewer carry records and
+  // fix-up waves: configs[2] forward 1.024-1.029 -> 1.000 ms (bf16), 1.57 -> 1.55 (fp32), same box
+  // (profiles/r06_ab_minmax_snap.jsonl).  The result does not depend on where a row is cut (no rounding in min / max);
+  // sums keep their partition: theirs does, in the last bits.
+  if (minmax) ws.snap = snap_items(ws.items);
+  if (c.partial) {
+    if (reduce == TSAMD_MEAN && c.deg_rowptr == nullptr) return answer(TSAMD_ERR_INVALID);
+    ws.partial = 1;
+    ws.accumulate = c.accumulate ? 1 : 0;
+    ws.arg_map = c.arg_map;
+    ws.arg_none = c.arg_none;
+    ws.deg_rowptr = reduce == TSAMD_MEAN ? c.deg_rowptr : nullptr;
+  }
+  if (c.wmask != nullptr) {  // 32-bit entry ids in the windows; sums of the floating types
+    if (E >= (int64_t)1 << 32 || reduce != TSAMD_SUM || !floating) return answer(TSAMD_ERR_UNSUPPORTED);
+    ws.wmask = c.wmask;
+    ws.rec_stride = win_record_stride(K);
+    ws.rec_meta = (uint32_t)ceil_div(K, 32);
+    ws.rec_has_z = win_record_masked_has_z(ws.rec_meta);  // a padding word behind (id, value)
+  }
+  // the copy of X.  Masked sums (the pull of the min / max backward): `col` points at winner records, not at column ids,
+  // so there is nothing to probe; same-box A/B at configs[2]: 1.76 ms with the copy, 1.93 without (the rows gathered are
+  // grad_out rows indexed by the R-MAT ROW ids of the forward, which camp like its column ids)
+  const int mode = ws.xperm == nullptr || p.vec == 1 || ws.out_relabel ? 0 : (ws.wmask != nullptr ? 1 : 2);
+  ws.relabel_mode = mode;
+  // hot rows instead of the full copy: floating-point sums with full-width packets (the shapes relabel_possible admits
+  // have no others); the side table starts in the copy's region, a whole number of rows from `mat`, and every index the
+  // merge kernel forms must fit a signed 32-bit row number (the block table ends at most 64 rows further from `mat`).
+  // (lgG < 3: the side-by-side short-row kernel knows nothing of the table; rows of >= 256 bytes in full-width packets
+  // never take it, this keeps the two decisions tied together)
+  const size_t es = dtype_size(dtype);
+  const bool hot = mode == 2 && !minmax && floating && p.vec == (es <= 2 ? 4 : (int)(16 / es)) && lgG < 3 && ws.cache_state == 0 &&
+                   ws.perm == nullptr &&
+                   hot_rows_place(ws, mat, ws.blk_word != nullptr ? N + 64 : N, (uint64_t)K * es, &ws.hot_side, &ws.hot_side_row);
+  if (!hot) ws.hot_flag = nullptr;
+  // pattern hints (section 1c): the probe's words, the block words, lists and totals live in the caller's buffer.  A
+  // call that does not take the hot-block route runs as tsamd_spmm; a build then leaves both verdicts "no".
+  char *hb = reinterpret_cast<char *>(c.hints);
+  if (c.hints_state != 0 && hot && ws.blk_word != nullptr) {
+    p.hints = c.hints_state;
+    ws.relabel_flag = reinterpret_cast<int *>(hb + p.hl.flags);
+    ws.blk_total = reinterpret_cast<uint32_t *>(hb + p.hl.blk_total);
+    ws.blk_word = reinterpret_cast<uint32_t *>(hb + p.hl.blk_word);
+    ws.blk_list = reinterpret_cast<uint32_t *>(hb + p.hl.blk_list);
+  } else if (c.hints_state == 1) {
+    p.hint_clear = 1;
+  }
+  p.copy = hot ? (ws.blk_word != nullptr ? 3 : 2) : (mode != 0 ? 1 : 0);
+  p.cached = p.copy == 1 ? ws.cache_state : 0;
+  if (p.cached == 2) {  // the copy kernel returns at once when the two fingerprints agree
+    ws.fp_stored = ws.cache_fp;
+    ws.fp_new = ws.cache_fp + kFingerprintWords;
+  }
+  // (a reused cache keeps the verdict of its first call, and so do reused hints)
+  p.probe = mode == 2 && p.cached != 2 && p.hints != 2;
+  // column order (section 1b).  Auto is for the calls whose size makes the relabelled copy possible: smaller ones would
+  // only pay the builder's launches.
+  const int sw = spmm_column_order_mode();
+  if (ws.order != nullptr && lgG < 3 && ws.wmask == nullptr && ws.perm == nullptr && !ws.out_relabel && !ws.partial &&
+      ws.cache_state == 0 && !ws.arg32 && ws.P >= 2)
+    p.order_mode = sw == 2 ? 2 : (sw == 1 && relabel_possible(dtype, reduce, N, K, E) ? 1 : 0);
+  if (p.order_mode == 0) {
+    ws.order = nullptr;
+    if (p.hints == 1) p.hint_clear = 2;
+  } else {
+    ws.order_mode = p.order_mode;
+    p.reuse_order = p.hints == 2;
+    // the counters stay in the workspace and are cleared there; with hints, only the header and the map move: the
+    // scatter kernel writes the header's three words in every call that builds
+    if (p.hints != 0) {
+      ws.order_hdr = reinterpret_cast<uint32_t *>(hb + p.hl.order_hdr);
+      ws.order = reinterpret_cast<uint32_t *>(hb + p.hl.order);
+    }
+  }
+  p.classify = p.reuse_order ? 0 : 1;
+  if (ws.wmask != nullptr) p.merge = kMergeMasked;
+  else if (records) p.merge = ws.rec_meta == 4u && ws.rec_stride == 8u ? kMergeRecords1 : kMergeRecords2;
+  else if (c.arg32) p.merge = lgG >= 3 ? kMergeArg32Short : kMergeArg32Coop;
+  else if (lgG >= 3) p.merge = kMergeShort;
+  else p.merge = p.copy == 2 ? kMergeHotRows : (p.copy == 3 ? kMergeHotBlocks : kMergeCoop);
+  if (ws.P > 1)
+    p.fixup = !c.arg32 ? kFixupPlain : (!records ? kFixupArg32 : (p.merge == kMergeRecords1 ? kFixupRecords1 : kFixupRecords2));
+  return p;
+}
+
+// The run half: T, VEC and RED are the plan's dtype, vec and the family the including unit owns.  A plan that names an
+// instantiation this unit does not carry answers TSAMD_ERR_UNSUPPORTED.
 template <typename T, int VEC, int RED>
-int launch_spmm(const SpmmCall &c, Workspace ws) {
+int run_spmm(const SpmmCall &c, const SpmmPlan &p) {
+  const Workspace &ws = p.ws;
   const int64_t *rowptr = c.rowptr, *col = c.col;
   const T *value = reinterpret_cast<const T *>(c.value), *mat = reinterpret_cast<const T *>(c.mat);
   T *out = reinterpret_cast<T *>(c.out);
@@ -2287,137 +2483,83 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   const bool mean = c.reduce == TSAMD_MEAN;
   hipStream_t stream = c.stream;
   hipEvent_t *ev = c.ev;
-  const LaneLayout lay = lane_layout(K, VEC);
-  const uint32_t ktiles = lay.ktiles;
-  const int lgG = lay.lgG;
+  const uint32_t ktiles = p.lay.ktiles;
+  const int lgG = p.lay.lgG;
   const unsigned int threads = kWavesPerBlock * kWave;
-  int hints_state = c.hints != nullptr ? c.hints_state : 0;  // 0 none (or not for this call), 1 build, 2 reuse
-  HintsLayout hl{};
-  char *hb = nullptr;
-
-  // hot rows: floating-point sums with full-width packets (the shapes relabel_possible admits have no others)
-  constexpr bool kHotable = !kPartial && RED == RED_ADD && VEC == kMaxVec<T> &&
-                            (std::is_same<T, float>::value || std::is_same<T, double>::value ||
-                             std::is_same<T, f16_t>::value || std::is_same<T, bf16_t>::value);
+  const bool reuse = p.hints == 2;
+  char *hb = reinterpret_cast<char *>(c.hints);
+  constexpr bool kFloating = std::is_same<T, float>::value || std::is_same<T, double>::value ||
+                             std::is_same<T, f16_t>::value || std::is_same<T, bf16_t>::value;
+  constexpr bool kHotable = !kPartial && RED == RED_ADD && VEC == kMaxVec<T> && kFloating;  // hot rows / hot blocks
+  constexpr bool kMaskable = RED == RED_ADD && kFloating;                                   // the masked sum
+  constexpr bool kArg32able = !kPartial && RED != RED_ADD && kFloating;                     // int32 winner ids
+  constexpr bool kRecordable = kArg32able && VEC == 4 && sizeof(typename Traits<T>::acc_t) == 4;
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[0], stream));
-  {
-    int mode = ws.xperm != nullptr && VEC > 1 && !ws.out_relabel ? 2 : 0;
-    // masked sums (the pull of the min / max backward): `col` points at winner records, not at column ids, so there
-    // is nothing to probe; same-box A/B at configs[2]: 1.76 ms with the copy, 1.93 without (the rows gathered are
-    // grad_out rows indexed by the R-MAT ROW ids of the forward, which camp like its column ids)
-    if (mode == 2 && ws.wmask != nullptr) mode = 1;
-    ws.relabel_mode = mode;
-    // hot rows instead of the full copy: the side table starts in the copy's region, a whole number of rows from `mat`
-    // (row sizes here are powers of two), and every index the merge kernel forms must fit a signed 32-bit row number
-    bool hot = false;
-    if constexpr (kHotable) {
-      // (lgG < 3: the side-by-side short-row kernel knows nothing of the table; rows of >= 256 bytes in full-width
-      // packets never take it, this keeps the two decisions tied together)
-      if (mode == 2 && lgG < 3 && ws.cache_state == 0 && ws.perm == nullptr)
-        hot = hot_rows_place(ws, mat, ws.blk_word != nullptr ? N + 64 : N, (uint64_t)K * sizeof(T), &ws.hot_side,
-                             &ws.hot_side_row);  // (the block table ends at most 64 rows further from `mat`)
-    }
-    if (!hot) ws.hot_flag = nullptr;
-    // pattern hints (section 1c): the probe's words, the block words, lists and totals live in the caller's buffer.  A
-    // call that does not take the hot-block route runs as tsamd_spmm; a build then leaves both verdicts "no".
-    if (hints_state != 0) {
-      if (!hints_layout(c.dtype, c.reduce, B, M, N, K, E, &hl)) return TSAMD_ERR_UNSUPPORTED;  // (spmm_entry checked)
-      hb = reinterpret_cast<char *>(c.hints);
-      if (hot && ws.blk_word != nullptr) {
-        ws.relabel_flag = reinterpret_cast<int *>(hb + hl.flags);
-        ws.blk_total = reinterpret_cast<uint32_t *>(hb + hl.blk_total);
-        ws.blk_word = reinterpret_cast<uint32_t *>(hb + hl.blk_word);
-        ws.blk_list = reinterpret_cast<uint32_t *>(hb + hl.blk_list);
-      } else {
-        if (hints_state == 1) TSAMD_HIP_TRY(hipMemsetAsync(hb + hl.flags, 0, hl.blk_total - hl.flags, stream));
-        hints_state = 0;
-      }
-    }
-    const bool reuse = hints_state == 2;
-    const bool cached = ws.cache_state != 0 && mode != 0;
-    // (a reused cache keeps the verdict of its first call, and so do reused hints)
-    if (mode == 2 && !(cached && ws.cache_state == 2) && !reuse) {
-      TSAMD_HIP_TRY(hipMemsetAsync(ws.relabel_flag, 0, 4 * sizeof(int), stream));
-      hipLaunchKernelGGL(spmm_probe_kernel, dim3(kProbeBlocks), dim3(256), 0, stream, col, E,
-                         ws.relabel_flag);
+  if (p.hint_clear == 1) TSAMD_HIP_TRY(hipMemsetAsync(hb + p.hl.flags, 0, p.hl.blk_total - p.hl.flags, stream));
+  if (p.probe) {
+    TSAMD_HIP_TRY(hipMemsetAsync(ws.relabel_flag, 0, 4 * sizeof(int), stream));
+    hipLaunchKernelGGL(spmm_probe_kernel, dim3(kProbeBlocks), dim3(256), 0, stream, col, E, ws.relabel_flag);
+    TSAMD_LAUNCH_CHECK();
+  }
+  if (p.copy >= 2) {
+    const int64_t words = ceil_div(N, (int64_t)64);
+    const uint32_t pslots = (uint32_t)(K * sizeof(T) / 16);
+    int lgL = 0;
+    while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
+    if (!reuse) {
+      TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
+      hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
       TSAMD_LAUNCH_CHECK();
     }
-    if (hot) {
-      const int64_t words = ceil_div(N, (int64_t)64);
-      const uint32_t pslots = (uint32_t)(K * sizeof(T) / 16);
-      int lgL = 0;
-      while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
-      if (!reuse) {
-        TSAMD_HIP_TRY(hipMemsetAsync(ws.hot_flag, 0, (size_t)N, stream));
-        hipLaunchKernelGGL(spmm_hot_mark_kernel, dim3(kHotBlocks), dim3(256), 0, stream, col, E, ws);
+    if (p.copy == 3) {  // hot blocks: select and compact, then copy; no scan launches
+      const int lgS = ilog2_ceil(pslots);  // (exact: the rows that relabel_possible admits are powers of two)
+      if (!reuse) {  // (reused hints hold the words, the lists and the totals: the copy is all that reads X)
+        hipLaunchKernelGGL(spmm_hot_block_bits_kernel, dim3(kHotChunks), dim3(256), 0, stream, N, ws);
         TSAMD_LAUNCH_CHECK();
       }
-      if (ws.blk_word != nullptr) {  // hot blocks: select and compact, then copy; no scan launches
-        const int lgS = ilog2_ceil(pslots);  // (exact: the rows that relabel_possible admits are powers of two)
-        if (!reuse) {  // (reused hints hold the words, the lists and the totals: the copy is all that reads X)
-          hipLaunchKernelGGL(spmm_hot_block_bits_kernel, dim3(kHotChunks), dim3(256), 0, stream, N, ws);
-          TSAMD_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(spmm_hot_block_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, kHotBlocks)), dim3(256), 0,
-                           stream, reinterpret_cast<const void *>(mat), N, lgS, ws);
-        TSAMD_LAUNCH_CHECK();
-      } else {
-        hipLaunchKernelGGL(spmm_hot_bits_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(words, (int64_t)4), kHotBlocks)),
-                           dim3(256), 0, stream, N, ws);
-        TSAMD_LAUNCH_CHECK();
-        // (the scan is not device-gated: on a graph the probe does not flag, its three launches run over counts nobody
-        // wrote or reads -- a few idle microseconds, no effect)
-        const int st = exclusive_scan_i64(ws.hot_count, ws.hot_count, words, nullptr, ws.hot_scan, stream);
-        if (st != TSAMD_OK) return st;
-        hipLaunchKernelGGL(spmm_hot_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, 4 * kHotBlocks)), dim3(256), 0,
-                           stream, reinterpret_cast<const void *>(mat), N, pslots, lgL, ws);
-        TSAMD_LAUNCH_CHECK();
-      }
-    } else if (mode != 0) {
-      if (cached) {
-        hipLaunchKernelGGL(spmm_fingerprint_kernel, dim3(kFingerprintWords), dim3(256), 0, stream,
-                           reinterpret_cast<const uint4 *>(mat), (uint64_t)(B * N * K) * sizeof(T) / 16,
-                           ws.cache_fp + kFingerprintWords);
-        TSAMD_LAUNCH_CHECK();
-        if (ws.cache_state == 2) {
-          ws.fp_stored = ws.cache_fp;
-          ws.fp_new = ws.cache_fp + kFingerprintWords;
-        }
-      }
-      // the copy always moves 16-byte packets, whatever packet size the reduction kernel uses
-      constexpr int kPV = 16 / (int)sizeof(T);
-      const uint32_t pslots = (uint32_t)(K / kPV);
-      int lgL = 0;
-      while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
-      hipLaunchKernelGGL((spmm_permute_rows_kernel<T, kPV>), dim3(TSAMD_PERMUTE_BLOCKS), dim3(256), 0, stream, mat,
-                         reinterpret_cast<T *>(ws.xperm), B * N, (uint32_t)N, (uint32_t)K, lgL, ws);
+      hipLaunchKernelGGL(spmm_hot_block_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, kHotBlocks)), dim3(256), 0,
+                         stream, reinterpret_cast<const void *>(mat), N, lgS, ws);
       TSAMD_LAUNCH_CHECK();
-      if (cached)
-        TSAMD_HIP_TRY(hipMemcpyAsync(ws.cache_fp, ws.cache_fp + kFingerprintWords,
-                                     sizeof(unsigned long long) * kFingerprintWords, hipMemcpyDeviceToDevice, stream));
+    } else {
+      hipLaunchKernelGGL(spmm_hot_bits_kernel, dim3((unsigned int)std::min<int64_t>(ceil_div(words, (int64_t)4), kHotBlocks)),
+                         dim3(256), 0, stream, N, ws);
+      TSAMD_LAUNCH_CHECK();
+      // (the scan is not device-gated: on a graph the probe does not flag, its three launches run over counts nobody
+      // wrote or reads -- a few idle microseconds, no effect)
+      const int st = exclusive_scan_i64(ws.hot_count, ws.hot_count, words, nullptr, ws.hot_scan, stream);
+      if (st != TSAMD_OK) return st;
+      hipLaunchKernelGGL(spmm_hot_copy_kernel, dim3((unsigned int)std::min<int64_t>(words, 4 * kHotBlocks)), dim3(256), 0,
+                         stream, reinterpret_cast<const void *>(mat), N, pslots, lgL, ws);
+      TSAMD_LAUNCH_CHECK();
     }
-  }
-  // column order (section 1b): the partition kernel classifies, two more launches build the slot -> partition map
-  const int order_mode = !kPartial && RED == RED_ADD ? order_mode_of(ws, c.dtype, c.reduce, N, K, E, lgG) : 0;
-  const bool reuse_order = hints_state == 2 && order_mode != 0;
-  if (order_mode == 0) {
-    ws.order = nullptr;
-    // (hints built with the order switched off say "not in force" to a later call that has it on)
-    if (hints_state == 1) TSAMD_HIP_TRY(hipMemsetAsync(hb + hl.order_hdr, 0, sizeof(uint32_t) * kOrderHdrWords, stream));
-  } else {
-    ws.order_mode = order_mode;
-    // the counters stay in the workspace and are cleared there; with hints, only the header and the map move: the
-    // scatter kernel writes the header's three words in every call that builds
-    if (!reuse_order) TSAMD_HIP_TRY(hipMemsetAsync(ws.order_hdr, 0, order_clear_bytes(ws.P), stream));
-    if (hints_state != 0) {
-      ws.order_hdr = reinterpret_cast<uint32_t *>(hb + hl.order_hdr);
-      ws.order = reinterpret_cast<uint32_t *>(hb + hl.order);
+  } else if (p.copy == 1) {
+    if (p.cached) {
+      hipLaunchKernelGGL(spmm_fingerprint_kernel, dim3(kFingerprintWords), dim3(256), 0, stream,
+                         reinterpret_cast<const uint4 *>(mat), (uint64_t)(B * N * K) * sizeof(T) / 16,
+                         ws.cache_fp + kFingerprintWords);
+      TSAMD_LAUNCH_CHECK();
     }
+    // the copy always moves 16-byte packets, whatever packet size the reduction kernel uses
+    constexpr int kPV = 16 / (int)sizeof(T);
+    const uint32_t pslots = (uint32_t)(K / kPV);
+    int lgL = 0;
+    while (lgL < 8 && (1u << lgL) < pslots) ++lgL;
+    hipLaunchKernelGGL((spmm_permute_rows_kernel<T, kPV>), dim3(TSAMD_PERMUTE_BLOCKS), dim3(256), 0, stream, mat,
+                       reinterpret_cast<T *>(ws.xperm), B * N, (uint32_t)N, (uint32_t)K, lgL, ws);
+    TSAMD_LAUNCH_CHECK();
+    if (p.cached)
+      TSAMD_HIP_TRY(hipMemcpyAsync(ws.cache_fp, ws.cache_fp + kFingerprintWords,
+                                   sizeof(unsigned long long) * kFingerprintWords, hipMemcpyDeviceToDevice, stream));
   }
+  // column order (section 1b): the partition kernel classifies, two more launches build the slot -> partition map.  The
+  // header, the bucket counts, the cursors and the chunk counts are one span of the WORKSPACE (ws.order_hdr may be the hints')
+  if (p.hint_clear == 2) TSAMD_HIP_TRY(hipMemsetAsync(hb + p.hl.order_hdr, 0, sizeof(uint32_t) * kOrderHdrWords, stream));
+  if (p.order_mode != 0 && !p.reuse_order)
+    TSAMD_HIP_TRY(hipMemsetAsync(ws.order_hist - kOrderHdrWords, 0, order_clear_bytes(ws.P), stream));
   hipLaunchKernelGGL(spmm_partition_kernel, dim3((unsigned int)ceil_div(ws.P + 1, 256)), dim3(256),
-                     0, stream, rowptr, col, M, E, ws, reuse_order ? 0 : 1);
+                     0, stream, rowptr, col, M, E, ws, p.classify);
   TSAMD_LAUNCH_CHECK();
-  if (order_mode != 0 && !reuse_order) {
+  if (p.order_mode != 0 && !p.reuse_order) {
     hipLaunchKernelGGL(spmm_order_scatter_kernel, dim3((unsigned int)ceil_div(ws.P, (int64_t)1024)), dim3(1024), 0, stream,
                        ws);
     TSAMD_LAUNCH_CHECK();
@@ -2427,12 +2569,6 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
   }
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[1], stream));
   const unsigned int gx = (unsigned int)ceil_div(ws.P, kWavesPerBlock);
-  // int32 winner ids (tsamd_spmm_minmax_arg32): min / max of the floating types (what autograd differentiates)
-  constexpr bool kArg32able = !kPartial && RED != RED_ADD &&
-                              (std::is_same<T, float>::value || std::is_same<T, double>::value ||
-                               std::is_same<T, f16_t>::value || std::is_same<T, bf16_t>::value);
-  constexpr bool kMaskable = RED == RED_ADD && (std::is_same<T, float>::value || std::is_same<T, double>::value ||
-                                                std::is_same<T, f16_t>::value || std::is_same<T, bf16_t>::value);
   // every merge launch and every fix-up launch has the same shape: only the instantiation differs
   auto merge = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(gx, (unsigned int)(B * ktiles), 1), dim3(threads), 0, stream, rowptr, col, value, mat,
@@ -2442,168 +2578,56 @@ int launch_spmm(const SpmmCall &c, Workspace ws) {
     hipLaunchKernelGGL(kernel, dim3(gx, (unsigned int)B, 1), dim3(threads), 0, stream, rowptr, out, arg_out, M, (uint32_t)K,
                        E, mean, ws);
   };
-  if (ws.wmask != nullptr) {
-    if constexpr (kMaskable)
-      merge(spmm_merge_kernel<T, VEC, RED, false, true>);
-    else
-      return TSAMD_ERR_UNSUPPORTED;
-  } else if (kArg32able && ws.arg32) {
-    if constexpr (kArg32able) {
-      constexpr bool kRecordable = VEC == 4 && sizeof(typename Traits<T>::acc_t) == 4;
-      if (ws.rec_out != nullptr) {
-        if constexpr (kRecordable) {
-          if (lgG > 2 || ktiles != 1) return TSAMD_ERR_UNSUPPORTED;  // (spmm_emits_records: 33..256 features)
-          if (ws.rec_meta == 4u && ws.rec_stride == 8u)
-            merge(spmm_merge_kernel<T, VEC, RED, false, false, true, 1>);
-          else
-            merge(spmm_merge_kernel<T, VEC, RED, false, false, true, 2>);
-        } else {
-          return TSAMD_ERR_UNSUPPORTED;
-        }
-      } else if (lgG >= 3)
-        merge(spmm_merge_kernel<T, VEC, RED, true, false, true>);
-      else
-        merge(spmm_merge_kernel<T, VEC, RED, false, false, true>);
-    }
-  } else if (ws.arg32) {
-    return TSAMD_ERR_UNSUPPORTED;
-  } else if (lgG >= 3)
-    merge(spmm_merge_kernel<T, VEC, RED, true>);
-  else if (kHotable && ws.hot_flag != nullptr) {
-    if constexpr (kHotable) {
-      if (ws.blk_word != nullptr) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 2>);
-      else merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 1>);
-    }
-  } else
-    merge(spmm_merge_kernel<T, VEC, RED, false>);
+  const SpmmMerge m = p.merge;
+  // (the order of this chain is the order of the kernels in the code object: profiles/forward_plan_kres.md)
+  if (kMaskable && m == kMergeMasked) { if constexpr (kMaskable) merge(spmm_merge_kernel<T, VEC, RED, false, true>); }
+  else if (kRecordable && m == kMergeRecords1) { if constexpr (kRecordable) merge(spmm_merge_kernel<T, VEC, RED, false, false, true, 1>); }
+  else if (kRecordable && m == kMergeRecords2) { if constexpr (kRecordable) merge(spmm_merge_kernel<T, VEC, RED, false, false, true, 2>); }
+  else if (kArg32able && m == kMergeArg32Short) { if constexpr (kArg32able) merge(spmm_merge_kernel<T, VEC, RED, true, false, true>); }
+  else if (kArg32able && m == kMergeArg32Coop) { if constexpr (kArg32able) merge(spmm_merge_kernel<T, VEC, RED, false, false, true>); }
+  else if (m == kMergeShort) merge(spmm_merge_kernel<T, VEC, RED, true>);
+  else if (kHotable && m == kMergeHotBlocks) { if constexpr (kHotable) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 2>); }
+  else if (kHotable && m == kMergeHotRows) { if constexpr (kHotable) merge(spmm_merge_kernel<T, VEC, RED, false, false, false, 0, 1>); }
+  else if (m == kMergeCoop) merge(spmm_merge_kernel<T, VEC, RED, false>);
+  else return TSAMD_ERR_UNSUPPORTED;
   TSAMD_LAUNCH_CHECK();
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[2], stream));
-  if (ws.P > 1) {
-    if (kArg32able && ws.arg32) {
-      if constexpr (kArg32able) {
-        constexpr bool kRecordable = VEC == 4 && sizeof(typename Traits<T>::acc_t) == 4;
-        if (ws.rec_out != nullptr) {
-          if constexpr (kRecordable) {
-            if (ws.rec_meta == 4u && ws.rec_stride == 8u)
-              fixup(spmm_fixup_kernel<T, RED, true, 1>);
-            else
-              fixup(spmm_fixup_kernel<T, RED, true, 2>);
-          }
-        } else {
-          fixup(spmm_fixup_kernel<T, RED, true>);
-        }
-      }
-    } else {
-      fixup(spmm_fixup_kernel<T, RED>);
-    }
-    TSAMD_LAUNCH_CHECK();
-  }
+  if (kRecordable && p.fixup == kFixupRecords1) { if constexpr (kRecordable) fixup(spmm_fixup_kernel<T, RED, true, 1>); }
+  else if (kRecordable && p.fixup == kFixupRecords2) { if constexpr (kRecordable) fixup(spmm_fixup_kernel<T, RED, true, 2>); }
+  else if (kArg32able && p.fixup == kFixupArg32) { if constexpr (kArg32able) fixup(spmm_fixup_kernel<T, RED, true>); }
+  else if (p.fixup == kFixupPlain) fixup(spmm_fixup_kernel<T, RED>);
+  if (p.fixup != kFixupNone) TSAMD_LAUNCH_CHECK();
   if (ev) TSAMD_HIP_TRY(hipEventRecord(ev[3], stream));
   return TSAMD_OK;
 }
 
 // RED is the family the including unit owns (mean is the run-time flag of RED_ADD)
 template <typename T, int RED>
-int dispatch_spmm(int vec, const SpmmCall &c, const Workspace &ws) {
+int dispatch_spmm(const SpmmCall &c, const SpmmPlan &p) {
   // Packet per lane: up to 16 bytes for 4/8-byte types; up to 8 bytes (4 elements) for f16/bf16 --
   // with 8 narrow elements per lane the per-element state (fp32 accumulator, and the arg for
   // min/max) costs 80-84 VGPRs = 5 waves/SIMD, with 4 it is 8 waves/SIMD (measured +5...27 %).
   // Row pitches that are not a multiple of 16 bytes fall back to 8- or 4-byte packets
   // (e.g. F = 602 fp32 -> 8 bytes), odd pitches to single elements.
   if constexpr (kMaxVec<T> >= 4) {
-    if (vec >= 4) return launch_spmm<T, 4, RED>(c, ws);
+    if (p.vec >= 4) return run_spmm<T, 4, RED>(c, p);
   }
   if constexpr (kMaxVec<T> >= 2) {
-    if (vec >= 2) return launch_spmm<T, 2, RED>(c, ws);
+    if (p.vec >= 2) return run_spmm<T, 2, RED>(c, p);
   }
-  return launch_spmm<T, 1, RED>(c, ws);
+  return run_spmm<T, 1, RED>(c, p);
 }
 
-// What every SpMM entry point shares: the argument checks (their order and status codes are part of the C-ABI), the
-// workspace, the packet width.  `launch(vec, ws)` then reaches the instantiations of the including unit.
+// What every SpMM entry point is: plan, then run.  `launch(plan)` reaches the instantiations of the including unit.
 template <typename Launch>
 int spmm_entry(const SpmmCall &c, Launch launch) {
-  const int dtype = c.dtype, reduce = c.reduce;
-  const int64_t B = c.B, M = c.M, N = c.N, K = c.K, E = c.E;
-  if (B < 0 || M < 0 || N < 0 || K < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (reduce < TSAMD_SUM || reduce > TSAMD_MAX) return TSAMD_ERR_UNSUPPORTED;
-  if (dtype_size(dtype) == 0) return TSAMD_ERR_UNSUPPORTED;
-  if (N >= (int64_t)1 << 32 || K >= (int64_t)1 << 31 || B >= 65536) return TSAMD_ERR_UNSUPPORTED;
-  if (B * ceil_div(K, 64) >= 65536) return TSAMD_ERR_UNSUPPORTED;  // gridDim.y = B * feature tiles
-  const bool minmax = reduce == TSAMD_MIN || reduce == TSAMD_MAX;
-  // pattern hints (tsamd_spmm_hinted): the plain product of a shape in their scope, nothing else
-  HintsLayout hl{};
-  if (c.hints_state != 0) {
-    if (c.hints == nullptr || (c.hints_state != 1 && c.hints_state != 2) || ((uintptr_t)c.hints % 256) != 0) return TSAMD_ERR_INVALID;
-    if (c.relabelled || c.perm != nullptr || c.wmask != nullptr || c.cache != nullptr || c.partial || c.arg32 ||
-        !hints_layout(dtype, reduce, B, M, N, K, E, &hl))
-      return TSAMD_ERR_UNSUPPORTED;
-  }
-  if (B * M * K == 0) return TSAMD_OK;  // nothing to write
-  if (!c.rowptr || !c.out || (E > 0 && (!c.col || !c.mat)) || (minmax && !c.arg_out))
-    return TSAMD_ERR_INVALID;
-  // verification mode (tsamd_spmm_reference_order): the plain product in the reference's order of operations
-  // (hints: it builds none -- both verdicts "no" -- and reads none)
-  if (spmm_reference_order_on() && c.hints_state == 1)
-    TSAMD_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(c.hints) + hl.flags, 0, hl.blk_total - hl.flags, c.stream));
-  if (spmm_reference_order_on() && !c.relabelled && c.perm == nullptr && c.wmask == nullptr && !c.partial)
-    return spmm_reference_order_run(dtype, reduce, c.rowptr, c.col, c.value, c.mat, c.out, c.arg_out, c.arg32, B, M, N, K, E,
-                                    c.stream);
-  // operand cache: the relabelled copy and the probe verdict live in the caller's buffer, not in the workspace
-  const size_t cache_need = operand_cache_bytes(dtype, reduce, B, N, K, E);
-  const bool use_cache = c.cache != nullptr && !c.relabelled && cache_need > 0 && c.cache_bytes >= cache_need &&
-                         ((uintptr_t)c.cache % 256) == 0 && ((uintptr_t)c.mat % 16) == 0;
-  const bool no_xperm_in_ws = c.relabelled || use_cache || c.partial;
-  const size_t need = carve(nullptr, dtype, reduce, B, M, N, K, E, nullptr, no_xperm_in_ws, c.wmask != nullptr);
-  if (!c.workspace || c.workspace_bytes < need) return TSAMD_ERR_WORKSPACE;
-  if ((uintptr_t)c.workspace % 256 != 0) return TSAMD_ERR_WORKSPACE;
-  Workspace ws;
-  carve(c.workspace, dtype, reduce, B, M, N, K, E, &ws, no_xperm_in_ws, c.wmask != nullptr);
-  if (use_cache) {
-    char *cb = reinterpret_cast<char *>(c.cache);
-    ws.relabel_flag = reinterpret_cast<int *>(cb);
-    ws.cache_fp = reinterpret_cast<unsigned long long *>(cb + 256);
-    ws.xperm = cb + kOperandCacheHeader;
-    ws.cache_state = c.cache_valid ? 2 : 1;
-  }
-  if (c.relabelled) {
-    if (M >= (int64_t)1 << 32) return TSAMD_ERR_UNSUPPORTED;
-    ws.out_relabel = 1;
-  }
-  ws.perm = c.perm;
-  if (c.arg32) {  // E itself ("no winner") must fit a non-negative int32
-    if (!minmax || c.partial || E >= (int64_t)1 << 31) return TSAMD_ERR_UNSUPPORTED;
-    ws.arg32 = 1;
-    if (c.rec_out != nullptr) {  // (tsamd_spmm_minmax_records checked the shape: spmm_emits_records)
-      ws.rec_out = c.rec_out;
-      ws.rec_value = c.value;
-      ws.rec_stride = win_record_stride(K);
-      ws.rec_meta = (uint32_t)ceil_div(K, 32);
-      ws.rec_has_z = ((ws.rec_meta + 3u) & 3u) != 0u ? 1 : 0;
-      ws.snap = snap_items(ws.items);
-    }
-  }
-  // min / max: partition boundaries snap to row starts (spmm_partition_kernel) -- fewer cut rows, fewer carry records and
-  // fix-up waves: configs[2] forward 1.024-1.029 -> 1.000 ms (bf16), 1.57 -> 1.55 (fp32), same box
-  // (profiles/r06_ab_minmax_snap.jsonl).  The result does not depend on where a row is cut (no rounding in min / max);
-  // sums keep their partition: theirs does, in the last bits.
-  if (minmax && ws.snap == 0) ws.snap = snap_items(ws.items);
-  if (c.partial) {
-    if (reduce == TSAMD_MEAN && c.deg_rowptr == nullptr) return TSAMD_ERR_INVALID;
-    ws.partial = 1;
-    ws.accumulate = c.accumulate ? 1 : 0;
-    ws.arg_map = c.arg_map;
-    ws.arg_none = c.arg_none;
-    ws.deg_rowptr = reduce == TSAMD_MEAN ? c.deg_rowptr : nullptr;
-  }
-  if (c.wmask != nullptr) {
-    if (E >= (int64_t)1 << 32 || reduce != TSAMD_SUM) return TSAMD_ERR_UNSUPPORTED;  // 32-bit entry ids in the windows
-    ws.wmask = c.wmask;
-    ws.rec_stride = win_record_stride(K);
-    ws.rec_meta = (uint32_t)ceil_div(K, 32);
-    ws.rec_has_z = win_record_masked_has_z(ws.rec_meta);  // a padding word behind (id, value)
-  }
-  return launch(packet_width(dtype, minmax, c.arg32, K, c.mat, c.out, c.arg_out), ws);
+  const SpmmPlan p = plan_spmm(c, false);
+  if (p.status != TSAMD_OK || p.what == SpmmPlan::Nothing) return p.status;
+  if (p.what == SpmmPlan::Run) return launch(p);
+  if (p.hint_clear == 1)
+    TSAMD_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(c.hints) + p.hl.flags, 0, p.hl.blk_total - p.hl.flags, c.stream));
+  return spmm_reference_order_run(c.dtype, c.reduce, c.rowptr, c.col, c.value, c.mat, c.out, c.arg_out, c.arg32, c.B, c.M, c.N,
+                                  c.K, c.E, c.stream);
 }
 
 }  // namespace

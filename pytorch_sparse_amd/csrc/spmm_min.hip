@@ -2,6 +2,6 @@
 #define TSAMD_SPMM_PARTIAL_BUILD 0
 #include "spmm_kernels.h"
 
-int tsamd::spmm_launch_min(int vec, const SpmmCall &c, const Workspace &ws) {
-  return TSAMD_DISPATCH_DTYPE_ALL(c.dtype, [&]() -> int { return dispatch_spmm<scalar_t, RED_MIN>(vec, c, ws); });
+int tsamd::spmm_launch_min(const SpmmCall &c, const SpmmPlan &p) {
+  return TSAMD_DISPATCH_DTYPE_ALL(c.dtype, [&]() -> int { return dispatch_spmm<scalar_t, RED_MIN>(c, p); });
 }

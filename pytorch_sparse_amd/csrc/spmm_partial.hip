@@ -26,7 +26,7 @@ extern "C" int tsamd_spmm_partial(int dtype, int reduce, const int64_t *rowptr, 
   c.arg_map = arg_map;
   c.arg_none = arg_none;
   c.deg_rowptr = deg_rowptr;
-  return spmm_entry(c, [&](int vec, const Workspace &ws) -> int {
+  return spmm_entry(c, [&](const SpmmPlan &p) -> int {
     // partial products are the stages of the sharded SpMM over dense FEATURE matrices: floating point only
     if (dtype != TSAMD_F32 && dtype != TSAMD_F64 && dtype != TSAMD_F16 && dtype != TSAMD_BF16) return TSAMD_ERR_UNSUPPORTED;
     return TSAMD_DISPATCH_DTYPE_ALL(dtype, [&]() -> int {
@@ -34,11 +34,11 @@ extern "C" int tsamd_spmm_partial(int dtype, int reduce, const int64_t *rowptr, 
                       std::is_same<scalar_t, f16_t>::value || std::is_same<scalar_t, bf16_t>::value))
         return (int)TSAMD_ERR_UNSUPPORTED;
       else if (reduce == TSAMD_MIN)
-        return dispatch_spmm<scalar_t, RED_MIN>(vec, c, ws);
+        return dispatch_spmm<scalar_t, RED_MIN>(c, p);
       else if (reduce == TSAMD_MAX)
-        return dispatch_spmm<scalar_t, RED_MAX>(vec, c, ws);
+        return dispatch_spmm<scalar_t, RED_MAX>(c, p);
       else
-        return dispatch_spmm<scalar_t, RED_ADD>(vec, c, ws);
+        return dispatch_spmm<scalar_t, RED_ADD>(c, p);
     });
   });
 }

@@ -275,6 +275,10 @@ def test_scatter_and_row_parallel_at_the_lds_capacity(dev, K, dtype, exact, redu
     sddmm = (K * mr.element_size(dtype)) % 16 == 0
     r = d.route('ids64', True)
     assert (r['status'], r['mat'], r['value']) == (0, 'pull', 'masked_sddmm' if sddmm else 'row_parallel'), tag
+    # the masked sum has no side-by-side kernel: cooperative also where a plain sum would go short (8 packets and fewer:
+    # K <= 32 fp32, <= 16 fp64, <= 32 of the 2-byte types)
+    assert r['family'] == 'cooperative' and (r['sum_lgG'] >= 3) == (-(-K // r['vec']) <= 8), tag
+    assert r['sum_lgG'] >= 3 or K > 16, tag
     gv, gm = d.run('ids64', True)
     _check(c, gv, gm, exact, 'pull', tag + ('ids64 pull', r['value']))
     gv2, gm2 = d.run('ids64', True)

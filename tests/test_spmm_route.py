@@ -240,5 +240,40 @@ def test_reference_order_reports_its_own_family():
     assert route(F32, 'sum', 1, 1000, 500, 64, 20000)['family'] == 'cooperative'
 
 
+# the masked sum (the pull of the min / max backward) launches the cooperative masked kernel at every width: the family
+# word says what is launched, whatever lgG.  K -> lgG of the sum
+MASKED = [(8, 5), (16, 4), (32, 3), (64, 2)]
+
+
+@pytest.mark.parametrize('K,lgG', MASKED)
+def test_masked_sum_family_is_cooperative(K, lgG):
+    r = nat.spmm_minmax_bw_route('ids64', F32, 1, 1000, 1000, K, 20000, False, True)
+    assert (r['mat'], r['family'], r['sum_lgG']) == ('pull', 'cooperative', lgG)
+
+
+def test_one_plan_behind_every_query():
+    """tsamd_spmm_route, tsamd_spmm_hot_rows_layout, tsamd_spmm_hot_blocks_layout and tsamd_spmm_order_layout answer from
+    one plan: over dtype x reduce x B x N x row bytes x E x mat offset x out offset (5760 calls, M = 2048) they agree."""
+    import itertools
+    L, i64, vp = nat.lib(), ctypes.c_int64, ctypes.c_void_p
+    lay, order = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 8)()
+    cases = 0
+    for dtype, reduce, B, N, row_bytes, E, moff, ooff in itertools.product(
+            (F32, F64, BF16, I32), ('sum', 'mean', 'max'), (1, 2), (4095, 4096, 65535, 65536, 131072), (128, 256, 384, 512),
+            (1 << 20, 1 << 24), (0, 8, 16), (0, 8)):
+        K = row_bytes // torch.empty(0, dtype=dtype).element_size()
+        r = route(dtype, reduce, B, 2048, N, K, E, mat=A + moff, out=2 * A + ooff)
+        args = (nat.dtype_code(dtype), nat.REDUCES[reduce], i64(B), i64(2048), i64(N), i64(K), i64(E), vp(A + moff),
+                vp(2 * A + ooff), vp(WS))
+        assert L.tsamd_spmm_hot_rows_layout(*args, lay) == (1 if r['copy'] == 2 else 0)
+        assert L.tsamd_spmm_hot_blocks_layout(*args, lay) == (1 if r['copy'] == 3 else 0)
+        if L.tsamd_spmm_order_layout(*args, order) != 0:
+            assert reduce in ('sum', 'mean') and r['family'] in ('cooperative', 'hot_rows', 'hot_blocks')
+        if r['copy'] == 3:
+            assert nat.spmm_hints_bytes(dtype, reduce, B, 2048, N, K, E) > 0
+        cases += 1
+    assert cases == 5760
+
+
 def test_build_flags_stay_zero():
     assert nat.lib().tsamd_build_flags() == 0
