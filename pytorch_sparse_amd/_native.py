@@ -109,10 +109,11 @@ def lib():
         L.tsamd_attention_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, vp, vp, i64p]
         L.tsamd_attention_heads_workspace_bytes.argtypes = [ctypes.c_int, i64, i64, i64]
         L.tsamd_attention_heads_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_attention_heads.argtypes = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
-        L.tsamd_attention_heads_bw.argtypes = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
-        L.tsamd_gat_attention_heads.argtypes = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
-        L.tsamd_gat_attention_heads_bw.argtypes = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
+        # the fused calls: dot-product and additive (GAT) scores share their signatures
+        fused_fw = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
+        fused_bw = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
+        L.tsamd_attention_heads.argtypes = L.tsamd_gat_attention_heads.argtypes = fused_fw
+        L.tsamd_attention_heads_bw.argtypes = L.tsamd_gat_attention_heads_bw.argtypes = fused_bw
         L.tsamd_select_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_tiles_workspace_bytes.restype = ctypes.c_size_t

@@ -100,46 +100,61 @@ class _SpmmHeads(torch.autograd.Function):
         return grad_value, grad_x, None, None, None, None, None, None, None
 
 
+# ---- the fused calls.  Dot-product and additive scores share the bookkeeping of their autograd pair; below, (sr, sc)
+# are the score operands of the rows and of the columns, (q, k) or (a_dst, a_src), and `scalar` is scale or negative_slope
+def _fused_forward(ctx, op: str, sr: Tensor, sc: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor],
+                   rowptr: Tensor, col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor],
+                   csr2csc: Optional[Tensor], scalar: float) -> Tensor:
+    """out of ``tsamd::<op>``; saves (operands, out, lse, rowptr, col, [bias], [row], [colptr, row_csc, csr2csc])"""
+    b = None if bias is None else bias.detach()
+    out, lse = getattr(torch.ops.tsamd, op)(rowptr, col, b, sr.detach(), sc.detach(), v.detach(), scalar)
+    ctx.scalar = scalar
+    ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
+    ctx.save_for_backward(*([sr, sc, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
+                            ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+    return out
+
+
+def _fused_backward(ctx, op_bw: str, grad_out: Tensor):
+    """(p, d) = ``tsamd::<op_bw>`` on what the forward saved -> (sr, sc, d, rowptr, col, the column side or None, grad_v,
+    grad_bias): grad_v = spmm_heads(columns; p, grad_out), grad_bias = d, summed over the heads for a [nnz] bias.  The
+    gradients of the score operands are the caller's."""
+    sr, sc, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
+    rest = list(ctx.saved_tensors[7:])
+    bias = rest.pop(0) if ctx.has_bias else None
+    row = rest.pop(0) if ctx.has_row else None
+    csc = rest if ctx.has_csc else None
+    g = grad_out.contiguous()  # expanded / transposed gradients arrive here
+    p, d = getattr(torch.ops.tsamd, op_bw)(row, rowptr, col, bias, sr, sc, v, out, lse, g, ctx.scalar)
+    grad_v = grad_bias = None
+    if ctx.needs_input_grad[2]:
+        grad_v = torch.ops.tsamd.spmm_heads(csc[0], csc[1], csc[2], p, g, v.size(0))
+    if ctx.has_bias and ctx.needs_input_grad[3]:
+        grad_bias = d if bias.dim() == 2 else d.sum(1, dtype=lse.dtype).to(d.dtype)
+    return sr, sc, d, rowptr, col, csc, grad_v, grad_bias
+
+
 class _AttentionHeads(torch.autograd.Function):
     """out = tsamd::attention_heads; backward: (p, ds) = tsamd::attention_heads_bw, then grad_q = scale * spmm_heads(rows;
     ds, k), grad_k = scale * spmm_heads(columns; ds, q), grad_v = spmm_heads(columns; p, grad_out), grad_bias = ds"""
 
     @staticmethod
-    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor], rowptr: Tensor,
-                col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor], csr2csc: Optional[Tensor],
-                scale: float):
-        b = None if bias is None else bias.detach()
-        out, lse = torch.ops.tsamd.attention_heads(rowptr, col, b, q.detach(), k.detach(), v.detach(), scale)
-        ctx.scale = scale
-        ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
-        ctx.save_for_backward(*([q, k, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
-                                ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
-        return out
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, *bias_pattern_scale):
+        return _fused_forward(ctx, 'attention_heads', q, k, v, *bias_pattern_scale)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out: Tensor):
-        q, k, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
-        rest = list(ctx.saved_tensors[7:])
-        bias = rest.pop(0) if ctx.has_bias else None
-        row = rest.pop(0) if ctx.has_row else None
-        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
-        p, ds = torch.ops.tsamd.attention_heads_bw(row, rowptr, col, bias, q, k, v, out, lse, g, ctx.scale)
-        grad_q = grad_k = grad_v = grad_bias = None
+        q, k, ds, rowptr, col, csc, grad_v, grad_bias = _fused_backward(ctx, 'attention_heads_bw', grad_out)
+        grad_q = grad_k = None
         if ctx.needs_input_grad[0]:
             grad_q = torch.ops.tsamd.spmm_heads(rowptr, col, None, ds, k, q.size(0))
-            if ctx.scale != 1.0:
-                grad_q.mul_(ctx.scale)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            colptr, row_csc, csr2csc = rest
-            if ctx.needs_input_grad[1]:
-                grad_k = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, ds, q, k.size(0))
-                if ctx.scale != 1.0:
-                    grad_k.mul_(ctx.scale)
-            if ctx.needs_input_grad[2]:
-                grad_v = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, p, g, k.size(0))
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            grad_bias = ds if bias.dim() == 2 else ds.sum(1, dtype=lse.dtype).to(ds.dtype)
+            if ctx.scalar != 1.0:
+                grad_q.mul_(ctx.scalar)
+        if ctx.needs_input_grad[1]:
+            grad_k = torch.ops.tsamd.spmm_heads(csc[0], csc[1], csc[2], ds, q, k.size(0))
+            if ctx.scalar != 1.0:
+                grad_k.mul_(ctx.scalar)
         return grad_q, grad_k, grad_v, grad_bias, None, None, None, None, None, None, None
 
 
@@ -149,40 +164,46 @@ class _GatAttentionHeads(torch.autograd.Function):
     grad_out), grad_bias = dz"""
 
     @staticmethod
-    def forward(ctx, a_dst: Tensor, a_src: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor],
-                rowptr: Tensor, col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor],
-                csr2csc: Optional[Tensor], negative_slope: float):
-        b = None if bias is None else bias.detach()
-        out, lse = torch.ops.tsamd.gat_attention_heads(rowptr, col, b, a_dst.detach(), a_src.detach(), v.detach(),
-                                                       negative_slope)
-        ctx.negative_slope = negative_slope
-        ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
-        ctx.save_for_backward(*([a_dst, a_src, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
-                                ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
-        return out
+    def forward(ctx, a_dst: Tensor, a_src: Tensor, v: Tensor, *bias_pattern_slope):
+        return _fused_forward(ctx, 'gat_attention_heads', a_dst, a_src, v, *bias_pattern_slope)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out: Tensor):
-        a_dst, a_src, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
-        rest = list(ctx.saved_tensors[7:])
-        bias = rest.pop(0) if ctx.has_bias else None
-        row = rest.pop(0) if ctx.has_row else None
-        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
-        p, dz = torch.ops.tsamd.gat_attention_heads_bw(row, rowptr, col, bias, a_dst, a_src, v, out, lse, g,
-                                                       ctx.negative_slope)
-        grad_dst = grad_src = grad_v = grad_bias = None
+        a_dst, a_src, dz, rowptr, col, csc, grad_v, grad_bias = _fused_backward(ctx, 'gat_attention_heads_bw', grad_out)
+        grad_dst = grad_src = None
         if ctx.needs_input_grad[0]:
             grad_dst = torch.ops.tsamd.segment_reduce(dz, None, rowptr, a_dst.size(0), 'sum', True)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            colptr, row_csc, csr2csc = rest
-            if ctx.needs_input_grad[1]:
-                grad_src = torch.ops.tsamd.segment_reduce(dz, csr2csc, colptr, a_src.size(0), 'sum', True)
-            if ctx.needs_input_grad[2]:
-                grad_v = torch.ops.tsamd.spmm_heads(colptr, row_csc, csr2csc, p, g, v.size(0))
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            grad_bias = dz if bias.dim() == 2 else dz.sum(1, dtype=lse.dtype).to(dz.dtype)
+        if ctx.needs_input_grad[1]:
+            grad_src = torch.ops.tsamd.segment_reduce(dz, csc[2], csc[0], a_src.size(0), 'sum', True)
         return grad_dst, grad_src, grad_v, grad_bias, None, None, None, None, None, None, None
+
+
+def _fused(adj: SparseTensor, fn, op: str, sr: Tensor, sc: Tensor, v: Tensor, b: Optional[Tensor],
+           scalar: float) -> Tensor:
+    """The fused call: through the autograd pair `fn` where a gradient will be asked for -- with the column side of the
+    pattern when it is sc's or v's -- and through ``tsamd::<op>`` alone where none will"""
+    st = adj.storage
+    rowptr, col = st.rowptr(), st.col()
+    grad = torch.is_grad_enabled()
+    if grad and (sr.requires_grad or sc.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
+        csc = _csc_side(st) if sc.requires_grad or v.requires_grad else (None, None, None)
+        return fn.apply(sr, sc, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], scalar)
+    return getattr(torch.ops.tsamd, op)(rowptr, col, b, sr, sc, v, scalar)[0]
+
+
+def _edge_bias(adj: SparseTensor, H: int, dtype: torch.dtype, who: str) -> Tensor:
+    """The values of ``adj`` as the bias of a fused call with ``H`` heads, in ``dtype``; ``who`` is the operand the message
+    counts the heads of"""
+    b = adj.storage.value()
+    if b is None:
+        raise ValueError('bias=True needs a SparseTensor with values, this one has none')
+    if not b.is_floating_point():
+        raise ValueError('the bias must be floating point, got %s values' % b.dtype)
+    if b.dim() not in (1, 2) or (b.dim() == 2 and b.size(1) != H):
+        raise ValueError('the bias must be [nnz] or [nnz, %d] values (%s has %d heads), got %s'
+                         % (H, who, H, tuple(b.shape)))
+    return b.to(dtype)
 
 
 def _check_operand(t: Tensor, name: str, rows: int, what: str) -> None:
@@ -277,26 +298,9 @@ def attention(adj: SparseTensor, q: Tensor, k: Tensor, v: Tensor, scale: Optiona
     H, D = q.size(1), q.size(2)
     if D == 0:
         raise ValueError('attention needs at least one feature per head')
-    b = None
-    if bias:
-        b = adj.storage.value()
-        if b is None:
-            raise ValueError('bias=True needs a SparseTensor with values, this one has none')
-        if not b.is_floating_point():
-            raise ValueError('the bias must be floating point, got %s values' % b.dtype)
-        if b.dim() not in (1, 2) or (b.dim() == 2 and b.size(1) != H):
-            raise ValueError('the bias must be [nnz] or [nnz, %d] values (q has %d heads), got %s'
-                             % (H, H, tuple(b.shape)))
-        b = b.to(q.dtype)
+    b = _edge_bias(adj, H, q.dtype, 'q') if bias else None
     scale = float(D) ** -0.5 if scale is None else float(scale)
-    st = adj.storage
-    rowptr, col = st.rowptr(), st.col()
-    grad = torch.is_grad_enabled()
-    if grad and (q.requires_grad or k.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
-        csc = _csc_side(st) if k.requires_grad or v.requires_grad else (None, None, None)
-        out = _AttentionHeads.apply(q, k, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], scale)
-    else:
-        out = torch.ops.tsamd.attention_heads(rowptr, col, b, q, k, v, scale)[0]
+    out = _fused(adj, _AttentionHeads, 'attention_heads', q, k, v, b, scale)
     return out.squeeze(1) if flat else out
 
 
@@ -337,25 +341,8 @@ def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, ne
     negative_slope = float(negative_slope)
     if negative_slope != negative_slope or negative_slope in (float('inf'), float('-inf')):
         raise ValueError('negative_slope must be finite, got %r' % negative_slope)
-    b = None
-    if bias:
-        b = adj.storage.value()
-        if b is None:
-            raise ValueError('bias=True needs a SparseTensor with values, this one has none')
-        if not b.is_floating_point():
-            raise ValueError('the bias must be floating point, got %s values' % b.dtype)
-        if b.dim() not in (1, 2) or (b.dim() == 2 and b.size(1) != H):
-            raise ValueError('the bias must be [nnz] or [nnz, %d] values (v has %d heads), got %s'
-                             % (H, H, tuple(b.shape)))
-        b = b.to(v.dtype)
-    st = adj.storage
-    rowptr, col = st.rowptr(), st.col()
-    grad = torch.is_grad_enabled()
-    if grad and (a_dst.requires_grad or a_src.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
-        csc = _csc_side(st) if a_src.requires_grad or v.requires_grad else (None, None, None)
-        out = _GatAttentionHeads.apply(a_dst, a_src, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], negative_slope)
-    else:
-        out = torch.ops.tsamd.gat_attention_heads(rowptr, col, b, a_dst, a_src, v, negative_slope)[0]
+    b = _edge_bias(adj, H, v.dtype, 'v') if bias else None
+    out = _fused(adj, _GatAttentionHeads, 'gat_attention_heads', a_dst, a_src, v, b, negative_slope)
     return out.squeeze(1) if flat else out
 
 

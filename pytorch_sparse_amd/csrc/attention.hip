@@ -78,6 +78,25 @@ struct AtPlan {
   int64_t chunk;    // entries per group
 };
 
+// one call, forward or backward, in either score mode: what the four entry points fill in
+struct AtCall {
+  int dtype, mode;
+  const int64_t *row, *rowptr, *col;  // row: backward only, may be null
+  const void *bias;
+  int64_t bias_heads;
+  const void *sr, *sc;  // the score operands of the row and of the column: q, k (kAtDot) or a_dst, a_src (kAtAdditive)
+  const void *v;
+  double scalar;        // scale (kAtDot) or negative_slope (kAtAdditive)
+  void *out, *lse;      // written by the forward, read by the backward
+  const void *grad_out;
+  void *p_out, *d_out;  // backward: p and ds (kAtDot) or dz (kAtAdditive)
+  int64_t nseg, nsrc, H, D, E;
+  void *workspace;
+  size_t workspace_bytes;
+  hipStream_t stream;
+};
+constexpr int kAtProceed = -1;  // no status yet: the call has work and its arguments are in order
+
 __device__ __forceinline__ float at_log(float x) { return logf(x); }
 __device__ __forceinline__ double at_log(double x) { return log(x); }
 
@@ -392,33 +411,32 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_fixup_kernel(
 }
 
 template <typename T, int MODE>
-int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, const void *bias, int64_t bias_heads,
-                     const void *q, const void *k, const void *v, double scale, void *out, void *lse, int64_t nseg,
-                     int64_t H, int64_t D, int64_t E, void *workspace, hipStream_t stream) {
+int launch_attention(const AtPlan &p, const AtCall &c) {
   using A = typename Traits<T>::acc_t;
-  const int64_t W = H * D;
+  const int64_t nseg = c.nseg, H = c.H, D = c.D, E = c.E, W = H * D;
+  hipStream_t stream = c.stream;
   const dim3 block(kAtWaves * kWave);
-  T *oo = reinterpret_cast<T *>(out);
-  A *ll = reinterpret_cast<A *>(lse);
+  T *oo = reinterpret_cast<T *>(c.out);
+  A *ll = reinterpret_cast<A *>(c.lse);
   {  // rows without entries: out = 0, lse = -inf
     const int64_t bytes = (int64_t)sizeof(T) * nseg * W;
     const int64_t units = bytes / 16 + 2, n = units > nseg * H ? units : nseg * H;
     hipLaunchKernelGGL((attention_fill_kernel<A>), dim3((unsigned int)ceil_div(n, (int64_t)256)), block, 0, stream,
-                       reinterpret_cast<unsigned char *>(out), bytes, ll, nseg * H);
+                       reinterpret_cast<unsigned char *>(c.out), bytes, ll, nseg * H);
     TSAMD_LAUNCH_CHECK();
   }
   if (E == 0) return TSAMD_OK;
   const SegRecords rec = at_records(sizeof(A), p.chunk, H, D, E);
   const int64_t nchunks = (int64_t)rec.nchunks;
-  A *head_acc = rec.plane<A>(workspace, 0), *tail_acc = rec.plane<A>(workspace, 1);
-  A *head_ml = rec.plane<A>(workspace, 2), *tail_ml = rec.plane<A>(workspace, 3);
-  int64_t *head_seg = rec.head_seg(workspace), *tail_seg = rec.tail_seg(workspace);
+  A *head_acc = rec.plane<A>(c.workspace, 0), *tail_acc = rec.plane<A>(c.workspace, 1);
+  A *head_ml = rec.plane<A>(c.workspace, 2), *tail_ml = rec.plane<A>(c.workspace, 3);
+  int64_t *head_seg = rec.head_seg(c.workspace), *tail_seg = rec.tail_seg(c.workspace);
   const dim3 tiles((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)p.blocks);
-  const T *bb = reinterpret_cast<const T *>(bias), *qq = reinterpret_cast<const T *>(q),
-          *kk = reinterpret_cast<const T *>(k), *xx = reinterpret_cast<const T *>(v);
+  const T *bb = reinterpret_cast<const T *>(c.bias), *qq = reinterpret_cast<const T *>(c.sr),
+          *kk = reinterpret_cast<const T *>(c.sc), *xx = reinterpret_cast<const T *>(c.v);
 #define TSAMD_AT_LAUNCH(PACKED, WIDE)                                                                              \
-  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE, MODE>), tiles, block, 0, stream, ptr, ind, bb,        \
-                     bias_heads, qq, kk, xx, (A)scale, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg,     \
+  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE, MODE>), tiles, block, 0, stream, c.rowptr, c.col, bb, \
+                     c.bias_heads, qq, kk, xx, (A)c.scalar, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg, \
                      tail_seg, nseg, E, H, D, p.lg_lph, p.lg_hpp, p.fblocks)
   if (p.fblocks > 1) {
     if (p.generic) TSAMD_AT_LAUNCH(false, true); else TSAMD_AT_LAUNCH(true, true);
@@ -428,7 +446,7 @@ int launch_attention(const AtPlan &p, const int64_t *ptr, const int64_t *ind, co
 #undef TSAMD_AT_LAUNCH
   TSAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL((attention_fixup_kernel<T>), dim3((unsigned int)ceil_div(nchunks, (int64_t)kAtWaves)), block, 0,
-                     stream, ptr, oo, ll, (const A *)head_acc, (const A *)tail_acc, (const A *)head_ml,
+                     stream, c.rowptr, oo, ll, (const A *)head_acc, (const A *)tail_acc, (const A *)head_ml,
                      (const A *)tail_ml, (const int64_t *)head_seg, H, D, p.chunk, nchunks);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
@@ -540,18 +558,16 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
 }
 
 template <typename T, int MODE>
-int launch_attention_bw(const AtPlan &p, const int64_t *row, const int64_t *ptr, const int64_t *ind, const void *bias,
-                        int64_t bias_heads, const void *q, const void *k, const void *v, const void *out,
-                        const void *lse, const void *go, double scale, void *p_out, void *ds_out, int64_t nseg,
-                        int64_t H, int64_t D, int64_t E, hipStream_t stream) {
+int launch_attention_bw(const AtPlan &p, const AtCall &c) {
   using A = typename Traits<T>::acc_t;
-  const dim3 grid((unsigned int)ceil_div(E, (int64_t)kAtWaves * kWave)), block(kAtWaves * kWave);
+  const dim3 grid((unsigned int)ceil_div(c.E, (int64_t)kAtWaves * kWave)), block(kAtWaves * kWave);
 #define TSAMD_AT_BW(PACKED)                                                                                         \
-  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED, MODE>), grid, block, 0, stream, row, ptr, ind,                 \
-                     reinterpret_cast<const T *>(bias), bias_heads, reinterpret_cast<const T *>(q),                 \
-                     reinterpret_cast<const T *>(k), reinterpret_cast<const T *>(v), reinterpret_cast<const T *>(out), \
-                     reinterpret_cast<const A *>(lse), reinterpret_cast<const T *>(go), (A)scale,                   \
-                     reinterpret_cast<T *>(p_out), reinterpret_cast<T *>(ds_out), nseg, H, D, E, p.lg_lph, p.lg_hpp)
+  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED, MODE>), grid, block, 0, c.stream, c.row, c.rowptr, c.col,      \
+                     reinterpret_cast<const T *>(c.bias), c.bias_heads, reinterpret_cast<const T *>(c.sr),          \
+                     reinterpret_cast<const T *>(c.sc), reinterpret_cast<const T *>(c.v),                           \
+                     reinterpret_cast<const T *>(c.out), reinterpret_cast<const A *>(c.lse),                        \
+                     reinterpret_cast<const T *>(c.grad_out), (A)c.scalar, reinterpret_cast<T *>(c.p_out),          \
+                     reinterpret_cast<T *>(c.d_out), c.nseg, c.H, c.D, c.E, p.lg_lph, p.lg_hpp)
   if (p.generic) TSAMD_AT_BW(false); else TSAMD_AT_BW(true);
 #undef TSAMD_AT_BW
   TSAMD_LAUNCH_CHECK();
@@ -567,6 +583,64 @@ bool at_indexable(int dtype, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, i
   at_lanes(dtype, H, D, kAtFwHeads, &p);
   if (p.blocks > 65535) return false;  // column blocks are blockIdx.y
   return ceil_div(E, (int64_t)kAtWaves * kWave) <= lim;
+}
+
+// the status of a call the host can decide, or kAtProceed.  include/tsamd.h lists the cases in this order
+int at_check_sizes(const AtCall &c) {
+  if (c.nseg < 0 || c.nsrc < 0 || c.H < 0 || c.D < 0 || c.E < 0) return TSAMD_ERR_INVALID;
+  if (!is_float_dtype(c.dtype)) return TSAMD_ERR_UNSUPPORTED;
+  if (!at_indexable(c.dtype, c.nseg, c.nsrc, c.H, c.D, c.E)) return TSAMD_ERR_UNSUPPORTED;
+  if (c.bias && c.bias_heads != 1 && c.bias_heads != c.H) return TSAMD_ERR_INVALID;
+  return kAtProceed;
+}
+
+int at_check_forward(const AtCall &c) {
+  const int st = at_check_sizes(c);
+  if (st != kAtProceed) return st;
+  if (c.nseg * c.H * c.D == 0) return TSAMD_OK;  // out has no element
+  if (!c.out || !c.lse) return TSAMD_ERR_INVALID;
+  if (c.E > 0) {
+    if (c.nsrc == 0 || !c.rowptr || !c.col || !c.sr || !c.sc || !c.v) return TSAMD_ERR_INVALID;
+    if (!c.workspace || c.workspace_bytes < tsamd_attention_heads_workspace_bytes(c.dtype, c.H, c.D, c.E))
+      return TSAMD_ERR_WORKSPACE;
+  }
+  return kAtProceed;
+}
+
+int at_check_backward(const AtCall &c) {
+  const int st = at_check_sizes(c);
+  if (st != kAtProceed) return st;
+  if (c.E == 0 || c.H == 0) return TSAMD_OK;  // p and ds / dz have no element
+  if (c.D == 0) return TSAMD_ERR_INVALID;     // the forward defines no lse for D = 0
+  if (c.nseg == 0 || c.nsrc == 0 || !c.p_out || !c.d_out || !c.col || !c.sr || !c.sc || !c.v || !c.out || !c.lse ||
+      !c.grad_out || (!c.row && !c.rowptr))
+    return TSAMD_ERR_INVALID;
+  return kAtProceed;
+}
+
+// a_dst / a_src are element loads of any alignment: in kAtAdditive the route is decided by v, out, grad_out and D
+AtPlan at_call_plan(const AtCall &c, int max_heads) {
+  const bool dot = c.mode == kAtDot;
+  return at_plan(c.dtype, c.H, c.D, max_heads, dot ? c.sr : nullptr, dot ? c.sc : nullptr, c.v, c.out, c.grad_out);
+}
+
+int at_forward(const AtCall &c) {
+  const int st = at_check_forward(c);
+  if (st != kAtProceed) return st;
+  const AtPlan p = at_call_plan(c, kAtFwHeads);
+  return TSAMD_DISPATCH_FLOAT(c.dtype, [&]() -> int {
+    return c.mode == kAtDot ? launch_attention<scalar_t, kAtDot>(p, c) : launch_attention<scalar_t, kAtAdditive>(p, c);
+  });
+}
+
+int at_backward(const AtCall &c) {
+  const int st = at_check_backward(c);
+  if (st != kAtProceed) return st;
+  const AtPlan p = at_call_plan(c, kAtBwHeads);
+  return TSAMD_DISPATCH_FLOAT(c.dtype, [&]() -> int {
+    return c.mode == kAtDot ? launch_attention_bw<scalar_t, kAtDot>(p, c)
+                            : launch_attention_bw<scalar_t, kAtAdditive>(p, c);
+  });
 }
 
 }  // namespace
@@ -600,94 +674,43 @@ extern "C" size_t tsamd_attention_heads_workspace_bytes(int dtype, int64_t H, in
   return at_records(acc_size(dtype), p.chunk, H, D, E).bytes();
 }
 
+// ---- the four calls: a descriptor each.  The additive (GAT) pair runs the same kernels in MODE = kAtAdditive, a_dst
+// for the row operand, a_src for the column operand, the slope for the scalar -------------------------------------------
 extern "C" int tsamd_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
                                      int64_t bias_heads, const void *q, const void *k, const void *v, double scale,
                                      void *out, void *lse, int64_t nseg, int64_t nsrc, int64_t H, int64_t D,
-                                     int64_t E, void *workspace, size_t workspace_bytes, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
-  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
-  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
-  if (nseg * H * D == 0) return TSAMD_OK;  // out has no element
-  if (!out || !lse) return TSAMD_ERR_INVALID;
-  if (E > 0) {
-    if (nsrc == 0 || !rowptr || !col || !q || !k || !v) return TSAMD_ERR_INVALID;
-    if (!workspace || workspace_bytes < tsamd_attention_heads_workspace_bytes(dtype, H, D, E))
-      return TSAMD_ERR_WORKSPACE;
-  }
-  const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, q, k, v, out);
-  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention<scalar_t, kAtDot>(p, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nseg, H, D,
-                                              E, workspace, stream);
-  });
+                                     int64_t E, void *workspace, size_t workspace_bytes, void *stream) {
+  return at_forward({dtype, kAtDot, nullptr, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nullptr, nullptr,
+                     nullptr, nseg, nsrc, H, D, E, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)});
 }
 
-extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
-                                        const void *bias, int64_t bias_heads, const void *q, const void *k,
-                                        const void *v, const void *out, const void *lse, const void *grad_out,
-                                        double scale, void *p_out, void *ds_out, int64_t nseg, int64_t nsrc, int64_t H,
-                                        int64_t D, int64_t E, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
-  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
-  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
-  if (E == 0 || H == 0) return TSAMD_OK;  // p and ds have no element
-  if (D == 0) return TSAMD_ERR_INVALID;   // the forward defines no lse for D = 0
-  if (nseg == 0 || nsrc == 0 || !p_out || !ds_out || !col || !q || !k || !v || !out || !lse || !grad_out ||
-      (!row && !rowptr))
-    return TSAMD_ERR_INVALID;
-  const AtPlan p = at_plan(dtype, H, D, kAtBwHeads, q, k, v, out, grad_out);
-  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention_bw<scalar_t, kAtDot>(p, row, rowptr, col, bias, bias_heads, q, k, v, out, lse, grad_out,
-                                                 scale, p_out, ds_out, nseg, H, D, E, stream);
-  });
-}
-
-// ---- additive (GAT) scores: the same kernels in MODE = kAtAdditive, a_dst for q, a_src for k, the slope for scale -------
 extern "C" int tsamd_gat_attention_heads(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
                                          int64_t bias_heads, const void *a_dst, const void *a_src, const void *v,
                                          double negative_slope, void *out, void *lse, int64_t nseg, int64_t nsrc,
                                          int64_t H, int64_t D, int64_t E, void *workspace, size_t workspace_bytes,
-                                         void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
-  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
-  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
-  if (nseg * H * D == 0) return TSAMD_OK;  // out has no element
-  if (!out || !lse) return TSAMD_ERR_INVALID;
-  if (E > 0) {
-    if (nsrc == 0 || !rowptr || !col || !a_dst || !a_src || !v) return TSAMD_ERR_INVALID;
-    if (!workspace || workspace_bytes < tsamd_attention_heads_workspace_bytes(dtype, H, D, E))
-      return TSAMD_ERR_WORKSPACE;
-  }
-  const AtPlan p = at_plan(dtype, H, D, kAtFwHeads, nullptr, nullptr, v, out);  // a_dst / a_src: element loads
-  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention<scalar_t, kAtAdditive>(p, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope,
-                                                   out, lse, nseg, H, D, E, workspace, stream);
-  });
+                                         void *stream) {
+  return at_forward({dtype, kAtAdditive, nullptr, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope, out,
+                     lse, nullptr, nullptr, nullptr, nseg, nsrc, H, D, E, workspace, workspace_bytes,
+                     reinterpret_cast<hipStream_t>(stream)});
+}
+
+// out and lse are only read here
+extern "C" int tsamd_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                        const void *bias, int64_t bias_heads, const void *q, const void *k,
+                                        const void *v, const void *out, const void *lse, const void *grad_out,
+                                        double scale, void *p_out, void *ds_out, int64_t nseg, int64_t nsrc, int64_t H,
+                                        int64_t D, int64_t E, void *stream) {
+  return at_backward({dtype, kAtDot, row, rowptr, col, bias, bias_heads, q, k, v, scale, const_cast<void *>(out),
+                      const_cast<void *>(lse), grad_out, p_out, ds_out, nseg, nsrc, H, D, E, nullptr, 0,
+                      reinterpret_cast<hipStream_t>(stream)});
 }
 
 extern "C" int tsamd_gat_attention_heads_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
                                             const void *bias, int64_t bias_heads, const void *a_dst, const void *a_src,
                                             const void *v, const void *out, const void *lse, const void *grad_out,
                                             double negative_slope, void *p_out, void *dz_out, int64_t nseg,
-                                            int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (nseg < 0 || nsrc < 0 || H < 0 || D < 0 || E < 0) return TSAMD_ERR_INVALID;
-  if (!is_float_dtype(dtype)) return TSAMD_ERR_UNSUPPORTED;
-  if (!at_indexable(dtype, nseg, nsrc, H, D, E)) return TSAMD_ERR_UNSUPPORTED;
-  if (bias && bias_heads != 1 && bias_heads != H) return TSAMD_ERR_INVALID;
-  if (E == 0 || H == 0) return TSAMD_OK;  // p and dz have no element
-  if (D == 0) return TSAMD_ERR_INVALID;   // the forward defines no lse for D = 0
-  if (nseg == 0 || nsrc == 0 || !p_out || !dz_out || !col || !a_dst || !a_src || !v || !out || !lse || !grad_out ||
-      (!row && !rowptr))
-    return TSAMD_ERR_INVALID;
-  const AtPlan p = at_plan(dtype, H, D, kAtBwHeads, nullptr, nullptr, v, out, grad_out);
-  return TSAMD_DISPATCH_FLOAT(dtype, [&]() -> int {
-    return launch_attention_bw<scalar_t, kAtAdditive>(p, row, rowptr, col, bias, bias_heads, a_dst, a_src, v, out, lse,
-                                                      grad_out, negative_slope, p_out, dz_out, nseg, H, D, E, stream);
-  });
+                                            int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream) {
+  return at_backward({dtype, kAtAdditive, row, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope,
+                      const_cast<void *>(out), const_cast<void *>(lse), grad_out, p_out, dz_out, nseg, nsrc, H, D, E,
+                      nullptr, 0, reinterpret_cast<hipStream_t>(stream)});
 }

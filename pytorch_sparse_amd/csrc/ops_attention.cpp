@@ -90,7 +90,37 @@ Tensor spmm_heads(Tensor ptr, Tensor ind, OptTensor perm, OptTensor value, Tenso
   return out;
 }
 
-// the checks both fused operators share -> the bias made contiguous (undefined without one)
+// ---- the fused calls.  Dot-product and additive (GAT) scores differ in their operand checks, the names in the
+// messages and the C entry points; below those the two score operands go by neutral names: sr belongs to the rows
+// (q / a_dst), sc to the columns (k / a_src), the scalar is scale / negative_slope -------------------------------------
+struct Fused {
+  bool dot;
+  const char *like_name;  // the operand the messages compare with: q (= sr) or v
+  const char *fw, *bw;    // the C entry points; the operators carry these names without "tsamd_"
+};
+const Fused kDotScores = {true, "q", "tsamd_attention_heads", "tsamd_attention_heads_bw"};
+const Fused kGatScores = {false, "v", "tsamd_gat_attention_heads", "tsamd_gat_attention_heads_bw"};
+const char *op_name(const char *entry) { return entry + 6; }
+
+// the bias against the pattern and the operand `like` -> made contiguous (undefined without one)
+Tensor check_bias(const OptTensor &bias, int64_t E, int64_t H, const Tensor &like, const char *like_name) {
+  Tensor b;
+  if (bias.has_value()) {
+    b = bias.value();
+    check_gpu(b, "bias");
+    TORCH_CHECK(b.dim() == 1 || b.dim() == 2, "bias must be [nnz] or [nnz, heads], got ", b.dim(), " dimension(s)");
+    TORCH_CHECK(b.size(0) == E, "bias has ", b.size(0), " rows, the pattern has ", E, " entries");
+    TORCH_CHECK(b.dim() == 1 || b.size(1) == H, "bias has ", b.dim() == 2 ? b.size(1) : 1, " heads, ", like_name,
+                " has ", H);
+    TORCH_CHECK(b.scalar_type() == like.scalar_type(), "bias and ", like_name, " differ in dtype: ", b.scalar_type(),
+                " and ", like.scalar_type());
+    TORCH_CHECK(b.get_device() == like.get_device(), "bias and ", like_name, " must be on one device");
+    b = b.contiguous();
+  }
+  return b;
+}
+
+// the checks both dot-product operators share -> the bias
 Tensor check_attention(const Tensor &rowptr, const Tensor &col, const OptTensor &bias, const Tensor &q,
                        const Tensor &k, const Tensor &v) {
   check_index(rowptr, "rowptr");
@@ -108,98 +138,10 @@ Tensor check_attention(const Tensor &rowptr, const Tensor &col, const OptTensor 
   TORCH_CHECK(v.sizes() == k.sizes(), "v must have the shape of k, got ", v.sizes(), " and ", k.sizes());
   TORCH_CHECK(rowptr.numel() == q.size(0) + 1, "rowptr has ", rowptr.numel(), " elements, q has ", q.size(0),
               " rows");
-  Tensor b;
-  if (bias.has_value()) {
-    b = bias.value();
-    check_gpu(b, "bias");
-    const int64_t E = col.numel(), H = q.size(1);
-    TORCH_CHECK(b.dim() == 1 || b.dim() == 2, "bias must be [nnz] or [nnz, heads], got ", b.dim(), " dimension(s)");
-    TORCH_CHECK(b.size(0) == E, "bias has ", b.size(0), " rows, the pattern has ", E, " entries");
-    TORCH_CHECK(b.dim() == 1 || b.size(1) == H, "bias has ", b.dim() == 2 ? b.size(1) : 1, " heads, q has ", H);
-    TORCH_CHECK(b.scalar_type() == q.scalar_type(), "bias and q differ in dtype: ", b.scalar_type(), " and ",
-                q.scalar_type());
-    TORCH_CHECK(b.get_device() == q.get_device(), "bias and q must be on one device");
-    b = b.contiguous();
-  }
-  return b;
+  return check_bias(bias, col.numel(), q.size(1), q, "q");
 }
 
-// fused scores -> softmax over the row -> aggregation (csrc/attention.hip) -> (out [M, H, D], lse [M, H])
-std::tuple<Tensor, Tensor> attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor q, Tensor k, Tensor v,
-                                           double scale) {
-  Tensor b = check_attention(rowptr, col, bias, q, k, v);
-  const int64_t M = q.size(0), N = k.size(0), H = q.size(1), D = q.size(2), E = col.numel();
-  c10::hip::HIPGuard guard(q.get_device());
-  q = q.contiguous();
-  k = k.contiguous();
-  v = v.contiguous();
-  rowptr = rowptr.contiguous();
-  col = col.contiguous();
-  Tensor out = torch::empty({M, H, D}, q.options().requires_grad(false));
-  const auto acc = q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
-  Tensor lse = torch::empty({M, H}, q.options().dtype(acc).requires_grad(false));
-  if (out.numel() == 0) {  // D == 0: every score is its bias alone, nothing is aggregated
-    TORCH_CHECK(D > 0 || lse.numel() == 0, "attention_heads needs at least one feature per head");
-    return std::make_tuple(out, lse);
-  }
-  const int dt = dtype_code(q);
-  Tensor ws = workspace(tsamd_attention_heads_workspace_bytes(dt, H, D, E), q);
-  check_status(tsamd_attention_heads(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                     b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
-                                     q.data_ptr(), k.data_ptr(), v.data_ptr(), scale, out.data_ptr(), lse.data_ptr(),
-                                     M, N, H, D, E, ws.data_ptr(), (size_t)ws.numel(), current_stream(q)),
-               "tsamd_attention_heads");
-  return std::make_tuple(out, lse);
-}
-
-// p = e(s - lse[row]) and ds = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>) -> two [E, H] arrays
-std::tuple<Tensor, Tensor> attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias, Tensor q,
-                                              Tensor k, Tensor v, Tensor out, Tensor lse, Tensor grad_out,
-                                              double scale) {
-  Tensor b = check_attention(rowptr, col, bias, q, k, v);
-  if (row.has_value()) check_index(row.value(), "row");
-  check_heads_operand(out, "out");
-  check_heads_operand(grad_out, "grad_out");
-  check_gpu(lse, "lse");
-  const int64_t M = q.size(0), N = k.size(0), H = q.size(1), D = q.size(2), E = col.numel();
-  TORCH_CHECK(out.sizes() == q.sizes(), "out must have the shape of q, got ", out.sizes(), " and ", q.sizes());
-  TORCH_CHECK(grad_out.sizes() == q.sizes(), "grad_out must have the shape of q, got ", grad_out.sizes(), " and ",
-              q.sizes());
-  TORCH_CHECK(out.scalar_type() == q.scalar_type() && grad_out.scalar_type() == q.scalar_type(),
-              "out, grad_out and q differ in dtype: ", out.scalar_type(), ", ", grad_out.scalar_type(), " and ",
-              q.scalar_type());
-  const auto acc = q.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
-  TORCH_CHECK(lse.dim() == 2 && lse.size(0) == M && lse.size(1) == H && lse.scalar_type() == acc,
-              "lse must be [rows, heads] of ", acc, ", got ", lse.sizes(), " of ", lse.scalar_type());
-  TORCH_CHECK(out.get_device() == q.get_device() && grad_out.get_device() == q.get_device() &&
-                  lse.get_device() == q.get_device(),
-              "out, lse, grad_out and q must be on one device");
-  TORCH_CHECK(!row.has_value() || row.value().numel() == E, "row and col differ in length");
-  TORCH_CHECK(D > 0 || E == 0 || H == 0, "attention_heads_bw needs at least one feature per head");
-  c10::hip::HIPGuard guard(q.get_device());
-  q = q.contiguous();
-  k = k.contiguous();
-  v = v.contiguous();
-  out = out.contiguous();
-  lse = lse.contiguous();
-  grad_out = grad_out.contiguous();
-  rowptr = rowptr.contiguous();
-  col = col.contiguous();
-  Tensor r = row.has_value() ? row.value().contiguous() : Tensor();
-  Tensor p = torch::empty({E, H}, q.options().requires_grad(false));
-  Tensor ds = torch::empty({E, H}, q.options().requires_grad(false));
-  if (p.numel() == 0) return std::make_tuple(p, ds);
-  check_status(tsamd_attention_heads_bw(dtype_code(q), row.has_value() ? r.data_ptr<int64_t>() : nullptr,
-                                        rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                        b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
-                                        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                        grad_out.data_ptr(), scale, p.data_ptr(), ds.data_ptr(), M, N, H, D, E,
-                                        current_stream(q)),
-               "tsamd_attention_heads_bw");
-  return std::make_tuple(p, ds);
-}
-
-// the checks both additive operators share -> the bias made contiguous (undefined without one)
+// the checks both additive operators share -> the bias
 Tensor check_gat_attention(const Tensor &rowptr, const Tensor &col, const OptTensor &bias, const Tensor &a_dst,
                            const Tensor &a_src, const Tensor &v, double negative_slope) {
   check_index(rowptr, "rowptr");
@@ -221,81 +163,73 @@ Tensor check_gat_attention(const Tensor &rowptr, const Tensor &col, const OptTen
   TORCH_CHECK(rowptr.numel() == a_dst.size(0) + 1, "rowptr has ", rowptr.numel(), " elements, a_dst has ",
               a_dst.size(0), " rows");
   TORCH_CHECK(std::isfinite(negative_slope), "negative_slope must be finite, got ", negative_slope);
-  Tensor b;
-  if (bias.has_value()) {
-    b = bias.value();
-    check_gpu(b, "bias");
-    const int64_t E = col.numel(), H = v.size(1);
-    TORCH_CHECK(b.dim() == 1 || b.dim() == 2, "bias must be [nnz] or [nnz, heads], got ", b.dim(), " dimension(s)");
-    TORCH_CHECK(b.size(0) == E, "bias has ", b.size(0), " rows, the pattern has ", E, " entries");
-    TORCH_CHECK(b.dim() == 1 || b.size(1) == H, "bias has ", b.dim() == 2 ? b.size(1) : 1, " heads, v has ", H);
-    TORCH_CHECK(b.scalar_type() == v.scalar_type(), "bias and v differ in dtype: ", b.scalar_type(), " and ",
-                v.scalar_type());
-    TORCH_CHECK(b.get_device() == v.get_device(), "bias and v must be on one device");
-    b = b.contiguous();
-  }
-  return b;
+  return check_bias(bias, col.numel(), v.size(1), v, "v");
 }
 
-// fused additive (GAT) scores -> softmax over the row -> aggregation (csrc/attention.hip)
-// -> (out [M, H, D], lse [M, H])
-std::tuple<Tensor, Tensor> gat_attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor a_dst, Tensor a_src,
-                                               Tensor v, double negative_slope) {
-  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
-  const int64_t M = a_dst.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
+// fused scores -> softmax over the row -> aggregation (csrc/attention.hip) -> (out [M, H, D], lse [M, H]); the operands
+// have passed their checker, b is its bias
+std::tuple<Tensor, Tensor> fused_forward(const Fused &m, Tensor rowptr, Tensor col, const Tensor &b, Tensor sr,
+                                         Tensor sc, Tensor v, double scalar) {
+  const int64_t M = sr.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
   c10::hip::HIPGuard guard(v.get_device());
-  a_dst = a_dst.contiguous();
-  a_src = a_src.contiguous();
+  sr = sr.contiguous();
+  sc = sc.contiguous();
   v = v.contiguous();
   rowptr = rowptr.contiguous();
   col = col.contiguous();
   Tensor out = torch::empty({M, H, D}, v.options().requires_grad(false));
   const auto acc = v.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
   Tensor lse = torch::empty({M, H}, v.options().dtype(acc).requires_grad(false));
-  if (out.numel() == 0) {
-    TORCH_CHECK(D > 0 || lse.numel() == 0, "gat_attention_heads needs at least one feature per head");
+  if (out.numel() == 0) {  // D == 0: every score would be its bias alone, nothing is aggregated
+    TORCH_CHECK(D > 0 || lse.numel() == 0, op_name(m.fw), " needs at least one feature per head");
     return std::make_tuple(out, lse);
   }
   const int dt = dtype_code(v);
   Tensor ws = workspace(tsamd_attention_heads_workspace_bytes(dt, H, D, E), v);
-  check_status(tsamd_gat_attention_heads(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                         b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
-                                         a_dst.data_ptr(), a_src.data_ptr(), v.data_ptr(), negative_slope,
-                                         out.data_ptr(), lse.data_ptr(), M, N, H, D, E, ws.data_ptr(),
-                                         (size_t)ws.numel(), current_stream(v)),
-               "tsamd_gat_attention_heads");
+  const auto call = m.dot ? tsamd_attention_heads : tsamd_gat_attention_heads;
+  check_status(call(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), b.defined() ? b.data_ptr() : nullptr,
+                    b.defined() && b.dim() == 2 ? H : 1, sr.data_ptr(), sc.data_ptr(), v.data_ptr(), scalar,
+                    out.data_ptr(), lse.data_ptr(), M, N, H, D, E, ws.data_ptr(), (size_t)ws.numel(),
+                    current_stream(v)),
+               m.fw);
   return std::make_tuple(out, lse);
 }
 
-// p = e(s - lse[row]) and dz = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>) * (z > 0 ? 1 : negative_slope)
-// -> two [E, H] arrays
-std::tuple<Tensor, Tensor> gat_attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias,
-                                                  Tensor a_dst, Tensor a_src, Tensor v, Tensor out, Tensor lse,
-                                                  Tensor grad_out, double negative_slope) {
-  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
+// p = e(s - lse[row]) and ds = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>), for the additive scores
+// dz = ds * (z > 0 ? 1 : negative_slope) in its place -> two [E, H] arrays
+std::tuple<Tensor, Tensor> fused_backward(const Fused &m, const OptTensor &row, Tensor rowptr, Tensor col,
+                                          const Tensor &b, Tensor sr, Tensor sc, Tensor v, Tensor out, Tensor lse,
+                                          Tensor grad_out, double scalar) {
   if (row.has_value()) check_index(row.value(), "row");
   check_heads_operand(out, "out");
   check_heads_operand(grad_out, "grad_out");
   check_gpu(lse, "lse");
-  const int64_t M = a_dst.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
-  TORCH_CHECK(out.dim() == 3 && out.size(0) == M && out.size(1) == H && out.size(2) == D,
-              "out must be [rows, heads, features] = [", M, ", ", H, ", ", D, "], got ", out.sizes());
-  TORCH_CHECK(grad_out.sizes() == out.sizes(), "grad_out must have the shape of out, got ", grad_out.sizes(), " and ",
-              out.sizes());
-  TORCH_CHECK(out.scalar_type() == v.scalar_type() && grad_out.scalar_type() == v.scalar_type(),
-              "out, grad_out and v differ in dtype: ", out.scalar_type(), ", ", grad_out.scalar_type(), " and ",
-              v.scalar_type());
-  const auto acc = v.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
+  const int64_t M = sr.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
+  const Tensor &like = m.dot ? sr : v;
+  if (m.dot) {
+    TORCH_CHECK(out.sizes() == sr.sizes(), "out must have the shape of q, got ", out.sizes(), " and ", sr.sizes());
+    TORCH_CHECK(grad_out.sizes() == sr.sizes(), "grad_out must have the shape of q, got ", grad_out.sizes(), " and ",
+                sr.sizes());
+  } else {
+    TORCH_CHECK(out.dim() == 3 && out.size(0) == M && out.size(1) == H && out.size(2) == D,
+                "out must be [rows, heads, features] = [", M, ", ", H, ", ", D, "], got ", out.sizes());
+    TORCH_CHECK(grad_out.sizes() == out.sizes(), "grad_out must have the shape of out, got ", grad_out.sizes(),
+                " and ", out.sizes());
+  }
+  TORCH_CHECK(out.scalar_type() == like.scalar_type() && grad_out.scalar_type() == like.scalar_type(),
+              "out, grad_out and ", m.like_name, " differ in dtype: ", out.scalar_type(), ", ", grad_out.scalar_type(),
+              " and ", like.scalar_type());
+  const auto acc = like.scalar_type() == at::kDouble ? at::kDouble : at::kFloat;
   TORCH_CHECK(lse.dim() == 2 && lse.size(0) == M && lse.size(1) == H && lse.scalar_type() == acc,
               "lse must be [rows, heads] of ", acc, ", got ", lse.sizes(), " of ", lse.scalar_type());
-  TORCH_CHECK(out.get_device() == v.get_device() && grad_out.get_device() == v.get_device() &&
-                  lse.get_device() == v.get_device(),
-              "out, lse, grad_out and v must be on one device");
+  TORCH_CHECK(out.get_device() == like.get_device() && grad_out.get_device() == like.get_device() &&
+                  lse.get_device() == like.get_device(),
+              "out, lse, grad_out and ", m.like_name, " must be on one device");
   TORCH_CHECK(!row.has_value() || row.value().numel() == E, "row and col differ in length");
-  TORCH_CHECK(D > 0 || E == 0 || H == 0, "gat_attention_heads_bw needs at least one feature per head");
+  TORCH_CHECK(D > 0 || E == 0 || H == 0, op_name(m.bw), " needs at least one feature per head");
   c10::hip::HIPGuard guard(v.get_device());
-  a_dst = a_dst.contiguous();
-  a_src = a_src.contiguous();
+  sr = sr.contiguous();
+  sc = sc.contiguous();
   v = v.contiguous();
   out = out.contiguous();
   lse = lse.contiguous();
@@ -304,16 +238,41 @@ std::tuple<Tensor, Tensor> gat_attention_heads_bw(OptTensor row, Tensor rowptr, 
   col = col.contiguous();
   Tensor r = row.has_value() ? row.value().contiguous() : Tensor();
   Tensor p = torch::empty({E, H}, v.options().requires_grad(false));
-  Tensor dz = torch::empty({E, H}, v.options().requires_grad(false));
-  if (p.numel() == 0) return std::make_tuple(p, dz);
-  check_status(tsamd_gat_attention_heads_bw(dtype_code(v), row.has_value() ? r.data_ptr<int64_t>() : nullptr,
-                                            rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(),
-                                            b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
-                                            a_dst.data_ptr(), a_src.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                            lse.data_ptr(), grad_out.data_ptr(), negative_slope, p.data_ptr(),
-                                            dz.data_ptr(), M, N, H, D, E, current_stream(v)),
-               "tsamd_gat_attention_heads_bw");
-  return std::make_tuple(p, dz);
+  Tensor d = torch::empty({E, H}, v.options().requires_grad(false));
+  if (p.numel() == 0) return std::make_tuple(p, d);
+  const auto call = m.dot ? tsamd_attention_heads_bw : tsamd_gat_attention_heads_bw;
+  check_status(call(dtype_code(v), row.has_value() ? r.data_ptr<int64_t>() : nullptr, rowptr.data_ptr<int64_t>(),
+                    col.data_ptr<int64_t>(), b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
+                    sr.data_ptr(), sc.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(),
+                    scalar, p.data_ptr(), d.data_ptr(), M, N, H, D, E, current_stream(v)),
+               m.bw);
+  return std::make_tuple(p, d);
+}
+
+std::tuple<Tensor, Tensor> attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor q, Tensor k, Tensor v,
+                                           double scale) {
+  Tensor b = check_attention(rowptr, col, bias, q, k, v);
+  return fused_forward(kDotScores, rowptr, col, b, q, k, v, scale);
+}
+
+std::tuple<Tensor, Tensor> attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias, Tensor q,
+                                              Tensor k, Tensor v, Tensor out, Tensor lse, Tensor grad_out,
+                                              double scale) {
+  Tensor b = check_attention(rowptr, col, bias, q, k, v);
+  return fused_backward(kDotScores, row, rowptr, col, b, q, k, v, out, lse, grad_out, scale);
+}
+
+std::tuple<Tensor, Tensor> gat_attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor a_dst, Tensor a_src,
+                                               Tensor v, double negative_slope) {
+  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
+  return fused_forward(kGatScores, rowptr, col, b, a_dst, a_src, v, negative_slope);
+}
+
+std::tuple<Tensor, Tensor> gat_attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias,
+                                                  Tensor a_dst, Tensor a_src, Tensor v, Tensor out, Tensor lse,
+                                                  Tensor grad_out, double negative_slope) {
+  Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
+  return fused_backward(kGatScores, row, rowptr, col, b, a_dst, a_src, v, out, lse, grad_out, negative_slope);
 }
 
 }  // namespace
