@@ -798,6 +798,20 @@ int tsamd_sort_rank_mode(int set);
  * decided on the device (a bucket beyond `cap` falls back).  TSAMD_ERR_UNSUPPORTED where the sorts refuse the sizes,
  * TSAMD_ERR_INVALID for negative sizes, a value_bytes other than 0 / 4 / 8 or out == NULL. */
 int tsamd_sort_route(int64_t E, int64_t M, int64_t N, int value_bytes, int coalesce, int64_t out[16]);
+/* tsamd_sort_header: where a sort of route 2 (and route 0 beyond the one-launch sizes) leaves what it decided on the
+ * device, for a caller that owns the workspace and reads it back after the call -- host arithmetic only, from the carve
+ * the driver itself uses.  The header is an array of 64-bit words inside the workspace of the sorts above
+ * (coalesce = 0, tsamd_sort_coo_workspace_bytes) or of tsamd_sort_coalesce* (coalesce = 1,
+ * tsamd_sort_coalesce_workspace_bytes), zeroed by the call's first fill:
+ *   out[0] byte offset of the header in that workspace
+ *   out[1] word index of the probe's #descents (probing sorts with a bucket plan, and the counts of every probing sort)
+ *   out[2] word index of the fast word: 1 = the bucket path sorted this input (and, for a compacting sort, wrote the
+ *          compacted outputs itself), 0 = the one-sweep passes did -- a bucket beyond the plan's capacity, an input
+ *          without descents, no bucket plan, or an id that does not fit the bit width of its size (an untrusted COO
+ *          never reaches the bucket kernels)
+ *   out[3] word index of the error word (a look-back that gave up; the launch is aborted then)
+ * The one-launch sort (route 1) has no header.  TSAMD_ERR_INVALID for E < 0 or out == NULL. */
+int tsamd_sort_header(int64_t E, int coalesce, int64_t out[4]);
 size_t tsamd_sort_coo_workspace_bytes(int64_t E);
 int tsamd_sort_coo(const int64_t *row, const int64_t *col, int64_t E, int64_t M,
                    int64_t N, int64_t *row_out, int64_t *col_out, int64_t *perm_out,

@@ -28,7 +28,7 @@ SYMBOLS = [
     'tsamd_spmm_minmax_bw_workspace_bytes', 'tsamd_spmm_minmax_bw',
     'tsamd_spmm_minmax_bw_csc_workspace_bytes', 'tsamd_spmm_minmax_bw_csc', 'tsamd_spmm_minmax_bw_route',
     'tsamd_ind2ptr', 'tsamd_ptr2ind',
-    'tsamd_coo_order', 'tsamd_coo_check', 'tsamd_sort_rank_mode', 'tsamd_sort_route', 'tsamd_sort_coalesce_workspace_bytes', 'tsamd_sort_coalesce', 'tsamd_sort_coalesce_reduce', 'tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo', 'tsamd_sort_coo_auto', 'tsamd_sort_coo_probed', 'tsamd_sort_coo_values',
+    'tsamd_coo_order', 'tsamd_coo_check', 'tsamd_sort_rank_mode', 'tsamd_sort_route', 'tsamd_sort_header', 'tsamd_sort_coalesce_workspace_bytes', 'tsamd_sort_coalesce', 'tsamd_sort_coalesce_reduce', 'tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo', 'tsamd_sort_coo_auto', 'tsamd_sort_coo_probed', 'tsamd_sort_coo_values',
     'tsamd_coalesce_workspace_bytes', 'tsamd_coalesce_index', 'tsamd_segment_reduce',
     'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
     'tsamd_segment_softmax_route', 'tsamd_segment_softmax_workspace_bytes', 'tsamd_segment_softmax', 'tsamd_segment_softmax_bw',
@@ -99,6 +99,8 @@ def lib():
         L.tsamd_spmm_minmax_records_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_segment_softmax_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_sort_coo_workspace_bytes.restype = ctypes.c_size_t
+        L.tsamd_sort_coalesce_workspace_bytes.restype = ctypes.c_size_t
         i64, vp, i64p = ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)
         L.tsamd_sddmm_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, i64p]
         L.tsamd_sddmm_heads.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, i64, i64, i64, i64, i64, vp]

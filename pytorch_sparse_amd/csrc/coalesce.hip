@@ -360,6 +360,10 @@ extern "C" size_t tsamd_sort_coalesce_workspace_bytes(int64_t E) {
 }
 
 namespace {
+// what lies in front of the sort's own workspace in the workspace of a compacting call (sort_coalesce_impl)
+size_t sort_coalesce_pre_zero(int64_t E) {
+  return align_up(sizeof(unsigned long long) * kSortCoalesceStatusWords, 256) + tsamd_coalesce_workspace_bytes(E);
+}
 // reduce < 0: tsamd_sort_coalesce (counts has 3 entries); else tsamd_sort_coalesce_reduce (4 entries, value_u)
 int sort_coalesce_impl(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
                        int64_t *row_tmp, int64_t *col_tmp, int64_t *row_u, int64_t *col_u, int64_t *seg_ptr,
@@ -384,7 +388,7 @@ int sort_coalesce_impl(const int64_t *row, const int64_t *col, int64_t E, int64_
   unsigned long long *status = reinterpret_cast<unsigned long long *>(wsp);
   void *co_ws = wsp + align_up(sizeof(unsigned long long) * kSortCoalesceStatusWords, 256);
   const size_t co_bytes = tsamd_coalesce_workspace_bytes(E);
-  const size_t pre_zero = align_up(sizeof(unsigned long long) * kSortCoalesceStatusWords, 256) + co_bytes;
+  const size_t pre_zero = sort_coalesce_pre_zero(E);
   void *sort_ws = wsp + pre_zero;
   SortCoalesce sc{row_u, col_u, seg_ptr, counts + 2, status};
   sc.pre_zero_bytes = pre_zero;
@@ -422,6 +426,13 @@ int sort_coalesce_impl(const int64_t *row, const int64_t *col, int64_t E, int64_
   return TSAMD_OK;
 }
 }  // namespace
+
+extern "C" int tsamd_sort_header(int64_t E, int coalesce, int64_t out[4]) {
+  if (E < 0 || !out) return TSAMD_ERR_INVALID;
+  sort_header_words(E, out);
+  if (coalesce) out[0] += (int64_t)sort_coalesce_pre_zero(E);
+  return TSAMD_OK;
+}
 
 extern "C" int tsamd_sort_coalesce(const int64_t *row, const int64_t *col, int64_t E, int64_t M, int64_t N,
                                    int64_t *row_tmp, int64_t *col_tmp, int64_t *row_u, int64_t *col_u, int64_t *seg_ptr,

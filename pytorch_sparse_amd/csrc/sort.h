@@ -37,6 +37,15 @@ struct SortCoalesce {
 };
 constexpr int kSortCoalesceStatusWords = 1 << 14;
 const unsigned long long *sort_fast_flag(void *workspace, int64_t E);
+// {byte offset of the header in the sort's workspace, word index of #descents, of the fast word, of the error word}
+// (tsamd_sort_header, coalesce.hip, adds what lies in front of the sort's workspace in a compacting call)
+void sort_header_words(int64_t E, int64_t out[4]);
+// Untrusted ids: every kernel behind sort_coo_run stays inside its buffers for ANY 64-bit row / col (the constructor
+// enqueues the sort before its range check is read back).  sort_build_kernel keeps an id beyond its bit width out of
+// the bucket histogram and bucket_plan_kernel then leaves the fast word at 0: such an input is sorted by the one-sweep
+// passes, whose positions come from masked digits and ranks alone (sort.hip, UNTRUSTED IDS).  Its outputs mean nothing
+// but lie inside their arrays, perm_out is a permutation, a riding value is value[perm_out], and counts[2..3] of a
+// range-checking probe are the unsigned maxima.
 
 // What decides whether the input is ordered at all -- on the device, without a host sync:
 enum class SortOrder {

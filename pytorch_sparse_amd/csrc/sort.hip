@@ -76,7 +76,8 @@ constexpr int kMaxPasses = 8;
 
 // workspace header (zeroed by the one memset of a sort): 64 words
 constexpr int kHdrDescents = 0, kHdrDups = 1, kHdrError = 2, kHdrMaxRow = 3, kHdrMaxCol = 4;
-constexpr int kHdrFast = 5;  // 1 = the bucket path sorts this input (decided by the build kernel's last workgroup)
+constexpr int kHdrFast = 5;  // 1 = the bucket path sorts this input (decided by bucket_plan_kernel)
+constexpr int kHdrWild = 6;  // != 0: some id does not fit its bit width (build kernel, bucket plans only): never the bucket path
 [[maybe_unused]] constexpr int kHdrTicket = 8;  // ticket[kMaxPasses], -DTSAMD_SORT_TICKET=1 only
 constexpr int kHdrWords = 64;
 
@@ -113,6 +114,20 @@ int bits_for(int64_t n) {  // bits needed for ids in [0, n)
 //   offsets and DECIDES: every bucket <= the LDS capacity -> hdr[kHdrFast] = 1 and the scatter + bucket-sort kernels
 //   run while the one-sweep passes return at once; otherwise (power-law rows, heavy duplication over few keys, ...)
 //   the two bucket kernels return at once and the one-sweep passes sort as before.  No host sync either way.
+//
+// UNTRUSTED IDS.  The constructor enqueues this sort before it has read its range check back (storage.py), so every
+// kernel here must stay inside its buffers for ANY 64-bit row / col.  The bucket kernels index LDS counters and the
+// bucket offsets with the bucket id, which is < nb only while every id fits its bit width (row < 2^row_bits,
+// col < 2^col_bits, as unsigned numbers; an id that is out of range but inside the width -- row 511 of 300 -- gives an
+// ordinary bucket id).  sort_build_kernel enforces that: an entry with an id beyond its width ("wild": too large, or
+// negative) is left out of the bucket histogram and raises hdr[kHdrWild], and bucket_plan_kernel never raises
+// hdr[kHdrFast] then, so neither bucket kernel ever sees a wild id.  The one-sweep passes then sort the input, and they
+// are safe for any word: every pass masks its digit to 8 bits; the digit histograms are taken from the same bits of the
+// same word the passes read (packed words lose the key's bits above 64 - idx_bits in `key << idx_bits`, never the
+// idx_bits position bits below), so every digit's run has exactly the room the histogram gave it; an output slot is
+// that run's base plus a rank; and the last pass gathers a riding value through the position bits / the position
+// payload, which are < E by construction.  The decoded ids of such a sort mean nothing (the caller throws them away);
+// the permutation is still a permutation and counts[2..3] still report the unsigned maxima.
 // ---------------------------------------------------------------------------
 constexpr int kBkMaxBits = 11;                   // buckets one scatter level separates (LDS counters of a tile)
 constexpr int kBkMaxBuckets = 1 << kBkMaxBits;
@@ -180,6 +195,11 @@ __global__ __launch_bounds__(kBuildThreads) void sort_build_kernel(
   __syncthreads();
   unsigned int desc = 0, dup = 0;
   unsigned long long mr = 0, mc = 0;  // probe == 2: the range check's maxima (unsigned: a negative id reads as huge)
+  bool wild = false;                  // bucket plans: an id of this thread does not fit its bit width
+  // wave-uniform masks (scalar registers; per entry they cost ANDs, where 64-bit shifts by a run-time count cost more):
+  // the bits of an id beyond its width (both widths are <= 63: the shifts are defined), and the key bits a word holds
+  const unsigned long long row_wild_mask = ~0ull << (L.key_bits - L.col_bits), col_wild_mask = ~0ull << L.col_bits;
+  const unsigned long long word_key_mask = L.packed ? ~0ull >> L.idx_bits : ~0ull;
   const int lane = (int)(threadIdx.x & 63);
   constexpr int kB = 4;  // entries per thread and step: the loads of a step are all in flight together
   for (int64_t base = (int64_t)blockIdx.x * (kBuildThreads * kB); base < n; base += (int64_t)gridDim.x * (kBuildThreads * kB)) {
@@ -225,8 +245,12 @@ __global__ __launch_bounds__(kBuildThreads) void sort_build_kernel(
           dup += (r[u] == pr) && (c[u] == pc);
         }
       }
+      // the digits as the passes will read them: a packed word keeps the low 64 - idx_bits bits of the key (all of them
+      // for ids inside their widths; a wild id may reach above, and a histogram that counted the lost bits would hand
+      // the passes runs of the wrong sizes)
+      const unsigned long long hkey = key & word_key_mask;
       for (int p = 0; p < hist_passes; ++p) {
-        const unsigned int d = (unsigned int)(key >> (p * kRadixBits)) & (kRadix - 1);
+        const unsigned int d = (unsigned int)(hkey >> (p * kRadixBits)) & (kRadix - 1);
         // the high digits of a power-law matrix take a handful of values: one add per wave when all lanes agree
         const unsigned int d0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)d);
         const unsigned long long act = __ballot(ok[u]);
@@ -237,13 +261,20 @@ __global__ __launch_bounds__(kBuildThreads) void sort_build_kernel(
         }
       }
       if (B.on) {
+        // ids inside their bit widths give b < B.nb (UNTRUSTED IDS above); any other entry is not counted -- no index
+        // beyond the histogram reaches LDS -- and takes the bucket path away from the whole input
+        // (a width of 0 bits admits the id 0 alone)
+        const bool fit = ok[u] && (((unsigned long long)r[u] & row_wild_mask) | ((unsigned long long)c[u] & col_wild_mask)) == 0ull;
+        wild |= ok[u] && !fit;
         const unsigned int b = B.strip ? (unsigned int)(key >> B.kshift)
                                        : (unsigned int)(((key << L.idx_bits) | (unsigned long long)i) >> B.shift);
         const unsigned int b0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)b);
-        const unsigned long long act = __ballot(ok[u]);
-        if (__ballot(ok[u] && b == b0) == act) {
+        const unsigned long long act = __ballot(fit);
+        if (__ballot(fit && b == b0) == act) {
+          // (lane 0 may itself hold a wild entry: b0 is used only when every counted lane agrees with it, and then
+          // one of them is a fitting entry's id)
           if (lane == 0 && act) atomicAdd(&bcnt[b0], (unsigned int)__popcll(act));
-        } else if (ok[u]) {
+        } else if (fit) {
           atomicAdd(&bcnt[b], 1u);
         }
       }
@@ -296,6 +327,10 @@ __global__ __launch_bounds__(kBuildThreads) void sort_build_kernel(
     }
   }
   if (!B.on) return;
+  // a wild id: one plain store per wave that saw one, all of the same value into the zeroed header, read by the plan
+  // kernel behind the kernel boundary (not a slot of wgstat: nothing is written at all for a valid input, so the word
+  // is no hot address where speed matters)
+  if (__ballot(wild) != 0ull && lane == 0) hdr[kHdrWild] = 1ull;
   // bucket histogram -> global (bucket_plan_kernel turns it into offsets and decides the route)
   // (kBkHistCopies copies of the histogram, one per residue of the workgroup id: 512 workgroups adding to the same
   // 128 cache lines queued for ~150 us on the lines' atomic units; 16 adds per line and copy do not)
@@ -402,6 +437,9 @@ __global__ __launch_bounds__(kBuildThreads) void bucket_plan_kernel(
     bool fast = gmx <= (unsigned int)B.cap;
     // an input without descents is not sorted at all (the passes' last kernel writes the copy + identity)
     if (probe && hdr[kHdrDescents] == 0ull) fast = false;
+    // an id beyond its bit width (UNTRUSTED IDS above): the histogram left it out, the offsets above add up to fewer
+    // than n entries and nobody may use them -- the one-sweep passes sort this input
+    if (hdr[kHdrWild] != 0ull) fast = false;
     hdr[kHdrFast] = fast ? 1ull : 0ull;
   }
 }
@@ -1713,6 +1751,7 @@ struct SortWs {
   unsigned int *bhist, *boff, *cursor, *cursor1;
   unsigned long long *wgstat;  // [kBuildMaxWgs][4]: the probe's per-workgroup results (with a bucket plan)
   size_t zero_bytes;  // hdr + hist + tile_state (+ the used part of bhist) are contiguous: one memset
+  size_t hdr_off;     // byte offset of hdr in the workspace
 };
 
 size_t carve_sort(void *base, int64_t E, SortWs *ws) {
@@ -1726,6 +1765,7 @@ size_t carve_sort(void *base, int64_t E, SortWs *ws) {
     return r;
   };
   SortWs w;
+  w.hdr_off = off;
   w.hdr = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * kHdrWords));
   w.hist = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * kMaxPasses * kRadix));
   w.tile_state = reinterpret_cast<unsigned long long *>(take(sizeof(unsigned long long) * ntiles * kRadix));
@@ -1815,6 +1855,15 @@ const unsigned long long *sort_fast_flag(void *workspace, int64_t E) {
   SortWs ws;
   carve_sort(workspace, E, &ws);
   return ws.hdr + kHdrFast;
+}
+
+void sort_header_words(int64_t E, int64_t out[4]) {
+  SortWs ws;
+  carve_sort(nullptr, E, &ws);
+  out[0] = (int64_t)ws.hdr_off;
+  out[1] = kHdrDescents;
+  out[2] = kHdrFast;
+  out[3] = kHdrError;
 }
 
 bool sort_coo_supported(int64_t E, int64_t M, int64_t N) {

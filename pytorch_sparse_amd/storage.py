@@ -118,7 +118,11 @@ class SparseStorage(object):
         # Both sizes given, unsorted COO, no caller caches to preserve: the check, the device-decided sort and the
         # gather of the values are ENQUEUED back to back and the check's four words are read afterwards -- the one
         # read-back no longer sits between the probe and the sort (an out-of-range id is still reported, after a
-        # sort whose result is then thrown away; ind2ptr clamps the ids it fills with to [0, M], csrc/convert.hip)
+        # sort whose result is then thrown away).  The contract that makes this safe: every kernel behind the sort
+        # stays inside its buffers for ANY 64-bit id -- sort_build_kernel (csrc/sort.hip, UNTRUSTED IDS) keeps an input
+        # with an id beyond the bit width of its size, or a negative one, off the bucket path, whose kernels index by
+        # such ids; the one-sweep passes place entries by masked digits and ranks alone -- and ind2ptr clamps the ids
+        # it fills with to [0, M] (csrc/convert.hip)
         presorted_row: Optional[Tensor] = None
         presorted_col: Optional[Tensor] = None
         presorted_value: Optional[Tensor] = None

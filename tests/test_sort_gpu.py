@@ -408,14 +408,17 @@ def test_fused_compaction(dev, ops, E):
     assert np.array_equal(seg[:k + 1].cpu().numpy(), np.append(pos, E))
 
 
-@pytest.mark.parametrize('E', [500, 20000])
+@pytest.mark.parametrize('E', [500, 20000, 131072, (1 << 20) + 1])
 def test_constructor_rejects_out_of_range_and_negative_ids(dev, E):
     """The enqueue-before-check constructor sorts an untrusted COO before its range assert fires (memory-safe:
-    positions come from ranks); the assert must still fire -- for ids >= the size and for negative ids (read as
-    unsigned maxima) -- on the one-launch path (E <= 8192) and on the general path."""
+    positions come from ranks, and an id beyond its bit width keeps the input off the bucket path --
+    tests/test_sort_device_routes_gpu.py); the assert must still fire -- for ids >= the size and for negative ids (read
+    as unsigned maxima) -- on the one-launch path (E <= 8192), on the one-sweep passes and with a bucket plan: full
+    words at E = 2^17 and stripped keys at 2^20 + 1 entries of a 2^22 x 2^22 matrix (where `m` and `n` themselves are
+    the first ids beyond the width)."""
     import pytorch_sparse_amd as ts
     g = torch.Generator().manual_seed(E)
-    m, n = 300, 200
+    m, n = (1 << 22, 1 << 22) if E == (1 << 20) + 1 else (300, 200)
     row = torch.randint(0, m, (E, ), generator=g)
     col = torch.randint(0, n, (E, ), generator=g)
     val = torch.rand(E, generator=g)

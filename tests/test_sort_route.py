@@ -128,6 +128,20 @@ def test_route_refuses_what_the_sorts_refuse():
     assert L.tsamd_sort_route(i64((1 << 32) - 1), i64(4), i64(4), 0, 0, out) == 0
 
 
+def test_sort_header_location():
+    """tsamd_sort_header: the header opens the sort's own workspace; in the workspace of tsamd_sort_coalesce* the
+    2^14 status words of the compacting bucket sort and the compaction kernel's state (8 + ceil(E / 2048) words, rounded
+    up to 256 bytes) lie in front of it.  Words: #descents 0, fast 5, error 2."""
+    L = nat.lib()
+    out = (ctypes.c_int64 * 4)()
+    for E, pre in ((0, 131072 + 256), (1, 131072 + 256), (9000, 131072 + 256), (1 << 17, 131072 + 768),
+                   ((1 << 20) + 1, 131072 + 4352), (7500000, 131072 + 29440)):
+        assert L.tsamd_sort_header(i64(E), 0, out) == 0 and list(out) == [0, 0, 5, 2], E
+        assert L.tsamd_sort_header(i64(E), 1, out) == 0 and list(out) == [pre, 0, 5, 2], E
+        assert pre + L.tsamd_sort_coo_workspace_bytes(i64(E)) == L.tsamd_sort_coalesce_workspace_bytes(i64(E))
+    assert L.tsamd_sort_header(i64(-1), 0, out) == 1 and L.tsamd_sort_header(i64(5), 0, None) == 1
+
+
 # ---- status codes: every case fails (or finishes) before any HIP call; `fake` is never dereferenced ----
 fake = vp(0x1000)
 BIG = sz(1 << 40)
