@@ -17,299 +17,10 @@
 // kernels run on the current stream without synchronising.  Unlike the reference there is
 // no CPU branch: tensors must live on the GPU, anything else raises.
 #include "ops_common.h"
-
-#include <array>
+#include "ops_spmm_state.h"
 
 namespace tsamd_ops {
 namespace {
-
-// Neither cache may hold on to memory that was allocated while a HIP graph is being captured (it would come
-// from the graph's private pool): a capturing stream bypasses them.
-bool stream_is_capturing(void *stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) != hipSuccess ||
-         cs != hipStreamCaptureStatusNone;
-}
-
-// "The same tensor contents as last time", as far as torch can tell: the same storage object (held weakly: while it is
-// alive its address cannot be handed to another tensor), the same data pointer and the same version counter.
-// Inference tensors have no version counter: no cache below ever keeps or matches one (their callers turn them away).
-struct TensorIdentity {
-  c10::weak_intrusive_ptr<c10::StorageImpl> storage{c10::weak_intrusive_ptr<c10::StorageImpl>(
-      c10::make_intrusive<c10::StorageImpl>(c10::StorageImpl::use_byte_size_t(), 0, c10::DataPtr(), nullptr, false))};
-  const void *ptr = nullptr;
-  uint32_t version = 0;
-
-  static uint32_t version_of(const Tensor &t) { return t.unsafeGetTensorImpl()->version_counter().current_version(); }
-  bool matches(const Tensor &t) const {
-    if (ptr != t.data_ptr() || version != version_of(t)) return false;
-    auto alive = storage.lock();
-    return alive && alive.get() == t.storage().unsafeGetStorageImpl();
-  }
-  void rearm(const Tensor &t) {
-    storage = c10::weak_intrusive_ptr<c10::StorageImpl>(
-        c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(t.storage().unsafeGetStorageImpl()));
-    ptr = t.data_ptr();
-    version = version_of(t);
-  }
-  void forget() { ptr = nullptr; }
-};
-
-// ---- operand cache (include/tsamd.h: tsamd_spmm_cached) ------------------------------------------------
-// One entry: the relabelled copy of the last dense operand that needed one.  A call may reuse it when the
-// operand is provably the same tensor contents as far as torch can tell (TensorIdentity), with the same shape /
-// dtype / device / stream, same sparse pattern (col pointer, version and length) and reduction class -- and the
-// kernel side re-checks a sampled fingerprint on the device.
-//
-// OPT-IN (off by default): the reference boundary keeps no state between calls (csrc/cuda/spmm_cuda.cu:102,134
-// allocate fresh outputs, nothing else survives), and neither the version counter nor a SAMPLED fingerprint can
-// see a sparse write that bypasses autograd's bookkeeping (`x.data[i] = ...`, a DLPack / raw-pointer writer, a
-// collective landing in a persistent buffer): with the cache on such a write returns a stale product.  A caller
-// that knows its operand is only ever updated through torch (or densely) turns it on with
-// torch.ops.tsamd.operand_cache(True) or TSAMD_OPERAND_CACHE=1; inference tensors (no version counter) never use it.
-struct OperandCache {
-  std::mutex mu;
-  bool enabled = false;
-  TensorIdentity mat;
-  // the rest of the key: dtype, reduction class, device, col pointer / version / length, sizes of mat
-  using Key = std::tuple<int, int, int, const void *, uint32_t, int64_t, std::vector<int64_t>>;
-  Key key;
-  void *stream = nullptr;
-  Tensor buf;
-  int64_t hits = 0, fills = 0;
-};
-
-OperandCache &operand_cache_state() {
-  static OperandCache c;
-  static bool init = [] {
-    const char *env = getenv("TSAMD_OPERAND_CACHE");
-    if (env != nullptr) c.enabled = env[0] == '1';
-    return true;
-  }();
-  (void)init;
-  return c;
-}
-
-// torch.ops.tsamd.operand_cache(enable) -> [was enabled, hits, fills]; drops the cached copy
-std::vector<int64_t> operand_cache_ctl(bool enable) {
-  OperandCache &c = operand_cache_state();
-  std::lock_guard<std::mutex> lock(c.mu);
-  std::vector<int64_t> r = {c.enabled ? 1 : 0, c.hits, c.fills};
-  c.enabled = enable;
-  c.buf = Tensor();
-  c.mat.forget();
-  return r;
-}
-
-// ---- transposed-pattern cache ------------------------------------------------------------------------------
-// grad_mat = A^T * grad_out multiplies by the CSC view (colptr, row[csr2csc], value[csr2csc]).  The reference
-// gathers row[csr2csc] and value[csr2csc] anew in every backward (spmm.cpp:104-106).  The row ids of the CSC
-// order only depend on the PATTERN, which a training loop does not change: they are gathered once and kept
-// (one entry; key = the identities of `row` and `csr2csc`), so that every
-// later backward reads them sequentially; the stream is part of the key (a backward on another stream starts a
-// new entry instead of reading arrays whose producer it is not ordered after).  TSAMD_PATTERN_CACHE=0 turns it off (then, and for a pattern seen
-// for the first time in a no-reuse setting, the kernel reads (row, value) through csr2csc -- tsamd_spmm_permuted).
-//
-// Only the `tsamd::spmm_sum_owned` / `tsamd::spmm_mean_owned` ops consult it -- the ones SparseTensor.matmul
-// calls with arrays that its SparseStorage owns (immutable by the storage's contract, exactly like the
-// reference's own storage-level caches rowcount / colptr / csr2csc).  The bare reference ops
-// `torch_sparse::spmm_sum / spmm_mean` keep no state THAT A RESULT CAN DEPEND ON between calls: not this cache, not the
-// operand cache unless the caller opts in.  (They do keep pattern hints, below: advisory state, which moves addresses and
-// the order of execution and which no value can depend on -- a stale hint is at worst a slower call.)
-struct PatternCache {
-  std::mutex mu;
-  bool enabled = true;
-  TensorIdentity row, perm;
-  int64_t E = -1;
-  void *stream = nullptr;  // the gathered arrays are produced and consumed on one stream only (no cross-stream events)
-  int seen = 0;  // calls with this key so far
-  Tensor row_t;
-  // value[csr2csc] of FIXED edge weights (a value tensor that does not require grad, e.g. GCN's normalised
-  // adjacency): valid while the pattern entry is and the value tensor keeps its identity
-  TensorIdentity val;
-  Tensor value_t;
-  // what the backwards did with the entry (torch.ops.tsamd.pattern_cache_stats; read by the tests only)
-  int64_t row_hits = 0, value_hits = 0, value_fills = 0;
-};
-
-PatternCache &pattern_cache_state() {
-  static PatternCache c;
-  static bool init = [] {
-    const char *env = getenv("TSAMD_PATTERN_CACHE");
-    if (env != nullptr && env[0] == '0') c.enabled = false;
-    return true;
-  }();
-  (void)init;
-  return c;
-}
-
-// torch.ops.tsamd.pattern_cache(enable) -> was enabled; drops the cached row ids
-bool pattern_cache_ctl(bool enable) {
-  PatternCache &c = pattern_cache_state();
-  std::lock_guard<std::mutex> lock(c.mu);
-  const bool was = c.enabled;
-  c.enabled = enable;
-  c.row_t = Tensor();
-  c.value_t = Tensor();
-  c.row.forget();
-  c.val.forget();
-  return was;
-}
-
-// torch.ops.tsamd.pattern_cache_stats() -> [enabled, backwards served from the kept row ids, backwards served from the
-// kept value[csr2csc], gathers of value[csr2csc] into the entry]; the counters only grow
-std::vector<int64_t> pattern_cache_stats() {
-  PatternCache &c = pattern_cache_state();
-  std::lock_guard<std::mutex> lock(c.mu);
-  return {c.enabled ? 1 : 0, c.row_hits, c.value_hits, c.value_fills};
-}
-
-// row[csr2csc] from the cache, or an undefined tensor when the caller should read through csr2csc instead
-// (cache off, inference tensors, or the FIRST backward with this pattern: the gather only pays off when the
-// pattern comes back, so it is made on the second sighting)
-Tensor cached_csc_rows(const Tensor &row, const Tensor &csr2csc) {
-  PatternCache &pc = pattern_cache_state();
-  if (!pc.enabled || row.is_inference() || csr2csc.is_inference() || !row.is_contiguous() || !csr2csc.is_contiguous() ||
-      !row.device().is_cuda() || stream_is_capturing(current_stream(row)))
-    return Tensor();
-  void *stream = current_stream(row);
-  std::lock_guard<std::mutex> lock(pc.mu);
-  if (!(pc.E == row.numel() && pc.stream == stream && pc.row.matches(row) && pc.perm.matches(csr2csc))) {
-    pc.row.rearm(row);
-    pc.perm.rearm(csr2csc);
-    pc.E = row.numel();
-    pc.stream = stream;
-    pc.seen = 1;
-    pc.row_t = Tensor();
-    pc.value_t = Tensor();
-    pc.val.forget();
-    return Tensor();
-  }
-  ++pc.seen;
-  ++pc.row_hits;
-  if (!pc.row_t.defined()) pc.row_t = row.index_select(0, csr2csc);
-  return pc.row_t;
-}
-
-// value[csr2csc] for the pattern that cached_csc_rows() just confirmed (call right after it returned a defined
-// tensor): kept across backwards when `value` is not trainable, gathered anew otherwise
-Tensor csc_values(const Tensor &value, const Tensor &csr2csc) {
-  Tensor v = value.detach();
-  PatternCache &pc = pattern_cache_state();
-  if (needs_grad(value) || v.is_inference() || !v.is_contiguous() || stream_is_capturing(current_stream(v)))
-    return v.index_select(0, csr2csc);
-  std::lock_guard<std::mutex> lock(pc.mu);
-  if (!pc.enabled || pc.perm.ptr != csr2csc.data_ptr() || !pc.row_t.defined() || pc.stream != current_stream(v))
-    return v.index_select(0, csr2csc);
-  if (pc.value_t.defined() && pc.value_t.scalar_type() == v.scalar_type() && pc.value_t.numel() == v.numel() &&
-      pc.val.matches(v)) {
-    ++pc.value_hits;
-  } else {
-    pc.value_t = v.index_select(0, csr2csc);
-    pc.val.rearm(v);
-    ++pc.value_fills;
-  }
-  return pc.value_t;
-}
-
-// ---- pattern hints (include/tsamd.h: tsamd_spmm_hinted) ---------------------------------------------------
-// What the forward works out from (rowptr, col) alone -- the camping probe's verdict, the hot 64-id blocks and their
-// ranks, the slot -> partition map of the column order -- is kept per pattern and reused by the later calls with the
-// same pattern: the same tensors in every layer and every epoch.  ON by default and without a switch, for the bare
-// reference ops too, because the ops keep no state THAT A RESULT CAN DEPEND ON: the hints are advisory (they choose
-// addresses and the order of execution, never a value), a call with stale hints -- `col.data` overwritten in place,
-// which no version counter sees -- returns the bits of a call without any, only more slowly.  That is the difference to
-// the operand cache above, which keeps a copy of X: there a stale entry is a wrong result, hence opt-in.
-// Four entries, least recently used out (forward and transposed pattern of a training step, times two graphs).  Key:
-// the identities of rowptr and col plus every size the buffer's layout depends on (M, N, E, row bytes, dtype, reduction
-// class, B), the device, the stream (the entry's buffer is allocated, written and read on that stream only, so
-// replacing an entry is stream-ordered) and the column-order setting in force.  Inference tensors (no version counter),
-// non-contiguous inputs, capturing streams and the verification mode go without.
-struct PatternHints {
-  struct Entry {
-    TensorIdentity rowptr, col;
-    std::array<int64_t, 9> key{};
-    void *stream = nullptr;
-    Tensor buf;  // undefined: the slot is free
-    uint64_t used = 0;
-  };
-  std::mutex mu;
-  std::array<Entry, 4> entries;
-  uint64_t clock = 0;
-  int64_t builds = 0, reuses = 0;
-};
-
-PatternHints &pattern_hints_state() {
-  static PatternHints h;
-  return h;
-}
-
-// torch.ops.tsamd.pattern_hints() -> [entries, calls that built hints, calls that reused them]; drops every entry
-// (tests only: the counters only grow)
-std::vector<int64_t> pattern_hints_ctl() {
-  PatternHints &h = pattern_hints_state();
-  std::lock_guard<std::mutex> lock(h.mu);
-  int64_t n = 0;
-  for (auto &e : h.entries) {
-    n += e.buf.defined() ? 1 : 0;
-    e.buf = Tensor();
-    e.rowptr.forget();
-    e.col.forget();
-  }
-  return {n, h.builds, h.reuses};
-}
-
-// The hints buffer of this call's pattern and what to do with it (1 build, 2 reuse), or state 0: the call goes without.
-// `like`: a tensor on the call's device (the buffer is allocated under the current stream).
-std::pair<Tensor, int> pattern_hints_for(const Tensor &rowptr, const Tensor &col, int dt, int red, int64_t B, int64_t M,
-                                         int64_t N, int64_t K, int64_t E, const Tensor &like, void *stream) {
-  const size_t bytes = tsamd_spmm_hints_bytes(dt, red, B, M, N, K, E);
-  if (bytes == 0 || rowptr.is_inference() || col.is_inference() || !rowptr.is_contiguous() || !col.is_contiguous() ||
-      tsamd_spmm_reference_order(-1) != 0 || stream_is_capturing(stream))
-    return {Tensor(), 0};
-  const std::array<int64_t, 9> key = {M, N, E, K * (int64_t)like.element_size(), dt,
-                                      (red == TSAMD_MIN || red == TSAMD_MAX) ? 1 : 0, B, (int64_t)like.get_device(),
-                                      (int64_t)tsamd_spmm_column_order(-1)};
-  PatternHints &h = pattern_hints_state();
-  std::lock_guard<std::mutex> lock(h.mu);
-  PatternHints::Entry *same = nullptr, *victim = &h.entries[0];
-  for (auto &e : h.entries) {
-    if (e.buf.defined() && e.key == key && e.stream == stream && (size_t)e.buf.numel() >= bytes) {
-      if (e.rowptr.matches(rowptr) && e.col.matches(col)) {
-        e.used = ++h.clock;
-        ++h.reuses;
-        return {e.buf, 2};
-      }
-      // the same arrays after a recorded write: the entry is built anew in place
-      if (e.rowptr.ptr == rowptr.data_ptr() && e.col.ptr == col.data_ptr()) same = &e;
-    }
-    if (victim->buf.defined() && (!e.buf.defined() || e.used < victim->used)) victim = &e;
-  }
-  PatternHints::Entry &e = same != nullptr ? *same : *victim;
-  if (same == nullptr) {
-    e.buf = Tensor();  // release before the new allocation
-    e.buf = workspace(bytes, like);
-  }
-  e.rowptr.rearm(rowptr);
-  e.col.rearm(col);
-  e.key = key;
-  e.stream = stream;
-  e.used = ++h.clock;
-  ++h.builds;
-  return {e.buf, 1};
-}
-
-// a build call failed: its entry holds nothing a later call may reuse
-void pattern_hints_drop(const Tensor &buf) {
-  PatternHints &h = pattern_hints_state();
-  std::lock_guard<std::mutex> lock(h.mu);
-  for (auto &e : h.entries)
-    if (e.buf.defined() && e.buf.data_ptr() == buf.data_ptr()) {
-      e.buf = Tensor();
-      e.rowptr.forget();
-      e.col.forget();
-    }
-}
 
 // ---- the forward's arguments, once ----------------------------------------------------------------------
 // B, M, N, K, E of a product; mat.dim() >= 2
@@ -434,52 +145,29 @@ std::tuple<Tensor, OptTensor> spmm_fw(const Tensor &rowptr, const Tensor &col, c
 // the forward of the registered ops: tsamd_spmm, or tsamd_spmm_cached when this product copies its operand
 std::tuple<Tensor, OptTensor> spmm_fw_cached(const Tensor &rowptr, const Tensor &col, const OptTensor &opt_value,
                                              const Tensor &mat_in, const std::string &reduce, bool arg32 = false) {
-  OperandCache &oc = operand_cache_state();
   const int red = reduce_code(reduce);
-  bool eligible = oc.enabled && mat_in.defined() && mat_in.device().is_cuda() && mat_in.dim() >= 2 &&
-                  mat_in.is_contiguous() && !mat_in.is_inference() && rowptr.device().is_cuda() &&
-                  rowptr.dim() == 1 && col.dim() == 1 && col.is_contiguous() && rowptr.is_contiguous() &&
-                  (reinterpret_cast<uintptr_t>(mat_in.data_ptr()) % 16) == 0;
-  if (eligible) {
+  // the shapes tsamd_spmm_cached takes as they are; which of them copy their operand is the kernel side's decision
+  bool shaped = operand_cache_enabled() && mat_in.defined() && mat_in.device().is_cuda() && mat_in.dim() >= 2 &&
+                mat_in.is_contiguous() && rowptr.device().is_cuda() && rowptr.dim() == 1 && col.dim() == 1 &&
+                col.is_contiguous() && rowptr.is_contiguous() &&
+                (reinterpret_cast<uintptr_t>(mat_in.data_ptr()) % 16) == 0;
+  if (shaped) {
     const at::ScalarType t = mat_in.scalar_type();
-    eligible = t == at::kFloat || t == at::kDouble || t == at::kHalf || t == at::kBFloat16 || t == at::kInt || t == at::kLong;
+    shaped = t == at::kFloat || t == at::kDouble || t == at::kHalf || t == at::kBFloat16 || t == at::kInt || t == at::kLong;
   }
-  size_t cache_bytes = 0;
-  int64_t E = 0;
-  int dt = -1;
-  if (eligible) {
+  if (shaped) {
     const SpmmDims d = spmm_dims(rowptr, col, mat_in);
-    E = d.E;
-    dt = dtype_code(mat_in);
-    cache_bytes = tsamd_spmm_operand_cache_bytes(dt, red, d.B, d.M, d.N, d.K, d.E);
-  }
-  if (!eligible || cache_bytes == 0 || stream_is_capturing(current_stream(mat_in)))
-    return spmm_fw(rowptr, col, opt_value, mat_in, reduce, std::nullopt, arg32);
-
-  check_spmm_args(rowptr, col, opt_value, mat_in);  // (before the entry is re-armed: a refused call leaves it alone)
-  c10::hip::HIPGuard guard(rowptr.get_device());
-  void *stream = current_stream(mat_in);
-  const uint32_t col_version = col.is_inference() ? 0u : TensorIdentity::version_of(col);
-  const OperandCache::Key key{dt, (red == TSAMD_MIN || red == TSAMD_MAX) ? 1 : 0, (int)mat_in.get_device(), col.data_ptr(),
-                              col_version, E, mat_in.sizes().vec()};
-
-  std::lock_guard<std::mutex> lock(oc.mu);
-  const bool valid = oc.buf.defined() && oc.key == key && oc.stream == stream && (size_t)oc.buf.numel() >= cache_bytes &&
-                     oc.mat.matches(mat_in);
-  if (!valid) {
-    // a buffer is only ever touched on the stream it was allocated under (the caching allocator's reuse is
-    // stream-ordered on that stream): another stream gets a fresh one instead of racing with pending work
-    if (!oc.buf.defined() || (size_t)oc.buf.numel() < cache_bytes || oc.buf.get_device() != mat_in.get_device() ||
-        oc.stream != stream) {
-      oc.buf = Tensor();  // release before the new allocation
-      oc.buf = workspace(cache_bytes, mat_in);
+    const int dt = dtype_code(mat_in);
+    const size_t cache_bytes = tsamd_spmm_operand_cache_bytes(dt, red, d.B, d.M, d.N, d.K, d.E);
+    if (cache_bytes != 0) {
+      check_spmm_args(rowptr, col, opt_value, mat_in);  // (before the entry is re-armed: a refused call leaves it alone)
+      c10::hip::HIPGuard guard(rowptr.get_device());
+      const OperandCopy copy = operand_cache_copy(col, mat_in, dt, red, d.E, cache_bytes);  // (locked until the return)
+      if (copy.buf.defined())
+        return spmm_run(rowptr, col, opt_value, mat_in, red, std::nullopt, arg32, copy.buf, copy.valid);
     }
-    oc.mat.rearm(mat_in);
-    oc.key = key;
-    oc.stream = stream;
   }
-  ++(valid ? oc.hits : oc.fills);
-  return spmm_run(rowptr, col, opt_value, mat_in, red, std::nullopt, arg32, oc.buf, valid);
+  return spmm_fw(rowptr, col, opt_value, mat_in, reduce, std::nullopt, arg32);
 }
 
 Tensor spmm_value_bw(const Tensor &row, const Tensor &rowptr, const Tensor &col, Tensor mat,
@@ -494,17 +182,26 @@ Tensor spmm_value_bw(const Tensor &row, const Tensor &rowptr, const Tensor &col,
   check_index(col, "col");
   check_index(row, "row");
   Tensor rp = rowptr.contiguous(), c = col.contiguous(), r = row.contiguous();
-  const int64_t M = grad.size(-2), N = mat.size(-2), K = mat.size(-1), E = col.numel();
-  const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
-  Tensor out = torch::empty({E}, grad.options().requires_grad(false));
+  const SpmmDims d = spmm_dims(rp, c, mat);
+  Tensor out = torch::empty({d.E}, grad.options().requires_grad(false));
   check_status(tsamd_spmm_value_bw(dtype_code(mat), reduce_code(reduce), r.data_ptr<int64_t>(),
                                    rp.data_ptr<int64_t>(), c.data_ptr<int64_t>(),
-                                   mat.data_ptr(), grad.data_ptr(), out.data_ptr(), B, M, N, K, E,
+                                   mat.data_ptr(), grad.data_ptr(), out.data_ptr(), d.B, grad.size(-2), d.N, d.K, d.E,
                                    current_stream(mat)),
                "tsamd_spmm_value_bw");
   return out;
 }
 
+// The per-edge weights of grad_mat = A^T * grad_out in CSC order (row_t = row[csr2csc]): value[csr2csc] for sum,
+// value[csr2csc] / max(rowcount[row_t], 1) for mean (rowcount given) -- its reciprocal count alone without values --
+// or none.  t: the dtype of the product.
+OptTensor csc_weights(const OptTensor &value, const Tensor &csr2csc, const OptTensor &rowcount, const Tensor &row_t,
+                      at::ScalarType t) {
+  if (!rowcount.has_value())
+    return value.has_value() ? OptTensor(value.value().detach().index_select(0, csr2csc)) : std::nullopt;
+  Tensor cnt = rowcount.value().index_select(0, row_t).to(t).clamp_min_(1);
+  return value.has_value() ? value.value().detach().index_select(0, csr2csc).div_(cnt) : cnt.reciprocal_();
+}
 
 // ---- sum / mean ---------------------------------------------------------------------------
 // One Function serves both: `mean` selects the divisor handling in both directions.
@@ -548,24 +245,23 @@ class SpmmAddFunction : public torch::autograd::Function<SpmmAddFunction> {
     if (needs_grad(mat)) {
       // grad_mat = A^T * grad_out: the CSC arrays are the CSR of A^T; per-edge weights are
       // value (sum) or value / max(deg(row), 1) (mean) in CSC order.
-      if (!mean) {
+      const OptTensor v = has_value ? OptTensor(value) : std::nullopt;
+      // the pattern's kept CSC row ids, if any, and with them the values of a sum (mean divides its weights in place: it
+      // gathers its own): one call, one lock
+      const CscView kept = owned ? pattern_cache_csc_view(row, csr2csc, v, has_value && !mean) : CscView();
+      if (mean) {
+        Tensor row_t = kept.row_t.defined() ? kept.row_t : row.index_select(0, csr2csc);
+        OptTensor w = csc_weights(v, csr2csc, rowcount, row_t, mat.scalar_type());
+        grad_mat = std::get<0>(spmm_fw(colptr, row_t, w, grad_out, "sum"));
+      } else if (kept.row_t.defined()) {
+        // the pattern came back: its CSC row ids are at hand, only the values are gathered (one ATen gather)
+        OptTensor w = has_value ? OptTensor(kept.value_t) : std::nullopt;
+        grad_mat = std::get<0>(spmm_fw(colptr, kept.row_t, w, grad_out, "sum"));
+      } else {
         // sum: the kernel reads (row, value) THROUGH csr2csc -- no row.index_select(0, csr2csc) /
         // value.index_select(0, csr2csc) temporaries as in the reference (spmm.cpp:104-106)
-        Tensor row_t = owned ? cached_csc_rows(row, csr2csc) : Tensor();
-        if (row_t.defined()) {
-          // the pattern came back: its CSC row ids are at hand, only the values are gathered (one ATen gather)
-          OptTensor w = has_value ? OptTensor(csc_values(value, csr2csc)) : std::nullopt;
-          grad_mat = std::get<0>(spmm_fw(colptr, row_t, w, grad_out, "sum"));
-        } else {
-          OptTensor w = has_value ? OptTensor(value.detach()) : std::nullopt;
-          grad_mat = std::get<0>(spmm_fw(colptr, row, w, grad_out, "sum", csr2csc));
-        }
-      } else {
-        Tensor row_t = owned ? cached_csc_rows(row, csr2csc) : Tensor();
-        if (!row_t.defined()) row_t = row.index_select(0, csr2csc);
-        Tensor cnt = rowcount.index_select(0, row_t).to(mat.scalar_type()).clamp_min_(1);
-        Tensor w = has_value ? value.detach().index_select(0, csr2csc).div_(cnt) : cnt.reciprocal_();
-        grad_mat = std::get<0>(spmm_fw(colptr, row_t, w, grad_out, "sum"));
+        OptTensor w = has_value ? OptTensor(value.detach()) : std::nullopt;
+        grad_mat = std::get<0>(spmm_fw(colptr, row, w, grad_out, "sum", csr2csc));
       }
     }
     return {Tensor(), Tensor(), Tensor(), grad_value, Tensor(), Tensor(), Tensor(), grad_mat,
@@ -593,7 +289,7 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
     Tensor records;
     bool use_records = false;
     // (grad mode is off inside a Function's forward; the front-end hands the CSC arrays over only when it was on)
-    if (arg32 && has_csc && needs_grad(mat) && !operand_cache_state().enabled &&
+    if (arg32 && has_csc && needs_grad(mat) && !operand_cache_enabled() &&
         mat.device().is_cuda() && mat.dim() >= 2 && rowptr.dim() == 1 && col.dim() == 1 &&
         (mat.scalar_type() == at::kFloat || mat.scalar_type() == at::kHalf || mat.scalar_type() == at::kBFloat16) &&
         (!has_value || value.scalar_type() == mat.scalar_type()) && opt_row.value().numel() == col.numel() &&
@@ -664,8 +360,8 @@ class SpmmMinMaxFunction : public torch::autograd::Function<SpmmMinMaxFunction> 
     if (!want_value && !want_mat)
       return {Tensor(), Tensor(), grad_value, grad_mat, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
     c10::hip::HIPGuard guard(mat.get_device());
-    const int64_t N = mat.size(-2), K = mat.size(-1), M = grad_out.size(-2), E = col.numel();
-    const int64_t B = (N * K) > 0 ? mat.numel() / (N * K) : 1;
+    const SpmmDims d = spmm_dims(rowptr, col, mat);
+    const int64_t B = d.B, M = grad_out.size(-2), N = d.N, K = d.K, E = d.E;
     const int dt = dtype_code(mat);
     // The pull is deterministic and faster for grad_mat alone (configs[2]: 1.36 vs 2.47 ms).  With grad_value as
     // well it pays a masked SDDMM where the scatter kernel gets the value gradient fused: WHICH of the two wins
@@ -825,13 +521,8 @@ class SpmmRelabelledFunction : public torch::autograd::Function<SpmmRelabelledFu
     }
     if (needs_grad(mat_h)) {
       Tensor row_t = row.index_select(0, csr2csc);
-      OptTensor w = std::nullopt;
-      if (mean) {
-        Tensor cnt = rowcount.index_select(0, row_t).to(mat_h.scalar_type()).clamp_min_(1);
-        w = has_value ? value.detach().index_select(0, csr2csc).div_(cnt) : cnt.reciprocal_();
-      } else if (has_value) {
-        w = value.detach().index_select(0, csr2csc);
-      }
+      OptTensor w = csc_weights(has_value ? OptTensor(value) : std::nullopt, csr2csc,
+                                mean ? OptTensor(rowcount) : std::nullopt, row_t, mat_h.scalar_type());
       grad_mat = std::get<0>(spmm_relabelled_fw(colptr, relabel_ids(row_t, M, row_t), w, grad_h, "sum"));
     }
     return {Tensor(), Tensor(), Tensor(), grad_value, Tensor(), Tensor(), Tensor(), grad_mat,
@@ -877,7 +568,7 @@ Tensor gather_rows(Tensor src, Tensor idx) {
 
 // ---- registered entry points (reference signatures) -----------------------------------------
 // owned: the index arrays belong to a SparseStorage (SparseTensor.matmul): the backward may keep row[csr2csc] (and
-// value[csr2csc] of non-trainable weights) across calls -- see PatternCache
+// value[csr2csc] of non-trainable weights) across calls -- see PatternCache in ops_spmm_state.cpp
 Tensor spmm_add(OptTensor opt_row, Tensor rowptr, Tensor col, OptTensor opt_value, OptTensor opt_rowcount,
                 OptTensor opt_colptr, OptTensor opt_csr2csc, Tensor mat, bool mean, bool owned) {
   Tensor value = opt_value.value_or(col);
@@ -1016,10 +707,6 @@ static auto registry_spmm = torch::RegisterOperators()
                            .op("tsamd::column_order", &column_order)
                            .op("tsamd::spmm_sum_owned", &spmm_sum_owned)
                            .op("tsamd::spmm_mean_owned", &spmm_mean_owned)
-                           .op("tsamd::operand_cache", &operand_cache_ctl)
-                           .op("tsamd::pattern_cache", &pattern_cache_ctl)
-                           .op("tsamd::pattern_cache_stats", &pattern_cache_stats)
-                           .op("tsamd::pattern_hints", &pattern_hints_ctl)
                            .op("tsamd::relabel_ids", &relabel_ids)
                            .op("tsamd::gather_rows", &gather_rows)
                            .op("tsamd::spmm_relabelled", &spmm_relabelled);

@@ -264,7 +264,7 @@ def _pattern_cache_delta(ops, before):
 
 
 def _expected_route(case, reduce, i, cache_on=True, refreshed=False):
-    """What backward #i on one SparseTensor does with the transposed-pattern cache (ops_spmm.cpp): #0 meets a new
+    """What backward #i on one SparseTensor does with the transposed-pattern cache (ops_spmm_state.cpp): #0 meets a new
     pattern and reads through csr2csc; from #1 on the kept row ids serve; fixed weights of a sum are gathered into
     the entry at #1 (and again after an in-place update), then served from it."""
     if not cache_on or i == 0:
@@ -335,6 +335,37 @@ def test_autograd_fixed_weights_and_their_update(dev, ts, ops, dtype):
             out.backward(case.gd)
             assert _pattern_cache_delta(ops, before) == _expected_route(case, reduce, 4, refreshed=True), case.tag
             case.check('fixed weights after mul_(3)', reduce, out.detach(), v, x, scale=3)
+
+
+def test_pattern_cache_entry_belongs_to_one_stream(dev, ts, ops):
+    """The stream is part of the pattern cache's key: a backward on another stream starts a new entry (a first
+    sighting, then the gathers of the second), and so does the next one back on the original stream -- the single entry
+    was replaced.  Every round is held to the fp64 reference."""
+    assert ops.tsamd.pattern_cache(True)
+    case = _Case(dev, torch.float32, 7, (), 'fixed')
+    v, x = case.leaves()
+    A = case.tensor(ts, v)
+    seen = []
+
+    def one_round(what, sighting):
+        x.grad = None
+        out = A.matmul(x, 'sum')
+        before = ops.tsamd.pattern_cache_stats()
+        out.backward(case.gd)
+        seen.append(_pattern_cache_delta(ops, before))
+        assert seen[-1] == _expected_route(case, 'sum', sighting), '%s %s sighting #%d' % (case.tag, what, sighting)
+        case.check('%s sighting #%d' % (what, sighting), 'sum', out.detach(), v, x)
+
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    for i in range(2):
+        one_round('first stream', i)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        for i in range(2):
+            one_round('side stream', i)
+    main.wait_stream(side)
+    one_round('back on the first stream', 0)
+    assert seen == [[0, 0, 0], [1, 0, 1], [0, 0, 0], [1, 0, 1], [0, 0, 0]]
 
 
 @pytest.mark.parametrize('dtype', FLOAT_DTYPES)
