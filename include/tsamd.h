@@ -717,6 +717,57 @@ int tsamd_gat_attention_heads_bw(int dtype, const int64_t *row, const int64_t *r
                                  double negative_slope, void *p_out, void *dz_out, int64_t nseg, int64_t nsrc,
                                  int64_t H, int64_t D, int64_t E, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Dropout on the probabilities of the two fused calls (csrc/attention.hip, the DROP instantiations of the same
+ * kernels).  Each entry has the signature of its plain twin with `double dropout, uint64_t seed` after the scalar.
+ *
+ * The mask is a pure function of (seed, e, h), e the entry's position in CSR storage order and h its head:
+ *     thr  = (uint32) floor(dropout * 2^32)
+ *     r    = philox(seed, c_lo = e >> 2, c2 = (uint32) h, c3 = 0xD20B)       Philox4x32-10, key = (lo32, hi32) of seed
+ *     keep = (r.x, r.y, r.z, r.w)[e & 3] >= thr
+ *     c    = 1 / (1 - dropout)          computed in double, used in the accumulator type
+ * It does not depend on the route, the lane map, the chunking, the feature block or the dtype; forward and backward
+ * recompute it and nothing of size E is stored for it.
+ *
+ *   forward   out[r, h, :] = sum_i softmax_i(s(., h)) * keep(i, h) * c * v[col[i], h, :].  The softmax itself is the
+ *             plain call's -- a dropped entry still counts in the denominator -- so lse is the plain call's lse bit
+ *             for bit and out is NaN exactly where the plain call's is; records, fix-up, fill, workspace and
+ *             tsamd_attention_heads_route are unchanged.
+ *   backward  with p = e(s - lse), dp = <grad_out[r, h], v[col[i], h]>, delta = <grad_out[r, h], out[r, h]> (out is the
+ *             forward's out WITH dropout): p_out = pt = p * keep * c and ds = p * (keep * c * dp - delta) (dz = ds *
+ *             (z > 0 ? 1 : negative_slope) for the additive call).  lse not finite: NaN both; s = -inf: 0 both.  The
+ *             gradients follow as for the plain calls with pt in the place of p: grad_v = spmm(columns; pt, grad_out).
+ *
+ * Status: a dropout that is NaN, negative or >= 1 is TSAMD_ERR_INVALID, before every other case; then the twin's cases
+ * in the twin's order.  dropout == 0 runs the twin's kernels and gives the twin's bits.
+ *
+ * tsamd_attention_dropout_mask is host arithmetic only, through the function the kernels compile: keep[(e - e0) * H +
+ * h] = 1 where entry e in [e0, e0 + n) keeps head h, else 0.  A null array, a negative e0, n or H, or a rate that is
+ * NaN or outside [0, 1) is TSAMD_ERR_INVALID.
+ * ------------------------------------------------------------------------ */
+int tsamd_attention_heads_dropout(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                                  int64_t bias_heads, const void *q, const void *k, const void *v, double scale,
+                                  double dropout, uint64_t seed, void *out, void *lse, int64_t nseg, int64_t nsrc,
+                                  int64_t H, int64_t D, int64_t E, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+int tsamd_attention_heads_dropout_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                     const void *bias, int64_t bias_heads, const void *q, const void *k,
+                                     const void *v, const void *out, const void *lse, const void *grad_out,
+                                     double scale, double dropout, uint64_t seed, void *p_out, void *ds_out,
+                                     int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream);
+int tsamd_gat_attention_heads_dropout(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                                      int64_t bias_heads, const void *a_dst, const void *a_src, const void *v,
+                                      double negative_slope, double dropout, uint64_t seed, void *out, void *lse,
+                                      int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+int tsamd_gat_attention_heads_dropout_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                                         const void *bias, int64_t bias_heads, const void *a_dst, const void *a_src,
+                                         const void *v, const void *out, const void *lse, const void *grad_out,
+                                         double negative_slope, double dropout, uint64_t seed, void *p_out,
+                                         void *dz_out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
+                                         void *stream);
+int tsamd_attention_dropout_mask(uint64_t seed, double rate, int64_t e0, int64_t n, int64_t H, uint8_t *keep);
+
 /* ------------------------------------------------------------------------ *
  * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):

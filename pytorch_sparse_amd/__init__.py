@@ -8,7 +8,7 @@ Drop-in surface (same names and argument meaning as ``torch_sparse``):
 
 and, widening along SURVEY.md section 8f (the callers either side of that path):
 
-    sum / mean / min / max, softmax (rows / columns, differentiable), sddmm / matmul_heads (multi-head attention scores and aggregation, differentiable), attention (scores, softmax and aggregation fused in one pass, differentiable), gat_attention (the same pass for additive GAT scores, differentiable), mul / add (+ _ / _nnz variants), remove_diag / set_diag / fill_diag / get_diag,
+    sum / mean / min / max, softmax (rows / columns, differentiable), sddmm / matmul_heads (multi-head attention scores and aggregation, differentiable), attention (scores, softmax and aggregation fused in one pass, differentiable), gat_attention (the same pass for additive GAT scores, differentiable; both fused calls take dropout on the probabilities: dropout=, training=, seed=), mul / add (+ _ / _nnz variants), remove_diag / set_diag / fill_diag / get_diag,
     narrow, select, index_select(_nnz), masked_select(_nnz), permute, cat, SparseTensor.__getitem__,
     sample, sample_adj, random_walk, saint_subgraph, reverse_cuthill_mckee, eye, spadd, converters
     torch.ops.torch_sparse.{non_diag_mask, sample_adj, neighbor_sample, random_walk, saint_subgraph,

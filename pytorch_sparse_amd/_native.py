@@ -35,6 +35,8 @@ SYMBOLS = [
     'tsamd_sddmm_heads_route', 'tsamd_sddmm_heads', 'tsamd_spmm_heads_route', 'tsamd_spmm_heads_workspace_bytes', 'tsamd_spmm_heads',
     'tsamd_attention_heads_route', 'tsamd_attention_heads_workspace_bytes', 'tsamd_attention_heads', 'tsamd_attention_heads_bw',
     'tsamd_gat_attention_heads', 'tsamd_gat_attention_heads_bw',
+    'tsamd_attention_heads_dropout', 'tsamd_attention_heads_dropout_bw', 'tsamd_gat_attention_heads_dropout',
+    'tsamd_gat_attention_heads_dropout_bw', 'tsamd_attention_dropout_mask',
     'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
     'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
     'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
@@ -116,6 +118,13 @@ def lib():
         fused_bw = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
         L.tsamd_attention_heads.argtypes = L.tsamd_gat_attention_heads.argtypes = fused_fw
         L.tsamd_attention_heads_bw.argtypes = L.tsamd_gat_attention_heads_bw.argtypes = fused_bw
+        # with dropout on the probabilities: (double rate, uint64 seed) after the scalar
+        drop = [ctypes.c_double, ctypes.c_uint64]
+        L.tsamd_attention_heads_dropout.argtypes = L.tsamd_gat_attention_heads_dropout.argtypes = \
+            fused_fw[:9] + drop + fused_fw[9:]
+        L.tsamd_attention_heads_dropout_bw.argtypes = L.tsamd_gat_attention_heads_dropout_bw.argtypes = \
+            fused_bw[:13] + drop + fused_bw[13:]
+        L.tsamd_attention_dropout_mask.argtypes = [ctypes.c_uint64, ctypes.c_double, i64, i64, i64, vp]
         L.tsamd_select_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_filter_tiles_workspace_bytes.restype = ctypes.c_size_t

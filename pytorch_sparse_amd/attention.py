@@ -14,18 +14,23 @@ the multi-head SpMM with the score gradient as values, w.r.t. ``k`` the same on 
 the value gradient of ``matmul_heads`` is an SDDMM of ``grad_out`` with ``x``, its ``x`` gradient the SpMM on the columns.
 The column-side caches of the storage are only built when such a gradient will be asked for.
 
-``attention(adj, q, k, v, scale=None, bias=False)`` is the whole chain in one call (``tsamd::attention_heads``,
+``attention(adj, q, k, v, scale=None, bias=False, dropout=0.0, training=True, seed=None)`` is the whole chain in one call (``tsamd::attention_heads``,
 csrc/attention.hip): the scores are formed, normalised with an online softmax over the row and multiplied into ``v``
 in one pass over the entries, so the forward writes nothing of size ``nnz``.  It keeps ``out`` and the row-wise
 ``lse = log sum exp(score)`` for the backward, where one kernel (``tsamd::attention_heads_bw``) recomputes the
 probabilities ``p`` and the score gradients ``ds = p * (<grad_out, v> - <grad_out, out>)`` per entry and
 ``tsamd::spmm_heads`` turns them into ``grad_q``, ``grad_k`` and ``grad_v``; ``ds`` itself is the gradient of the bias.
 
-``gat_attention(adj, a_dst, a_src, v, negative_slope=0.2, bias=False)`` is the same fused pass for the additive score
+``gat_attention(adj, a_dst, a_src, v, negative_slope=0.2, bias=False, dropout=0.0, training=True, seed=None)`` is the same fused pass for the additive score
 of a graph attention network (``tsamd::gat_attention_heads``): ``leaky_relu(a_dst[row] + a_src[col] (+ the edge
 term))`` with one scalar per node and head, so no ``[nnz, H]`` gather, add, activation or softmax array is written.
 Its backward kernel (``tsamd::gat_attention_heads_bw``) gives ``p`` and ``dz``, the gradient of the pre-activation;
 ``tsamd::segment_reduce`` sums ``dz`` over the rows into ``grad_a_dst`` and over the columns into ``grad_a_src``.
+
+Both fused calls take ``dropout`` on the probabilities (the DROP instantiations of the same kernels): the mask is a
+Philox function of ``(seed, entry, head)`` recomputed in the backward, so training with attention dropout keeps the
+fused pass and its memory: ``out = sum softmax(score) * keep / (1 - dropout) * v``, and the backward kernel returns
+``p * keep / (1 - dropout)`` and ``ds = p * (keep / (1 - dropout) * <grad_out, v> - <grad_out, out>)``.
 """
 from typing import Optional
 
@@ -104,11 +109,12 @@ class _SpmmHeads(torch.autograd.Function):
 # are the score operands of the rows and of the columns, (q, k) or (a_dst, a_src), and `scalar` is scale or negative_slope
 def _fused_forward(ctx, op: str, sr: Tensor, sc: Tensor, v: Tensor, bias: Optional[Tensor], row: Optional[Tensor],
                    rowptr: Tensor, col: Tensor, colptr: Optional[Tensor], row_csc: Optional[Tensor],
-                   csr2csc: Optional[Tensor], scalar: float) -> Tensor:
-    """out of ``tsamd::<op>``; saves (operands, out, lse, rowptr, col, [bias], [row], [colptr, row_csc, csr2csc])"""
+                   csr2csc: Optional[Tensor], scalar: float, dropout: float = 0.0, seed: int = 0) -> Tensor:
+    """out of ``tsamd::<op>``; saves (operands, out, lse, rowptr, col, [bias], [row], [colptr, row_csc, csr2csc]) and keeps
+    (dropout, seed): the backward recomputes the mask"""
     b = None if bias is None else bias.detach()
-    out, lse = getattr(torch.ops.tsamd, op)(rowptr, col, b, sr.detach(), sc.detach(), v.detach(), scalar)
-    ctx.scalar = scalar
+    out, lse = getattr(torch.ops.tsamd, op)(rowptr, col, b, sr.detach(), sc.detach(), v.detach(), scalar, dropout, seed)
+    ctx.scalar, ctx.dropout, ctx.seed = scalar, dropout, seed
     ctx.has_bias, ctx.has_row, ctx.has_csc = bias is not None, row is not None, colptr is not None
     ctx.save_for_backward(*([sr, sc, v, out, lse, rowptr, col] + ([bias] if ctx.has_bias else []) +
                             ([row] if ctx.has_row else []) + ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
@@ -118,14 +124,16 @@ def _fused_forward(ctx, op: str, sr: Tensor, sc: Tensor, v: Tensor, bias: Option
 def _fused_backward(ctx, op_bw: str, grad_out: Tensor):
     """(p, d) = ``tsamd::<op_bw>`` on what the forward saved -> (sr, sc, d, rowptr, col, the column side or None, grad_v,
     grad_bias): grad_v = spmm_heads(columns; p, grad_out), grad_bias = d, summed over the heads for a [nnz] bias.  The
-    gradients of the score operands are the caller's."""
+    gradients of the score operands are the caller's.  With dropout the kernel gives ``p * keep * c`` for p and
+    ``d = p * (keep * c * <grad_out, v> - <grad_out, out>)``: nothing else changes here."""
     sr, sc, v, out, lse, rowptr, col = ctx.saved_tensors[:7]
     rest = list(ctx.saved_tensors[7:])
     bias = rest.pop(0) if ctx.has_bias else None
     row = rest.pop(0) if ctx.has_row else None
     csc = rest if ctx.has_csc else None
     g = grad_out.contiguous()  # expanded / transposed gradients arrive here
-    p, d = getattr(torch.ops.tsamd, op_bw)(row, rowptr, col, bias, sr, sc, v, out, lse, g, ctx.scalar)
+    p, d = getattr(torch.ops.tsamd, op_bw)(row, rowptr, col, bias, sr, sc, v, out, lse, g, ctx.scalar, ctx.dropout,
+                                           ctx.seed)
     grad_v = grad_bias = None
     if ctx.needs_input_grad[2]:
         grad_v = torch.ops.tsamd.spmm_heads(csc[0], csc[1], csc[2], p, g, v.size(0))
@@ -139,8 +147,8 @@ class _AttentionHeads(torch.autograd.Function):
     ds, k), grad_k = scale * spmm_heads(columns; ds, q), grad_v = spmm_heads(columns; p, grad_out), grad_bias = ds"""
 
     @staticmethod
-    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, *bias_pattern_scale):
-        return _fused_forward(ctx, 'attention_heads', q, k, v, *bias_pattern_scale)
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, *bias_pattern_scale_dropout):
+        return _fused_forward(ctx, 'attention_heads', q, k, v, *bias_pattern_scale_dropout)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -155,7 +163,7 @@ class _AttentionHeads(torch.autograd.Function):
             grad_k = torch.ops.tsamd.spmm_heads(csc[0], csc[1], csc[2], ds, q, k.size(0))
             if ctx.scalar != 1.0:
                 grad_k.mul_(ctx.scalar)
-        return grad_q, grad_k, grad_v, grad_bias, None, None, None, None, None, None, None
+        return grad_q, grad_k, grad_v, grad_bias, None, None, None, None, None, None, None, None, None
 
 
 class _GatAttentionHeads(torch.autograd.Function):
@@ -164,8 +172,8 @@ class _GatAttentionHeads(torch.autograd.Function):
     grad_out), grad_bias = dz"""
 
     @staticmethod
-    def forward(ctx, a_dst: Tensor, a_src: Tensor, v: Tensor, *bias_pattern_slope):
-        return _fused_forward(ctx, 'gat_attention_heads', a_dst, a_src, v, *bias_pattern_slope)
+    def forward(ctx, a_dst: Tensor, a_src: Tensor, v: Tensor, *bias_pattern_slope_dropout):
+        return _fused_forward(ctx, 'gat_attention_heads', a_dst, a_src, v, *bias_pattern_slope_dropout)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -176,20 +184,45 @@ class _GatAttentionHeads(torch.autograd.Function):
             grad_dst = torch.ops.tsamd.segment_reduce(dz, None, rowptr, a_dst.size(0), 'sum', True)
         if ctx.needs_input_grad[1]:
             grad_src = torch.ops.tsamd.segment_reduce(dz, csc[2], csc[0], a_src.size(0), 'sum', True)
-        return grad_dst, grad_src, grad_v, grad_bias, None, None, None, None, None, None, None
+        return grad_dst, grad_src, grad_v, grad_bias, None, None, None, None, None, None, None, None, None
 
 
 def _fused(adj: SparseTensor, fn, op: str, sr: Tensor, sc: Tensor, v: Tensor, b: Optional[Tensor],
-           scalar: float) -> Tensor:
+           scalar: float, dropout: float = 0.0, seed: int = 0) -> Tensor:
     """The fused call: through the autograd pair `fn` where a gradient will be asked for -- with the column side of the
-    pattern when it is sc's or v's -- and through ``tsamd::<op>`` alone where none will"""
+    pattern when it is sc's or v's -- and through ``tsamd::<op>`` alone where none will.  ``dropout == 0`` passes neither
+    the rate nor a seed: the call as it was before dropout existed"""
+    extra = (dropout, seed) if dropout != 0.0 else ()
     st = adj.storage
     rowptr, col = st.rowptr(), st.col()
     grad = torch.is_grad_enabled()
     if grad and (sr.requires_grad or sc.requires_grad or v.requires_grad or (b is not None and b.requires_grad)):
         csc = _csc_side(st) if sc.requires_grad or v.requires_grad else (None, None, None)
-        return fn.apply(sr, sc, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], scalar)
-    return getattr(torch.ops.tsamd, op)(rowptr, col, b, sr, sc, v, scalar)[0]
+        return fn.apply(sr, sc, v, b, st._row, rowptr, col, csc[0], csc[1], csc[2], scalar, *extra)
+    return getattr(torch.ops.tsamd, op)(rowptr, col, b, sr, sc, v, scalar, *extra)[0]
+
+
+def _host_seed() -> int:
+    """One seed in [0, 2^63 - 1) from torch's CPU generator -- ``host_seed()`` of csrc/ops_sample.h, the samplers' rule:
+    reproducible under ``torch.manual_seed``, a new one per call, no device sync"""
+    return int(torch.randint(0, torch.iinfo(torch.int64).max, (1, ), dtype=torch.long))
+
+
+def _dropout_args(dropout, training: bool, seed):
+    """(rate, seed) of a fused call: (0.0, 0) where nothing is dropped"""
+    if isinstance(dropout, bool) or not isinstance(dropout, (int, float)):
+        raise TypeError('dropout must be a float, got %s' % type(dropout).__name__)
+    dropout = float(dropout)
+    if not 0.0 <= dropout < 1.0:  # NaN fails both comparisons
+        raise ValueError('dropout must be a rate in [0, 1), got %r' % dropout)
+    if seed is not None:
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError('seed must be an int or None, got %s' % type(seed).__name__)
+        if not 0 <= seed < 2 ** 63:
+            raise ValueError('seed must be in [0, 2^63), got %d' % seed)
+    if dropout == 0.0 or not training:
+        return 0.0, 0
+    return dropout, _host_seed() if seed is None else seed
 
 
 def _edge_bias(adj: SparseTensor, H: int, dtype: torch.dtype, who: str) -> Tensor:
@@ -269,12 +302,20 @@ def matmul_heads(adj: SparseTensor, x: Tensor) -> Tensor:
 
 
 def attention(adj: SparseTensor, q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None,
-              bias: bool = False) -> Tensor:
+              bias: bool = False, dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> Tensor:
     """Attention over the pattern of ``adj`` in one fused pass: for row ``m`` and head ``h`` the score of a stored entry
     ``(m, n)`` is ``scale * <q[m, h], k[n, h]>`` (``scale=None``: ``D ** -0.5``), plus, with ``bias=True``, the entry's own
     value (``[nnz]`` shared by the heads or ``[nnz, H]``; ``-inf`` masks an entry); ``out[m, h] = sum_n softmax_n(score) *
     v[n, h]``.  ``q [M, H, D]``, ``k`` and ``v [N, H, D]`` -> ``[M, H, D]``; 2-D operands mean one head.  Rows without
-    entries are zeros.  Differentiable (once) w.r.t. ``q``, ``k``, ``v`` and, with ``bias=True``, the values."""
+    entries are zeros.  Differentiable (once) w.r.t. ``q``, ``k``, ``v`` and, with ``bias=True``, the values.
+
+    ``dropout`` in ``[0, 1)`` drops each probability (per stored entry and head) with that rate and scales the kept ones by
+    ``1 / (1 - dropout)``, as ``F.dropout`` on the ``[nnz, H]`` softmax output of the chain does; the softmax itself is not
+    renormalised.  The mask is a counter-based function of ``(seed, entry, head)`` that forward and backward recompute, so
+    still nothing of size ``nnz`` is kept.  ``training=False`` or ``dropout=0`` is the call without dropout, bit for bit.
+    ``seed=None`` draws a seed from torch's CPU generator (reproducible under ``torch.manual_seed``, a new mask per call,
+    no device sync); an int in ``[0, 2^63)`` fixes the mask."""
+    dropout, seed = _dropout_args(dropout, training, seed)
     for t, name in ((q, 'q'), (k, 'k'), (v, 'v')):
         if not isinstance(t, Tensor):
             raise TypeError('%s must be a Tensor' % name)
@@ -300,12 +341,12 @@ def attention(adj: SparseTensor, q: Tensor, k: Tensor, v: Tensor, scale: Optiona
         raise ValueError('attention needs at least one feature per head')
     b = _edge_bias(adj, H, q.dtype, 'q') if bias else None
     scale = float(D) ** -0.5 if scale is None else float(scale)
-    out = _fused(adj, _AttentionHeads, 'attention_heads', q, k, v, b, scale)
+    out = _fused(adj, _AttentionHeads, 'attention_heads', q, k, v, b, scale, dropout, seed)
     return out.squeeze(1) if flat else out
 
 
 def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, negative_slope: float = 0.2,
-                  bias: bool = False) -> Tensor:
+                  bias: bool = False, dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> Tensor:
     """Additive (graph attention network) attention over the pattern of ``adj`` in one fused pass: for row ``m`` and head
     ``h`` the score of a stored entry ``(m, n)`` is ``leaky_relu(a_dst[m, h] + a_src[n, h] + b, negative_slope)``, where
     ``b`` is, with ``bias=True``, the entry's own value (``[nnz]`` shared by the heads or ``[nnz, H]``) and zero without;
@@ -317,7 +358,11 @@ def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, ne
     of ``0`` the product ``0 * -inf`` is NaN (IEEE) and the row is NaN; this is not special-cased.
 
     Differentiable (once) w.r.t. ``a_dst``, ``a_src``, ``v`` and, with ``bias=True``, the values; the derivative of the
-    activation at ``z == 0`` is ``negative_slope``, as torch has it."""
+    activation at ``z == 0`` is ``negative_slope``, as torch has it.
+
+    ``dropout``, ``training`` and ``seed`` are those of ``attention``: dropout on the attention coefficients (``GATConv``'s
+    ``dropout``), applied to the probabilities inside the fused pass."""
+    dropout, seed = _dropout_args(dropout, training, seed)
     for t, name in ((a_dst, 'a_dst'), (a_src, 'a_src'), (v, 'v')):
         if not isinstance(t, Tensor):
             raise TypeError('%s must be a Tensor' % name)
@@ -342,12 +387,13 @@ def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, ne
     if negative_slope != negative_slope or negative_slope in (float('inf'), float('-inf')):
         raise ValueError('negative_slope must be finite, got %r' % negative_slope)
     b = _edge_bias(adj, H, v.dtype, 'v') if bias else None
-    out = _fused(adj, _GatAttentionHeads, 'gat_attention_heads', a_dst, a_src, v, b, negative_slope)
+    out = _fused(adj, _GatAttentionHeads, 'gat_attention_heads', a_dst, a_src, v, b, negative_slope, dropout, seed)
     return out.squeeze(1) if flat else out
 
 
-SparseTensor.gat_attention = (lambda self, a_dst, a_src, v, negative_slope=0.2, bias=False:
-                              gat_attention(self, a_dst, a_src, v, negative_slope, bias))
-SparseTensor.attention = lambda self, q, k, v, scale=None, bias=False: attention(self, q, k, v, scale, bias)
+SparseTensor.gat_attention = (lambda self, a_dst, a_src, v, negative_slope=0.2, bias=False, dropout=0.0, training=True,
+                              seed=None: gat_attention(self, a_dst, a_src, v, negative_slope, bias, dropout, training, seed))
+SparseTensor.attention = (lambda self, q, k, v, scale=None, bias=False, dropout=0.0, training=True, seed=None:
+                          attention(self, q, k, v, scale, bias, dropout, training, seed))
 SparseTensor.sddmm = lambda self, q, k, scale=1.0: sddmm(self, q, k, scale)
 SparseTensor.matmul_heads = lambda self, x: matmul_heads(self, x)

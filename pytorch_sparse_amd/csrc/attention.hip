@@ -54,7 +54,20 @@
 // itself.  a_dst / a_src are element loads of any alignment: the packet route is decided by v, out and D.  Lane map,
 // chunk, records, fix-up, fill and workspace are those above.  The backward keeps two dot products (dp, delta) in the
 // butterfly and stores p and dz = ds * (z > 0 ? 1 : negative_slope).
+//
+// Dropout on the probabilities (tsamd_*_dropout, the DROP instantiations of the same two kernels): a mask that is a pure
+// function of (seed, entry e in CSR storage order, head h) -- at_drop_keep below, which host and device both compile --
+//   thr = floor(rate * 2^32),  r = philox(seed, e >> 2, h, 0xD20B),  keep = r[e & 3] >= thr,  c = 1 / (1 - rate).
+// The softmax state (m, l) is folded as without dropout; only the accumulator row sees the mask: acc = acc * fa +
+// (keep ? fb * c : 0) * x.  So lse, the records, the fix-up, the fill and the workspace are unchanged, and every
+// feature block of a WIDE head forms the same mask.  One Philox call serves four consecutive entries of a head: a
+// group of at least kAtBatch lanes starts its batches at multiples of four and calls once per batch and head, a
+// narrower group calls per entry.  The backward recomputes the mask and stores pt = p * keep * c (what grad_v needs)
+// and ds = p * (keep * c * dp - delta); nothing of size E is kept for the mask.  rate == 0 runs the plain kernels.
+#include "philox.h"
 #include "segtile.h"
+
+#include <cmath>
 
 #include <type_traits>
 
@@ -94,8 +107,31 @@ struct AtCall {
   void *workspace;
   size_t workspace_bytes;
   hipStream_t stream;
+  double dropout;  // rate in [0, 1) of the dropout on the probabilities; 0: the plain kernels
+  uint64_t seed;   // of its mask
 };
 constexpr int kAtProceed = -1;  // no status yet: the call has work and its arguments are in order
+
+// ---- the dropout mask: one rule for the kernels and the host query --------------------------------------------------
+constexpr uint32_t kAtDropTag = 0xD20B;  // c3 of the mask's Philox calls (docs/design/oracle_parity.md, the draw table)
+
+// rate in [0, 1): not NaN, not negative, not 1 or above
+inline bool at_rate_ok(double rate) { return rate >= 0.0 && rate < 1.0; }
+// floor(rate * 2^32): the product is exact in a double and below 2^32
+inline uint32_t at_drop_threshold(double rate) { return (uint32_t)std::floor(rate * 4294967296.0); }
+
+// the four words of the batch of entries [e & ~3, (e & ~3) + 4) of head h
+__host__ __device__ __forceinline__ U4 at_drop_words(uint64_t seed, int64_t e, int64_t h) {
+  return philox(seed, (uint64_t)e >> 2, (uint32_t)h, kAtDropTag);
+}
+__host__ __device__ __forceinline__ bool at_drop_pick(const U4 &r, int at, uint32_t thr) {
+  const uint32_t word = at == 0 ? r.x : at == 1 ? r.y : at == 2 ? r.z : r.w;
+  return word >= thr;
+}
+// keep of entry e (CSR storage order) and head h
+__host__ __device__ __forceinline__ bool at_drop_keep(uint64_t seed, uint32_t thr, int64_t e, int64_t h) {
+  return at_drop_pick(at_drop_words(seed, e, h), (int)(e & 3), thr);
+}
 
 __device__ __forceinline__ float at_log(float x) { return logf(x); }
 __device__ __forceinline__ double at_log(double x) { return log(x); }
@@ -190,14 +226,15 @@ __global__ __launch_bounds__(256) void attention_fill_kernel(unsigned char *__re
   if (i < nlse) lse[i] = -std::numeric_limits<A>::infinity();
 }
 
-template <typename T, bool PACKED, bool WIDE, int MODE>
+template <typename T, bool PACKED, bool WIDE, int MODE, bool DROP>
 __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
     const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind, const T *__restrict__ bias, int64_t bias_heads,
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ x, typename Traits<T>::acc_t scale,
     T *__restrict__ out, typename Traits<T>::acc_t *__restrict__ lse, typename Traits<T>::acc_t *__restrict__ head_acc,
     typename Traits<T>::acc_t *__restrict__ tail_acc, typename Traits<T>::acc_t *__restrict__ head_ml,
     typename Traits<T>::acc_t *__restrict__ tail_ml, int64_t *__restrict__ head_seg, int64_t *__restrict__ tail_seg,
-    int64_t nseg, int64_t E, int64_t H, int64_t D, int lg_lph, int lg_hpp, int fblocks) {
+    int64_t nseg, int64_t E, int64_t H, int64_t D, int lg_lph, int lg_hpp, int fblocks, uint64_t seed, uint32_t thr,
+    typename Traits<T>::acc_t keep_scale) {
   using A = typename Traits<T>::acc_t;
   constexpr int VEC = 16 / (int)sizeof(T);
   using P = Pack<T, VEC>;
@@ -252,6 +289,18 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
       uint32_t cc[kAtBatch];
       P kx[kAtBatch], xv[kAtBatch];
       A bb[kAtBatch], sa[kAtBatch];
+      bool kp[kAtBatch];
+      if constexpr (DROP) {
+        const int64_t p0 = c0 + (int64_t)w * lpr + j0;  // the batch's first entry
+        if (lpr >= kAtBatch) {  // p0 is a multiple of four: one call for the batch
+          const U4 r = at_drop_words(seed, p0, h);
+#pragma unroll
+          for (int u = 0; u < kAtBatch; ++u) kp[u] = at_drop_pick(r, u, thr);
+        } else {
+#pragma unroll
+          for (int u = 0; u < kAtBatch; ++u) kp[u] = at_drop_keep(seed, thr, p0 + u, h);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < kAtBatch; ++u) {
         const int j = j0 + u;
@@ -322,8 +371,14 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_tile_kernel(
           const A fa = sc.f_state(), fb_ = sc.f_entry();
           m = sc.mhi;
           l = l * fa + fb_;
+          if constexpr (DROP) {  // (m, l) above are the plain call's: only the accumulator row sees the mask
+            const A fk = kp[u] ? fb_ * keep_scale : A(0);
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[v] = acc[v] * fa + fb_ * Traits<T>::to_acc(xv[u].v[v]);
+            for (int v = 0; v < VEC; ++v) acc[v] = acc[v] * fa + fk * Traits<T>::to_acc(xv[u].v[v]);
+          } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = acc[v] * fa + fb_ * Traits<T>::to_acc(xv[u].v[v]);
+          }
         }
         if (fl[u] & kSegEnd) {
           if (fl[u] & kSegFresh) {
@@ -410,7 +465,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_fixup_kernel(
   }
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool DROP>
 int launch_attention(const AtPlan &p, const AtCall &c) {
   using A = typename Traits<T>::acc_t;
   const int64_t nseg = c.nseg, H = c.H, D = c.D, E = c.E, W = H * D;
@@ -434,10 +489,12 @@ int launch_attention(const AtPlan &p, const AtCall &c) {
   const dim3 tiles((unsigned int)ceil_div(E, (int64_t)kExpandTile), (unsigned int)p.blocks);
   const T *bb = reinterpret_cast<const T *>(c.bias), *qq = reinterpret_cast<const T *>(c.sr),
           *kk = reinterpret_cast<const T *>(c.sc), *xx = reinterpret_cast<const T *>(c.v);
-#define TSAMD_AT_LAUNCH(PACKED, WIDE)                                                                              \
-  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE, MODE>), tiles, block, 0, stream, c.rowptr, c.col, bb, \
-                     c.bias_heads, qq, kk, xx, (A)c.scalar, oo, ll, head_acc, tail_acc, head_ml, tail_ml, head_seg, \
-                     tail_seg, nseg, E, H, D, p.lg_lph, p.lg_hpp, p.fblocks)
+  const uint32_t thr = at_drop_threshold(c.dropout);
+  const A keep_scale = (A)(1.0 / (1.0 - c.dropout));
+#define TSAMD_AT_LAUNCH(PACKED, WIDE)                                                                               \
+  hipLaunchKernelGGL((attention_tile_kernel<T, PACKED, WIDE, MODE, DROP>), tiles, block, 0, stream, c.rowptr, c.col, \
+                     bb, c.bias_heads, qq, kk, xx, (A)c.scalar, oo, ll, head_acc, tail_acc, head_ml, tail_ml,        \
+                     head_seg, tail_seg, nseg, E, H, D, p.lg_lph, p.lg_hpp, p.fblocks, c.seed, thr, keep_scale)
   if (p.fblocks > 1) {
     if (p.generic) TSAMD_AT_LAUNCH(false, true); else TSAMD_AT_LAUNCH(true, true);
   } else {
@@ -453,13 +510,14 @@ int launch_attention(const AtPlan &p, const AtCall &c) {
 }
 
 // ---- backward: p and ds per entry and head ---------------------------------------------------------------------------
-template <typename T, bool PACKED, int MODE>
+template <typename T, bool PACKED, int MODE, bool DROP>
 __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
     const int64_t *__restrict__ row, const int64_t *__restrict__ ptr, const int64_t *__restrict__ ind,
     const T *__restrict__ bias, int64_t bias_heads, const T *__restrict__ q, const T *__restrict__ k,
     const T *__restrict__ x, const T *__restrict__ o, const typename Traits<T>::acc_t *__restrict__ lse,
     const T *__restrict__ go, typename Traits<T>::acc_t scale, T *__restrict__ p_out, T *__restrict__ ds_out,
-    int64_t nseg, int64_t H, int64_t D, int64_t E, int lg_lph, int lg_hpp) {
+    int64_t nseg, int64_t H, int64_t D, int64_t E, int lg_lph, int lg_hpp, uint64_t seed, uint32_t thr,
+    typename Traits<T>::acc_t keep_scale) {
   using A = typename Traits<T>::acc_t;
   constexpr int VEC = 16 / (int)sizeof(T);
   using P = Pack<T, VEC>;
@@ -547,7 +605,13 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
           pv = dv = A(0);
         } else {
           pv = soft_exp(sc - ls);
-          dv = pv * (pd - pl);
+          if constexpr (DROP) {  // pt = p * keep * c goes to p_out; ds = p * (keep * c * dp - delta)
+            const A kc = at_drop_keep(seed, thr, e, h) ? keep_scale : A(0);
+            dv = pv * (kc * pd - pl);
+            pv *= kc;
+          } else {
+            dv = pv * (pd - pl);
+          }
           if constexpr (MODE == kAtAdditive) dv *= ps;  // dz
         }
         p_out[e * H + h] = Traits<T>::from_acc(pv);
@@ -557,17 +621,19 @@ __global__ __launch_bounds__(kAtWaves *kWave) void attention_bw_kernel(
   }
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool DROP>
 int launch_attention_bw(const AtPlan &p, const AtCall &c) {
   using A = typename Traits<T>::acc_t;
+  const uint32_t thr = at_drop_threshold(c.dropout);
+  const A keep_scale = (A)(1.0 / (1.0 - c.dropout));
   const dim3 grid((unsigned int)ceil_div(c.E, (int64_t)kAtWaves * kWave)), block(kAtWaves * kWave);
 #define TSAMD_AT_BW(PACKED)                                                                                         \
-  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED, MODE>), grid, block, 0, c.stream, c.row, c.rowptr, c.col,      \
+  hipLaunchKernelGGL((attention_bw_kernel<T, PACKED, MODE, DROP>), grid, block, 0, c.stream, c.row, c.rowptr, c.col, \
                      reinterpret_cast<const T *>(c.bias), c.bias_heads, reinterpret_cast<const T *>(c.sr),          \
                      reinterpret_cast<const T *>(c.sc), reinterpret_cast<const T *>(c.v),                           \
                      reinterpret_cast<const T *>(c.out), reinterpret_cast<const A *>(c.lse),                        \
                      reinterpret_cast<const T *>(c.grad_out), (A)c.scalar, reinterpret_cast<T *>(c.p_out),          \
-                     reinterpret_cast<T *>(c.d_out), c.nseg, c.H, c.D, c.E, p.lg_lph, p.lg_hpp)
+                     reinterpret_cast<T *>(c.d_out), c.nseg, c.H, c.D, c.E, p.lg_lph, p.lg_hpp, c.seed, thr, keep_scale)
   if (p.generic) TSAMD_AT_BW(false); else TSAMD_AT_BW(true);
 #undef TSAMD_AT_BW
   TSAMD_LAUNCH_CHECK();
@@ -587,6 +653,7 @@ bool at_indexable(int dtype, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, i
 
 // the status of a call the host can decide, or kAtProceed.  include/tsamd.h lists the cases in this order
 int at_check_sizes(const AtCall &c) {
+  if (!at_rate_ok(c.dropout)) return TSAMD_ERR_INVALID;  // only the *_dropout entries can carry one
   if (c.nseg < 0 || c.nsrc < 0 || c.H < 0 || c.D < 0 || c.E < 0) return TSAMD_ERR_INVALID;
   if (!is_float_dtype(c.dtype)) return TSAMD_ERR_UNSUPPORTED;
   if (!at_indexable(c.dtype, c.nseg, c.nsrc, c.H, c.D, c.E)) return TSAMD_ERR_UNSUPPORTED;
@@ -628,8 +695,12 @@ int at_forward(const AtCall &c) {
   const int st = at_check_forward(c);
   if (st != kAtProceed) return st;
   const AtPlan p = at_call_plan(c, kAtFwHeads);
+  const bool drop = c.dropout != 0.0;  // rate 0 keeps every entry at c = 1: the plain kernels, the plain call's bits
   return TSAMD_DISPATCH_FLOAT(c.dtype, [&]() -> int {
-    return c.mode == kAtDot ? launch_attention<scalar_t, kAtDot>(p, c) : launch_attention<scalar_t, kAtAdditive>(p, c);
+    if (c.mode == kAtDot)
+      return drop ? launch_attention<scalar_t, kAtDot, true>(p, c) : launch_attention<scalar_t, kAtDot, false>(p, c);
+    return drop ? launch_attention<scalar_t, kAtAdditive, true>(p, c)
+                : launch_attention<scalar_t, kAtAdditive, false>(p, c);
   });
 }
 
@@ -637,9 +708,12 @@ int at_backward(const AtCall &c) {
   const int st = at_check_backward(c);
   if (st != kAtProceed) return st;
   const AtPlan p = at_call_plan(c, kAtBwHeads);
+  const bool drop = c.dropout != 0.0;
   return TSAMD_DISPATCH_FLOAT(c.dtype, [&]() -> int {
-    return c.mode == kAtDot ? launch_attention_bw<scalar_t, kAtDot>(p, c)
-                            : launch_attention_bw<scalar_t, kAtAdditive>(p, c);
+    if (c.mode == kAtDot)
+      return drop ? launch_attention_bw<scalar_t, kAtDot, true>(p, c) : launch_attention_bw<scalar_t, kAtDot, false>(p, c);
+    return drop ? launch_attention_bw<scalar_t, kAtAdditive, true>(p, c)
+                : launch_attention_bw<scalar_t, kAtAdditive, false>(p, c);
   });
 }
 
@@ -713,4 +787,59 @@ extern "C" int tsamd_gat_attention_heads_bw(int dtype, const int64_t *row, const
   return at_backward({dtype, kAtAdditive, row, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope,
                       const_cast<void *>(out), const_cast<void *>(lse), grad_out, p_out, dz_out, nseg, nsrc, H, D, E,
                       nullptr, 0, reinterpret_cast<hipStream_t>(stream)});
+}
+
+// ---- dropout on the probabilities: the four calls again, with the rate and the seed of the mask after the scalar -------
+extern "C" int tsamd_attention_heads_dropout(int dtype, const int64_t *rowptr, const int64_t *col, const void *bias,
+                                             int64_t bias_heads, const void *q, const void *k, const void *v,
+                                             double scale, double dropout, uint64_t seed, void *out, void *lse,
+                                             int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E,
+                                             void *workspace, size_t workspace_bytes, void *stream) {
+  return at_forward({dtype, kAtDot, nullptr, rowptr, col, bias, bias_heads, q, k, v, scale, out, lse, nullptr, nullptr,
+                     nullptr, nseg, nsrc, H, D, E, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
+                     dropout, seed});
+}
+
+extern "C" int tsamd_gat_attention_heads_dropout(int dtype, const int64_t *rowptr, const int64_t *col,
+                                                 const void *bias, int64_t bias_heads, const void *a_dst,
+                                                 const void *a_src, const void *v, double negative_slope,
+                                                 double dropout, uint64_t seed, void *out, void *lse, int64_t nseg,
+                                                 int64_t nsrc, int64_t H, int64_t D, int64_t E, void *workspace,
+                                                 size_t workspace_bytes, void *stream) {
+  return at_forward({dtype, kAtAdditive, nullptr, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope, out,
+                     lse, nullptr, nullptr, nullptr, nseg, nsrc, H, D, E, workspace, workspace_bytes,
+                     reinterpret_cast<hipStream_t>(stream), dropout, seed});
+}
+
+extern "C" int tsamd_attention_heads_dropout_bw(int dtype, const int64_t *row, const int64_t *rowptr,
+                                                const int64_t *col, const void *bias, int64_t bias_heads, const void *q,
+                                                const void *k, const void *v, const void *out, const void *lse,
+                                                const void *grad_out, double scale, double dropout, uint64_t seed,
+                                                void *p_out, void *ds_out, int64_t nseg, int64_t nsrc, int64_t H,
+                                                int64_t D, int64_t E, void *stream) {
+  return at_backward({dtype, kAtDot, row, rowptr, col, bias, bias_heads, q, k, v, scale, const_cast<void *>(out),
+                      const_cast<void *>(lse), grad_out, p_out, ds_out, nseg, nsrc, H, D, E, nullptr, 0,
+                      reinterpret_cast<hipStream_t>(stream), dropout, seed});
+}
+
+extern "C" int tsamd_gat_attention_heads_dropout_bw(int dtype, const int64_t *row, const int64_t *rowptr,
+                                                    const int64_t *col, const void *bias, int64_t bias_heads,
+                                                    const void *a_dst, const void *a_src, const void *v,
+                                                    const void *out, const void *lse, const void *grad_out,
+                                                    double negative_slope, double dropout, uint64_t seed, void *p_out,
+                                                    void *dz_out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D,
+                                                    int64_t E, void *stream) {
+  return at_backward({dtype, kAtAdditive, row, rowptr, col, bias, bias_heads, a_dst, a_src, v, negative_slope,
+                      const_cast<void *>(out), const_cast<void *>(lse), grad_out, p_out, dz_out, nseg, nsrc, H, D, E,
+                      nullptr, 0, reinterpret_cast<hipStream_t>(stream), dropout, seed});
+}
+
+// host arithmetic only, through the rule the kernels compile: keep[(e - e0) * H + h] of the entries [e0, e0 + n)
+extern "C" int tsamd_attention_dropout_mask(uint64_t seed, double rate, int64_t e0, int64_t n, int64_t H,
+                                            uint8_t *keep) {
+  if (!keep || e0 < 0 || n < 0 || H < 0 || !at_rate_ok(rate)) return TSAMD_ERR_INVALID;
+  const uint32_t thr = at_drop_threshold(rate);
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t h = 0; h < H; ++h) keep[i * H + h] = at_drop_keep(seed, thr, e0 + i, h) ? 1 : 0;
+  return TSAMD_OK;
 }

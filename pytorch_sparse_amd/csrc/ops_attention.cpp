@@ -102,6 +102,12 @@ const Fused kDotScores = {true, "q", "tsamd_attention_heads", "tsamd_attention_h
 const Fused kGatScores = {false, "v", "tsamd_gat_attention_heads", "tsamd_gat_attention_heads_bw"};
 const char *op_name(const char *entry) { return entry + 6; }
 
+// dropout on the probabilities: the rate and the seed of its mask (include/tsamd.h)
+void check_dropout(double dropout, int64_t seed) {
+  TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "dropout must be a rate in [0, 1), got ", dropout);
+  TORCH_CHECK(seed >= 0, "seed must not be negative, got ", seed);
+}
+
 // the bias against the pattern and the operand `like` -> made contiguous (undefined without one)
 Tensor check_bias(const OptTensor &bias, int64_t E, int64_t H, const Tensor &like, const char *like_name) {
   Tensor b;
@@ -167,9 +173,10 @@ Tensor check_gat_attention(const Tensor &rowptr, const Tensor &col, const OptTen
 }
 
 // fused scores -> softmax over the row -> aggregation (csrc/attention.hip) -> (out [M, H, D], lse [M, H]); the operands
-// have passed their checker, b is its bias
+// have passed their checker, b is its bias.  The *_dropout entries serve every call: a rate of 0 is the plain call
 std::tuple<Tensor, Tensor> fused_forward(const Fused &m, Tensor rowptr, Tensor col, const Tensor &b, Tensor sr,
-                                         Tensor sc, Tensor v, double scalar) {
+                                         Tensor sc, Tensor v, double scalar, double dropout, int64_t seed) {
+  check_dropout(dropout, seed);
   const int64_t M = sr.size(0), N = v.size(0), H = v.size(1), D = v.size(2), E = col.numel();
   c10::hip::HIPGuard guard(v.get_device());
   sr = sr.contiguous();
@@ -186,20 +193,22 @@ std::tuple<Tensor, Tensor> fused_forward(const Fused &m, Tensor rowptr, Tensor c
   }
   const int dt = dtype_code(v);
   Tensor ws = workspace(tsamd_attention_heads_workspace_bytes(dt, H, D, E), v);
-  const auto call = m.dot ? tsamd_attention_heads : tsamd_gat_attention_heads;
+  const auto call = m.dot ? tsamd_attention_heads_dropout : tsamd_gat_attention_heads_dropout;
   check_status(call(dt, rowptr.data_ptr<int64_t>(), col.data_ptr<int64_t>(), b.defined() ? b.data_ptr() : nullptr,
-                    b.defined() && b.dim() == 2 ? H : 1, sr.data_ptr(), sc.data_ptr(), v.data_ptr(), scalar,
-                    out.data_ptr(), lse.data_ptr(), M, N, H, D, E, ws.data_ptr(), (size_t)ws.numel(),
+                    b.defined() && b.dim() == 2 ? H : 1, sr.data_ptr(), sc.data_ptr(), v.data_ptr(), scalar, dropout,
+                    (uint64_t)seed, out.data_ptr(), lse.data_ptr(), M, N, H, D, E, ws.data_ptr(), (size_t)ws.numel(),
                     current_stream(v)),
                m.fw);
   return std::make_tuple(out, lse);
 }
 
 // p = e(s - lse[row]) and ds = p * (<grad_out[row], v[col]> - <grad_out[row], out[row]>), for the additive scores
-// dz = ds * (z > 0 ? 1 : negative_slope) in its place -> two [E, H] arrays
+// dz = ds * (z > 0 ? 1 : negative_slope) in its place -> two [E, H] arrays.  With dropout: pt = p * keep * c and
+// ds = p * (keep * c * <grad_out[row], v[col]> - <grad_out[row], out[row]>)
 std::tuple<Tensor, Tensor> fused_backward(const Fused &m, const OptTensor &row, Tensor rowptr, Tensor col,
                                           const Tensor &b, Tensor sr, Tensor sc, Tensor v, Tensor out, Tensor lse,
-                                          Tensor grad_out, double scalar) {
+                                          Tensor grad_out, double scalar, double dropout, int64_t seed) {
+  check_dropout(dropout, seed);
   if (row.has_value()) check_index(row.value(), "row");
   check_heads_operand(out, "out");
   check_heads_operand(grad_out, "grad_out");
@@ -240,39 +249,41 @@ std::tuple<Tensor, Tensor> fused_backward(const Fused &m, const OptTensor &row, 
   Tensor p = torch::empty({E, H}, v.options().requires_grad(false));
   Tensor d = torch::empty({E, H}, v.options().requires_grad(false));
   if (p.numel() == 0) return std::make_tuple(p, d);
-  const auto call = m.dot ? tsamd_attention_heads_bw : tsamd_gat_attention_heads_bw;
+  const auto call = m.dot ? tsamd_attention_heads_dropout_bw : tsamd_gat_attention_heads_dropout_bw;
   check_status(call(dtype_code(v), row.has_value() ? r.data_ptr<int64_t>() : nullptr, rowptr.data_ptr<int64_t>(),
                     col.data_ptr<int64_t>(), b.defined() ? b.data_ptr() : nullptr, b.defined() && b.dim() == 2 ? H : 1,
                     sr.data_ptr(), sc.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(),
-                    scalar, p.data_ptr(), d.data_ptr(), M, N, H, D, E, current_stream(v)),
+                    scalar, dropout, (uint64_t)seed, p.data_ptr(), d.data_ptr(), M, N, H, D, E, current_stream(v)),
                m.bw);
   return std::make_tuple(p, d);
 }
 
 std::tuple<Tensor, Tensor> attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor q, Tensor k, Tensor v,
-                                           double scale) {
+                                           double scale, double dropout, int64_t seed) {
   Tensor b = check_attention(rowptr, col, bias, q, k, v);
-  return fused_forward(kDotScores, rowptr, col, b, q, k, v, scale);
+  return fused_forward(kDotScores, rowptr, col, b, q, k, v, scale, dropout, seed);
 }
 
 std::tuple<Tensor, Tensor> attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias, Tensor q,
                                               Tensor k, Tensor v, Tensor out, Tensor lse, Tensor grad_out,
-                                              double scale) {
+                                              double scale, double dropout, int64_t seed) {
   Tensor b = check_attention(rowptr, col, bias, q, k, v);
-  return fused_backward(kDotScores, row, rowptr, col, b, q, k, v, out, lse, grad_out, scale);
+  return fused_backward(kDotScores, row, rowptr, col, b, q, k, v, out, lse, grad_out, scale, dropout, seed);
 }
 
 std::tuple<Tensor, Tensor> gat_attention_heads(Tensor rowptr, Tensor col, OptTensor bias, Tensor a_dst, Tensor a_src,
-                                               Tensor v, double negative_slope) {
+                                               Tensor v, double negative_slope, double dropout, int64_t seed) {
   Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
-  return fused_forward(kGatScores, rowptr, col, b, a_dst, a_src, v, negative_slope);
+  return fused_forward(kGatScores, rowptr, col, b, a_dst, a_src, v, negative_slope, dropout, seed);
 }
 
 std::tuple<Tensor, Tensor> gat_attention_heads_bw(OptTensor row, Tensor rowptr, Tensor col, OptTensor bias,
                                                   Tensor a_dst, Tensor a_src, Tensor v, Tensor out, Tensor lse,
-                                                  Tensor grad_out, double negative_slope) {
+                                                  Tensor grad_out, double negative_slope, double dropout,
+                                                  int64_t seed) {
   Tensor b = check_gat_attention(rowptr, col, bias, a_dst, a_src, v, negative_slope);
-  return fused_backward(kGatScores, row, rowptr, col, b, a_dst, a_src, v, out, lse, grad_out, negative_slope);
+  return fused_backward(kGatScores, row, rowptr, col, b, a_dst, a_src, v, out, lse, grad_out, negative_slope, dropout,
+                        seed);
 }
 
 }  // namespace
@@ -288,15 +299,16 @@ static auto registry_attention =
         .op("tsamd::spmm_heads(Tensor ptr, Tensor ind, Tensor? perm, Tensor? value, Tensor x, int nseg) -> Tensor",
             &spmm_heads)
         .op("tsamd::attention_heads(Tensor rowptr, Tensor col, Tensor? bias, Tensor q, Tensor k, Tensor v, "
-            "float scale) -> (Tensor, Tensor)",
+            "float scale, float dropout=0.0, int seed=0) -> (Tensor, Tensor)",
             &attention_heads)
         .op("tsamd::attention_heads_bw(Tensor? row, Tensor rowptr, Tensor col, Tensor? bias, Tensor q, Tensor k, "
-            "Tensor v, Tensor out, Tensor lse, Tensor grad_out, float scale) -> (Tensor, Tensor)",
+            "Tensor v, Tensor out, Tensor lse, Tensor grad_out, float scale, float dropout=0.0, int seed=0) -> "
+            "(Tensor, Tensor)",
             &attention_heads_bw)
         .op("tsamd::gat_attention_heads(Tensor rowptr, Tensor col, Tensor? bias, Tensor a_dst, Tensor a_src, Tensor v, "
-            "float negative_slope) -> (Tensor, Tensor)",
+            "float negative_slope, float dropout=0.0, int seed=0) -> (Tensor, Tensor)",
             &gat_attention_heads)
         .op("tsamd::gat_attention_heads_bw(Tensor? row, Tensor rowptr, Tensor col, Tensor? bias, Tensor a_dst, "
-            "Tensor a_src, Tensor v, Tensor out, Tensor lse, Tensor grad_out, float negative_slope) -> "
-            "(Tensor, Tensor)",
+            "Tensor a_src, Tensor v, Tensor out, Tensor lse, Tensor grad_out, float negative_slope, float dropout=0.0, "
+            "int seed=0) -> (Tensor, Tensor)",
             &gat_attention_heads_bw);
