@@ -977,7 +977,7 @@ int tsamd_spspmm_numeric(int dtype, const int64_t *rowptrA, const int64_t *colA,
 
 /* ------------------------------------------------------------------------ *
  * SpSpMM value gradients (csrc/spspmm_bw.hip).  Serves the autograd node of tsamd::spspmm
- * (csrc/ops_storage.cpp), i.e. SparseTensor @ SparseTensor (pytorch_sparse_amd/matmul.py) and the
+ * (csrc/ops_spspmm.cpp), i.e. SparseTensor @ SparseTensor (pytorch_sparse_amd/matmul.py) and the
  * functional spspmm (pytorch_sparse_amd/spspmm.py); the reference's torch.sparse.mm is differentiable
  * in both value tensors but torch_sparse/matmul.py:102 drops the graph at C._values().
  * With C = A * B as tsamd_spspmm_numeric leaves it (structural pattern, rows sorted by column, explicit

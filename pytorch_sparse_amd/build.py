@@ -25,7 +25,7 @@ ARCH = 'gfx950'
 
 HIP_SOURCES = ['api.hip', 'spmm.hip', 'spmm_min.hip', 'spmm_max.hip', 'spmm_partial.hip', 'spmm_bw.hip', 'spmm_ref_order.hip', 'spmm_coo.hip', 'convert.hip', 'scan.hip', 'sort.hip',
                'coalesce.hip', 'spspmm.hip', 'spspmm_bw.hip', 'select.hip', 'sample.hip', 'hgt_sample.hip', 'segreduce.hip', 'softmax.hip', 'sddmm.hip', 'spmm_heads.hip', 'attention.hip', 'partition.hip', 'rcm.hip']
-OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp']
+OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_spspmm.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp']
 
 
 def _hipcc():

@@ -260,6 +260,18 @@ static inline size_t acc_size(int dtype) {
     }                                                                      \
   }()
 
+// The same as a function: f(T{}) for the floating type behind `dtype` (a generic lambda; T = decltype of its argument)
+template <typename F>
+int dispatch_float(int dtype, F &&f) {
+  switch (dtype) {
+    case TSAMD_F32: return f(float{});
+    case TSAMD_F64: return f(double{});
+    case TSAMD_F16: return f(f16_t{});
+    case TSAMD_BF16: return f(bf16_t{});
+    default: return TSAMD_ERR_UNSUPPORTED;
+  }
+}
+
 static inline bool is_float_dtype(int dtype) {
   return dtype == TSAMD_F32 || dtype == TSAMD_F64 || dtype == TSAMD_F16 || dtype == TSAMD_BF16;
 }

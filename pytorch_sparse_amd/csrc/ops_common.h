@@ -1,4 +1,4 @@
-// Shared helpers of the torch operator glue (ops_spmm.cpp, ops_storage.cpp, ops_sample*.cpp): argument
+// Shared helpers of the torch operator glue (ops_spmm.cpp, ops_storage.cpp, ops_spspmm.cpp, ops_sample*.cpp): argument
 // checks, dtype / reduce codes, workspaces, the current HIP stream.  Host-only C++ (g++), links torch.
 #pragma once
 
@@ -82,5 +82,7 @@ inline bool needs_grad(const Tensor &t) { return torch::autograd::any_variable_r
 // defined in ops_storage.cpp, used by the samplers as well
 std::tuple<Tensor, Tensor, Tensor, Tensor> select_segments(Tensor ptr, Tensor ind, Tensor idx, bool want_seg,
                                                            bool want_ind);
+// defined in ops_storage.cpp, used by the SpSpMM backward (ops_spspmm.cpp) as well
+std::tuple<Tensor, Tensor, Tensor> sort_coo(Tensor row, Tensor col, int64_t M, int64_t N, bool index);
 
 }  // namespace tsamd_ops

@@ -90,3 +90,15 @@ int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, int64_t *tota
 }
 
 }  // namespace tsamd
+
+using namespace tsamd;
+
+extern "C" size_t tsamd_exclusive_scan_workspace_bytes(int64_t n) { return scan_workspace_bytes(n); }
+
+extern "C" int tsamd_exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, int64_t *total,
+                                        void *workspace, size_t workspace_bytes, void *stream) {
+  if (n < 0 || (n > 0 && (!in || !out))) return TSAMD_ERR_INVALID;
+  if (n > kScanTile && (!workspace || workspace_bytes < scan_workspace_bytes(n)))
+    return TSAMD_ERR_WORKSPACE;
+  return exclusive_scan_i64(in, out, n, total, workspace, reinterpret_cast<hipStream_t>(stream));
+}

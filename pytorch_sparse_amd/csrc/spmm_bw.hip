@@ -749,18 +749,6 @@ int launch_value_bw_masked(const int64_t *row, const int64_t *rowptr, const int6
   return TSAMD_OK;
 }
 
-// f(T{}) for the floating type behind `dtype`; integer dtypes have no gradient
-template <typename F>
-int dispatch_float(int dtype, F &&f) {
-  switch (dtype) {
-    case TSAMD_F32: return f(float{});
-    case TSAMD_F64: return f(double{});
-    case TSAMD_F16: return f(f16_t{});
-    case TSAMD_BF16: return f(bf16_t{});
-    default: return TSAMD_ERR_UNSUPPORTED;
-  }
-}
-
 // What the pull backward is given in place of arg_out: the winners as ids of either width, or as the records the forward
 // left (spmm_internal.h).  An accessor answers NULL for every kind but its own, so no route can read one as another.
 struct Winners {

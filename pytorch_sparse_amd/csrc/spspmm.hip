@@ -971,8 +971,9 @@ constexpr int kLgRange = sizeof(typename Traits<T>::acc_t) == 4 ? TSAMD_SPSPMM_L
 #ifndef TSAMD_SPSPMM_PAIRS
 #define TSAMD_SPSPMM_PAIRS 1
 #endif
+constexpr bool pairs_layout(size_t esize) { return TSAMD_SPSPMM_PAIRS && esize == 4; }  // (the host: Route::pairs)
 template <typename T>
-constexpr bool kPairs = TSAMD_SPSPMM_PAIRS && sizeof(T) == 4;
+constexpr bool kPairs = pairs_layout(sizeof(T));
 template <typename T>
 __device__ __forceinline__ void bin_load(const uint32_t *__restrict__ bcol, const T *__restrict__ bval, int64_t p, bool want_val,
                                          uint32_t &c, typename Traits<T>::acc_t &v) {
@@ -1683,8 +1684,40 @@ __global__ __launch_bounds__(64) void spspmm_smallbin_accum_kernel(
   }
 }
 
-// Every decision the host takes from N (columns of B) and the value type, in one place: numeric_rows,
-// tsamd_spspmm_symbolic, carve_large and the large-row stages read it, tsamd_spspmm_route() exports it
+// ---- the host layer: one call descriptor, one status ladder, one workspace plan, the stage drivers, thin C entry points
+
+// One call of the symbolic or of the numeric stage, as its entry point was given it.
+struct SpspmmCall {
+  int dtype;
+  const int64_t *rowptrA, *colA;
+  const void *valA;  // may be NULL, like valB
+  const int64_t *rowptrB;
+  const uint32_t *colB;  // the 32-bit copy tsamd_spspmm_plan made
+  const void *valB;
+  int64_t M, N;
+  const int64_t *prod, *bins;  // (tsamd_spspmm_plan)
+  int64_t n_medium, n_large, P_large;
+  void *workspace;
+  size_t workspace_bytes;
+  hipStream_t stream;
+  int64_t *nnzC;  // symbolic: the output
+  const int64_t *rowptrC;  // numeric: the scanned counts, and the outputs
+  int64_t *colC;
+  void *valC;
+  bool bin_values;     // symbolic: bin the large rows' products with their values
+  bool values_binned;  // numeric: it did
+
+  const int64_t *large_rows() const { return bins + M; }  // the second list of the plan
+};
+enum SpspmmStage { kSymbolic, kNumeric };
+constexpr int kSpProceed = -1;  // no status yet: the call has work and its arguments are in order
+
+// bytes of a value as the host lays it out: every size below comes from here.  (Anything but fp64 counts as 4 bytes:
+// tsamd_spspmm_workspace_bytes answers for any dtype; the stages refuse what is neither fp32 nor fp64.)
+size_t value_size(int dtype) { return dtype == TSAMD_F64 ? 8 : 4; }
+
+// Every decision the host takes from N (columns of B) and the value type, in one place: the stage drivers,
+// carve_large and the launch helpers read it, tsamd_spspmm_route() exports its first eight fields
 // (tests/test_spspmm_route.py pins the thresholds).  Pure host arithmetic, no HIP call.
 struct Route {
   int lg_range;      // log2 of the columns per range of the large-row path (value type)
@@ -1695,16 +1728,20 @@ struct Route {
   int passes;        // 8-bit radix passes over a column id
   bool narrow_hash;  // symbolic hash sets: 24-bit multiply
   bool large_ok;     // rows beyond kMediumCap products are supported at this N
+  size_t esize;      // value_size() of the call
+  bool pairs;        // binned products: (column, value) pairs in one array (kPairs<T> of the kernels)
 };
 
-Route spspmm_route(size_t esize, int64_t N) {
+Route spspmm_route(int dtype, int64_t N) {
   Route r;
+  r.esize = value_size(dtype);
+  r.pairs = pairs_layout(r.esize);
   int bits = 1;
   while (bits < 32 && ((int64_t)1 << bits) < N) ++bits;
   r.passes = (bits + 7) / 8;
   r.small_pairs = bits + kIdxBits > 32;
   r.narrow_hash = N <= ((int64_t)1 << 24);  // hash_slot: 24-bit multiply
-  r.lg_range = esize == 8 ? TSAMD_SPSPMM_LG_RANGE - 1 : TSAMD_SPSPMM_LG_RANGE;
+  r.lg_range = r.esize == 8 ? TSAMD_SPSPMM_LG_RANGE - 1 : TSAMD_SPSPMM_LG_RANGE;
   r.nr = (int)((N + ((int64_t)1 << r.lg_range) - 1) >> r.lg_range);
   if (r.nr < 1) r.nr = 1;
   r.sub = r.nr <= kMaxRanges / (kLargeThreads / 64) ? kLargeThreads / 64 : 1;
@@ -1713,24 +1750,51 @@ Route spspmm_route(size_t esize, int64_t N) {
   return r;
 }
 
+// The status of a stage call the host can decide, or kSpProceed.  The two stages test in different orders and callers
+// see the order through the status of a call that is wrong twice (tests/test_spspmm_status.py): numeric looks at the
+// dtype first, symbolic only after the pointers and the counts -- so symbolic(f16, M = 0) is OK, numeric's is not.
+int spspmm_status(const SpspmmCall &c, SpspmmStage stage) {
+  const bool dtype_ok = c.dtype == TSAMD_F32 || c.dtype == TSAMD_F64;
+  if (stage == kNumeric && !dtype_ok) return TSAMD_ERR_UNSUPPORTED;
+  if (c.M < 0 || c.N < 0 || c.N >= ((int64_t)1 << 32) - 1 || c.M >= ((int64_t)1 << 31)) return TSAMD_ERR_UNSUPPORTED;
+  if (c.M == 0) return TSAMD_OK;
+  // colA / colB may be NULL for operands without entries (every row then has zero products)
+  if (!c.rowptrA || !c.rowptrB || !c.prod || !c.bins) return TSAMD_ERR_INVALID;
+  if (stage == kSymbolic ? !c.nnzC : !c.rowptrC) return TSAMD_ERR_INVALID;
+  if (c.n_medium < 0 || c.n_large < 0 || c.n_medium + c.n_large > c.M) return TSAMD_ERR_INVALID;
+  if (!dtype_ok) return TSAMD_ERR_UNSUPPORTED;
+  if (c.n_large > 0 &&
+      (!c.workspace || c.workspace_bytes < tsamd_spspmm_workspace_bytes(c.dtype, c.n_large, c.P_large, c.N)))
+    return TSAMD_ERR_WORKSPACE;
+  return kSpProceed;
+}
+
+// The workspace of the large rows, and the route it was laid out for.
 struct LargeWs {
-  int64_t *hist;      // [n_large * nr * sub + 1] products per (bin, wave segment), scanned in place -> segment offsets
-  int64_t *bin_off;   // [n_large * nr + 1] offset of every bin = of its first segment
-  int sub;            // wave segments per bin: 4 (reproducible bin order) or 1 (too many ranges for the LDS counters)
-  int64_t *bin_cnt;   // [n_large * nr + 1] distinct columns per bin, scanned at numeric time
-  uint32_t *bcol;     // [P_large] column inside its range
-  void *bval;         // [P_large] value (numeric stage)
+  Route route;
+  int64_t ntask;      // n_large * nr (row, range) bins
+  int64_t *hist;      // [nseg() + 1] products per (bin, wave segment), scanned in place -> segment offsets
+  int64_t *bin_off;   // [ntask + 1] offset of every bin = of its first segment
+  int64_t *bin_cnt;   // [ntask + 1] distinct columns per bin, scanned at numeric time
+  uint32_t *bcol;     // [P_large] column inside its range (route.pairs: the pairs)
+  void *bval;         // [P_large] value (numeric stage; NULL with route.pairs)
   unsigned long long *queue;  // ticket counters of the persistent kernels
   int64_t *lists;             // [2 * ntask] small bins | big bins (spspmm_large_classify_kernel)
   unsigned long long *counts; // [2] their numbers
   void *scan_ws;
-  int nr, lg_range;
-  bool off_lds, large_ok;  // (spspmm_route)
-  int64_t ntask;
+
+  int64_t nseg() const { return ntask * route.sub; }
+  const int64_t *small_list() const { return lists; }
+  const unsigned long long *n_small() const { return counts; }
+  const int64_t *big_list() const { return lists + ntask; }
+  const int64_t *n_big() const { return reinterpret_cast<const int64_t *>(counts + 1); }
+  // resident waves of the small-bin kernels (grid-stride over the list)
+  unsigned int small_grid() const { return (unsigned int)(ntask < kSmallBinWaves ? ntask : kSmallBinWaves); }
+  int col_stride() const { return route.pairs ? 2 : 1; }  // of bcol, for the kernels that read the columns only
 };
 
-// One layout for both value types of a call sequence: the range is the one of the value type.
-size_t carve_large(void *base, int64_t n_large, int64_t P_large, int64_t N, size_t esize, LargeWs *w) {
+// One layout for both value types of a call sequence: the range is the one of the value type.  base == NULL: the size only.
+size_t carve_large(void *base, const Route &route, int64_t n_large, int64_t P_large, LargeWs *w) {
   char *p = reinterpret_cast<char *>(base);
   size_t off = 0;
   auto take = [&](size_t bytes) -> void * {
@@ -1739,42 +1803,29 @@ size_t carve_large(void *base, int64_t n_large, int64_t P_large, int64_t N, size
     return r;
   };
   LargeWs l;
-  const Route route = spspmm_route(esize, N);
-  l.lg_range = route.lg_range;
-  l.nr = route.nr;
-  l.sub = route.sub;
-  l.off_lds = route.off_lds;
-  l.large_ok = route.large_ok;
-  l.ntask = n_large * (int64_t)l.nr;
-  l.hist = (int64_t *)take(8 * (size_t)(l.ntask * l.sub + 1));
+  l.route = route;
+  l.ntask = n_large * (int64_t)route.nr;
+  l.hist = (int64_t *)take(8 * (size_t)(l.nseg() + 1));
   l.bin_off = (int64_t *)take(8 * (size_t)(l.ntask + 1));
   l.bin_cnt = (int64_t *)take(8 * (size_t)(l.ntask + 1));
-  if (TSAMD_SPSPMM_PAIRS && esize == 4) {  // (column, value) pairs in one array
+  if (route.pairs) {  // (column, value) pairs in one array
     l.bcol = (uint32_t *)take(8 * (size_t)P_large);
     l.bval = nullptr;
   } else {
     l.bcol = (uint32_t *)take(4 * (size_t)P_large);
-    l.bval = take(esize * (size_t)P_large);
+    l.bval = take(route.esize * (size_t)P_large);
   }
   l.queue = (unsigned long long *)take(64);
   l.lists = (int64_t *)take(16 * (size_t)l.ntask);
   l.counts = (unsigned long long *)take(64);
-  l.scan_ws = take(scan_workspace_bytes(l.ntask * l.sub + 1));
+  l.scan_ws = take(scan_workspace_bytes(l.nseg() + 1));
   if (w) *w = l;
   return off;
 }
 
-unsigned int persistent_blocks();
-// one-wave workgroups of the reproducible accumulation: as many as the LDS of the device holds at once
-template <typename T>
-unsigned int persistent_wave_blocks() {
-  const size_t lds = sizeof(typename Traits<T>::acc_t) * ((size_t)1 << kLgRange<T>) + 4 * (((size_t)1 << kLgRange<T>) / 32) + 4096 + 128;
-  const unsigned int per_cu = (unsigned int)((size_t)160 * 1024 / lds);
-  return persistent_blocks() / TSAMD_SPSPMM_ACCUM_WGS * (per_cu < 1 ? 1 : per_cu);
-}
-
-unsigned int persistent_blocks() {
-  static int cus = 0;  // the LDS footprint allows TSAMD_SPSPMM_ACCUM_WGS workgroups per CU
+// Grid of a persistent kernel that fits `per_cu` workgroups on a CU.
+unsigned int persistent_blocks(unsigned int per_cu) {
+  static int cus = 0;
   if (cus == 0) {
     int dev = 0;
     hipDeviceProp_t prop;
@@ -1783,157 +1834,192 @@ unsigned int persistent_blocks() {
         prop.multiProcessorCount > 0)
       cus = prop.multiProcessorCount;
   }
-  return (unsigned int)cus * TSAMD_SPSPMM_ACCUM_WGS;
+  return (unsigned int)cus * per_cu;
+}
+
+// one-wave workgroups of the reproducible accumulation: as many as the LDS of the device holds at once
+unsigned int persistent_wave_blocks(const Route &r) {
+  const size_t cols = (size_t)1 << r.lg_range;
+  const size_t lds = r.esize * cols + 4 * (cols / 32) + 4096 + 128;
+  const unsigned int per_cu = (unsigned int)((size_t)160 * 1024 / lds);
+  return persistent_blocks(per_cu < 1 ? 1 : per_cu);
 }
 
 // dynamic LDS of the hist / bin kernels: their nr * sub counters
-static size_t large_counter_bytes(const LargeWs &w) {
-  const size_t n = (size_t)w.nr * (size_t)w.sub;
+size_t large_counter_bytes(const Route &r) {
+  const size_t n = (size_t)r.nr * (size_t)r.sub;
   // (the bin kernel keeps an int64 offset beside every cursor when there are at most kOffLdsMax of them; the hist kernel
   // uses the first part only)
-  const size_t off_bytes = w.off_lds ? n * sizeof(int64_t) : 0;
+  const size_t off_bytes = r.off_lds ? n * sizeof(int64_t) : 0;
   return (((n + 1) & ~(size_t)1) * sizeof(int) + off_bytes + 255) / 256 * 256;
+}
+
+// the products of the large rows into their bins, columns only or with their values
+template <typename T, bool WITH_VAL>
+int launch_large_bin(const SpspmmCall &c, const LargeWs &w) {
+  const Route &r = w.route;
+  const T *va = WITH_VAL ? static_cast<const T *>(c.valA) : nullptr;
+  const T *vb = WITH_VAL ? static_cast<const T *>(c.valB) : nullptr;
+  hipLaunchKernelGGL((spspmm_large_bin_kernel<T, WITH_VAL>), dim3((unsigned int)c.n_large), dim3(kLargeThreads),
+                     large_counter_bytes(r), c.stream, c.rowptrA, c.colA, va, c.rowptrB, c.colB, vb, c.large_rows(),
+                     r.lg_range, r.nr, r.sub, (const int64_t *)w.hist, w.bcol,
+                     WITH_VAL ? static_cast<T *>(w.bval) : nullptr);
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
 }
 
 // valA / valB given (either may be NULL): the products are binned WITH their values, so that the numeric
 // stage does not have to expand the large rows a third time.
 template <typename T>
-int symbolic_large(const int64_t *rowptrA, const int64_t *colA, const void *valA, const int64_t *rowptrB,
-                   const uint32_t *colB, const void *valB, bool with_values, const int64_t *rows,
-                   int64_t n_large, int64_t P_large, int64_t N, int64_t *nnzC, void *workspace,
-                   hipStream_t stream) {
-  constexpr size_t esize = sizeof(T);
+int symbolic_large(const SpspmmCall &c, const Route &r) {
+  if (!r.large_ok) return TSAMD_ERR_UNSUPPORTED;
   LargeWs w;
-  carve_large(workspace, n_large, P_large, N, esize, &w);
-  if (!w.large_ok) return TSAMD_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(spspmm_large_hist_kernel, dim3((unsigned int)n_large), dim3(kLargeThreads),
-                     large_counter_bytes(w), stream,
-                     rowptrA, colA, rowptrB, colB, rows, w.lg_range, w.nr, w.sub, w.hist);
+  carve_large(c.workspace, r, c.n_large, c.P_large, &w);
+  const int64_t *rows = c.large_rows();
+  unsigned long long *nnzC = reinterpret_cast<unsigned long long *>(c.nnzC);
+  hipLaunchKernelGGL(spspmm_large_hist_kernel, dim3((unsigned int)c.n_large), dim3(kLargeThreads),
+                     large_counter_bytes(r), c.stream, c.rowptrA, c.colA, c.rowptrB, c.colB, rows, r.lg_range, r.nr,
+                     r.sub, w.hist);
   TSAMD_LAUNCH_CHECK();
-  TSAMD_HIP_TRY(hipMemsetAsync(w.hist + w.ntask * w.sub, 0, 8, stream));
-  int st = exclusive_scan_i64(w.hist, w.hist, w.ntask * w.sub + 1, nullptr, w.scan_ws, stream);
+  TSAMD_HIP_TRY(hipMemsetAsync(w.hist + w.nseg(), 0, 8, c.stream));
+  int st = exclusive_scan_i64(w.hist, w.hist, w.nseg() + 1, nullptr, w.scan_ws, c.stream);
   if (st != TSAMD_OK) return st;
-  hipLaunchKernelGGL(spspmm_bin_offsets_kernel, dim3((unsigned int)ceil_div(w.ntask + 1, 256)), dim3(256), 0, stream,
-                     (const int64_t *)w.hist, w.sub, w.ntask, w.bin_off);
+  hipLaunchKernelGGL(spspmm_bin_offsets_kernel, dim3((unsigned int)ceil_div(w.ntask + 1, 256)), dim3(256), 0, c.stream,
+                     (const int64_t *)w.hist, r.sub, w.ntask, w.bin_off);
   TSAMD_LAUNCH_CHECK();
-  if (with_values)
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
-                       stream, rowptrA, colA, reinterpret_cast<const T *>(valA), rowptrB, colB,
-                       reinterpret_cast<const T *>(valB), rows, w.lg_range, w.nr, w.sub, (const int64_t *)w.hist,
-                       w.bcol, reinterpret_cast<T *>(w.bval));
-  else
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, false>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
-                       stream, rowptrA, colA, (const T *)nullptr, rowptrB, colB, (const T *)nullptr, rows,
-                       w.lg_range, w.nr, w.sub, (const int64_t *)w.hist, w.bcol, (T *)nullptr);
+  st = c.bin_values ? launch_large_bin<T, true>(c, w) : launch_large_bin<T, false>(c, w);
+  if (st != TSAMD_OK) return st;
+  TSAMD_HIP_TRY(hipMemsetAsync(w.queue, 0, 64, c.stream));
+  TSAMD_HIP_TRY(hipMemsetAsync(w.counts, 0, 64, c.stream));
+  hipLaunchKernelGGL(spspmm_large_classify_kernel, dim3((unsigned int)ceil_div(c.n_large, 256)), dim3(256), 0, c.stream,
+                     (const int64_t *)w.bin_off, c.n_large, r.nr, w.ntask, w.lists, w.counts, w.bin_cnt);
   TSAMD_LAUNCH_CHECK();
-  TSAMD_HIP_TRY(hipMemsetAsync(w.queue, 0, 64, stream));
-  TSAMD_HIP_TRY(hipMemsetAsync(w.counts, 0, 64, stream));
-  hipLaunchKernelGGL(spspmm_large_classify_kernel, dim3((unsigned int)ceil_div(n_large, 256)), dim3(256), 0, stream,
-                     (const int64_t *)w.bin_off, n_large, w.nr, w.ntask, w.lists, w.counts, w.bin_cnt);
-  TSAMD_LAUNCH_CHECK();
-  const unsigned int small_grid = (unsigned int)(w.ntask < kSmallBinWaves ? w.ntask : kSmallBinWaves);
-  hipLaunchKernelGGL(spspmm_smallbin_count_kernel, dim3(small_grid), dim3(64), 0, stream, rows, w.nr,
-                     (const int64_t *)w.lists, (const unsigned long long *)w.counts, (const int64_t *)w.bin_off,
-                     (const uint32_t *)w.bcol, kPairs<T> ? 2 : 1, w.bin_cnt,
-                     reinterpret_cast<unsigned long long *>(nnzC));
+  hipLaunchKernelGGL(spspmm_smallbin_count_kernel, dim3(w.small_grid()), dim3(64), 0, c.stream, rows, r.nr,
+                     w.small_list(), w.n_small(), (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, w.col_stride(),
+                     w.bin_cnt, nnzC);
   TSAMD_LAUNCH_CHECK();
   // (the count kernel's footprint is its 4 KB bitmap: 8 persistent workgroups per CU instead of the accumulation's 4 --
   // a bin costs ~8 us of dependent round trips and barriers whatever its size, so bins in flight are what it needs:
   // SQ counters, profiles/r05_sq_counters.md: VALU pipe 0.12, waiting 0.92)
-  hipLaunchKernelGGL(spspmm_large_count_kernel, dim3(persistent_blocks() / TSAMD_SPSPMM_ACCUM_WGS * TSAMD_SPSPMM_COUNT_WGS), dim3(kAccumThreads), 0, stream, rows,
-                     w.nr, (const int64_t *)(w.lists + w.ntask), (const int64_t *)(w.counts + 1),
-                     (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, kPairs<T> ? 2 : 1, (1 << w.lg_range) / 32, w.bin_cnt,
-                     reinterpret_cast<unsigned long long *>(nnzC), w.queue);
+  hipLaunchKernelGGL(spspmm_large_count_kernel, dim3(persistent_blocks(TSAMD_SPSPMM_COUNT_WGS)), dim3(kAccumThreads), 0,
+                     c.stream, rows, r.nr, w.big_list(), w.n_big(), (const int64_t *)w.bin_off,
+                     (const uint32_t *)w.bcol, w.col_stride(), (1 << r.lg_range) / 32, w.bin_cnt, nnzC, w.queue);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
 }
 
 template <typename T>
-int numeric_large(const int64_t *rowptrA, const int64_t *colA, const void *valA, const int64_t *rowptrB,
-                  const uint32_t *colB, const void *valB, const int64_t *rows, int64_t n_large,
-                  int64_t P_large, int64_t N, const int64_t *rowptrC, int64_t *colC, void *valC,
-                  bool values_binned, void *workspace, hipStream_t stream) {
+int numeric_large(const SpspmmCall &c, const Route &r) {
+  if (!r.large_ok) return TSAMD_ERR_UNSUPPORTED;
   LargeWs w;
-  carve_large(workspace, n_large, P_large, N, sizeof(T), &w);
-  if (!w.large_ok) return TSAMD_ERR_UNSUPPORTED;
-  T *bv = reinterpret_cast<T *>(w.bval);
-  if (valC != nullptr && !values_binned) {  // the symbolic stage binned the columns only; the values follow the same offsets
-    hipLaunchKernelGGL((spspmm_large_bin_kernel<T, true>), dim3((unsigned int)n_large), dim3(kLargeThreads), large_counter_bytes(w),
-                       stream, rowptrA, colA, reinterpret_cast<const T *>(valA), rowptrB, colB,
-                       reinterpret_cast<const T *>(valB), rows, w.lg_range, w.nr, w.sub, (const int64_t *)w.hist,
-                       w.bcol, bv);
-    TSAMD_LAUNCH_CHECK();
+  carve_large(c.workspace, r, c.n_large, c.P_large, &w);
+  const int64_t *rows = c.large_rows();
+  const T *bv = static_cast<const T *>(w.bval);
+  T *vc = static_cast<T *>(c.valC);
+  if (vc != nullptr && !c.values_binned) {  // the symbolic stage binned the columns only; the values follow the same offsets
+    const int st = launch_large_bin<T, true>(c, w);
+    if (st != TSAMD_OK) return st;
   }
-  TSAMD_HIP_TRY(hipMemsetAsync(w.bin_cnt + w.ntask, 0, 8, stream));
-  int st = exclusive_scan_i64(w.bin_cnt, w.bin_cnt, w.ntask + 1, nullptr, w.scan_ws, stream);
+  TSAMD_HIP_TRY(hipMemsetAsync(w.bin_cnt + w.ntask, 0, 8, c.stream));
+  int st = exclusive_scan_i64(w.bin_cnt, w.bin_cnt, w.ntask + 1, nullptr, w.scan_ws, c.stream);
   if (st != TSAMD_OK) return st;
-  TSAMD_HIP_TRY(hipMemsetAsync(w.queue, 0, 64, stream));
+  TSAMD_HIP_TRY(hipMemsetAsync(w.queue, 0, 64, c.stream));
   // (the lists of small / big bins were left in the workspace by the symbolic stage)
-  const unsigned int small_grid = (unsigned int)(w.ntask < kSmallBinWaves ? w.ntask : kSmallBinWaves);
-  hipLaunchKernelGGL((spspmm_smallbin_accum_kernel<T>), dim3(small_grid), dim3(64), 0, stream, rows, w.nr,
-                     (const int64_t *)w.lists, (const unsigned long long *)w.counts, (const int64_t *)w.bin_off,
-                     (const uint32_t *)w.bcol, (const T *)bv, (const int64_t *)w.bin_cnt, rowptrC, colC,
-                     reinterpret_cast<T *>(valC));
+  hipLaunchKernelGGL((spspmm_smallbin_accum_kernel<T>), dim3(w.small_grid()), dim3(64), 0, c.stream, rows, r.nr,
+                     w.small_list(), w.n_small(), (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, bv,
+                     (const int64_t *)w.bin_cnt, c.rowptrC, c.colC, vc);
   TSAMD_LAUNCH_CHECK();
-  if (w.sub > 1)  // bins in a reproducible order: sum them in that order, one wave per bin
-    hipLaunchKernelGGL((spspmm_large_accum_wave_kernel<T>), dim3(persistent_wave_blocks<T>()), dim3(64), 0, stream,
-                       rows, w.nr, (const int64_t *)(w.lists + w.ntask), (const int64_t *)(w.counts + 1),
-                       (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, (const T *)bv, (const int64_t *)w.bin_cnt,
-                       rowptrC, colC, reinterpret_cast<T *>(valC), w.queue);
+  if (r.sub > 1)  // bins in a reproducible order: sum them in that order, one wave per bin
+    hipLaunchKernelGGL((spspmm_large_accum_wave_kernel<T>), dim3(persistent_wave_blocks(r)), dim3(64), 0, c.stream, rows,
+                       r.nr, w.big_list(), w.n_big(), (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, bv,
+                       (const int64_t *)w.bin_cnt, c.rowptrC, c.colC, vc, w.queue);
   else
-    hipLaunchKernelGGL((spspmm_large_accum_kernel<T>), dim3(persistent_blocks()), dim3(kAccumThreads), 0, stream,
-                       rows, w.nr, (const int64_t *)(w.lists + w.ntask), (const int64_t *)(w.counts + 1),
-                       (const int64_t *)w.bin_off, (const uint32_t *)w.bcol, (const T *)bv, (const int64_t *)w.bin_cnt,
-                       rowptrC, colC, reinterpret_cast<T *>(valC), w.queue);
+    hipLaunchKernelGGL((spspmm_large_accum_kernel<T>), dim3(persistent_blocks(TSAMD_SPSPMM_ACCUM_WGS)),
+                       dim3(kAccumThreads), 0, c.stream, rows, r.nr, w.big_list(), w.n_big(), (const int64_t *)w.bin_off,
+                       (const uint32_t *)w.bcol, bv, (const int64_t *)w.bin_cnt, c.rowptrC, c.colC, vc, w.queue);
   TSAMD_LAUNCH_CHECK();
   return TSAMD_OK;
 }
 
 template <typename T>
-int numeric_rows(const int64_t *rowptrA, const int64_t *colA, const void *valA, const int64_t *rowptrB,
-                 const uint32_t *colB, const void *valB, const int64_t *prod, const int64_t *bins,
-                 int64_t M, int64_t N, int64_t n_medium, const int64_t *rowptrC, int64_t *colC, void *valC,
-                 hipStream_t stream) {
-  const Route route = spspmm_route(sizeof(T), N);
-  const int passes = route.passes;  // 8-bit radix passes over the column ids
-  const T *va = reinterpret_cast<const T *>(valA);
-  const T *vb = reinterpret_cast<const T *>(valB);
-  T *vc = reinterpret_cast<T *>(valC);
-  {  // small rows: all M rows in natural order, the kernel skips the others
-    if (!route.small_pairs) {
-      // (one workgroup per row: a persistent launch pipelined across rows measured slower,
-      // profiles/r04_ab_spspmm_row_pipe.log)
-      hipLaunchKernelGGL((spspmm_numeric_small_kernel<T>), dim3((unsigned int)M), dim3(64), 0, stream,
-                         rowptrA, colA, va, rowptrB, colB, vb, prod, rowptrC, colC, vc);
-    } else
-      hipLaunchKernelGGL((spspmm_numeric_pairs_kernel<T, 64, kSmallCap>), dim3((unsigned int)M), dim3(64),
-                         0, stream, rowptrA, colA, va, rowptrB, colB, vb, prod, bins, rowptrC, colC, vc,
-                         passes);
-    TSAMD_LAUNCH_CHECK();
-  }
-  if (n_medium > 0) {
-    hipLaunchKernelGGL((spspmm_numeric_pairs_kernel<T, 256, kMediumCap>), dim3((unsigned int)n_medium),
-                       dim3(256), 0, stream, rowptrA, colA, va, rowptrB, colB, vb, prod, bins, rowptrC,
-                       colC, vc, passes);
+int numeric_rows(const SpspmmCall &c, const Route &r) {
+  const T *va = static_cast<const T *>(c.valA);
+  const T *vb = static_cast<const T *>(c.valB);
+  T *vc = static_cast<T *>(c.valC);
+  // small rows: all M rows in natural order, the kernel skips the others
+  if (!r.small_pairs) {
+    // (one workgroup per row: a persistent launch pipelined across rows measured slower,
+    // profiles/r04_ab_spspmm_row_pipe.log)
+    hipLaunchKernelGGL((spspmm_numeric_small_kernel<T>), dim3((unsigned int)c.M), dim3(64), 0, c.stream, c.rowptrA,
+                       c.colA, va, c.rowptrB, c.colB, vb, c.prod, c.rowptrC, c.colC, vc);
+  } else
+    hipLaunchKernelGGL((spspmm_numeric_pairs_kernel<T, 64, kSmallCap>), dim3((unsigned int)c.M), dim3(64), 0, c.stream,
+                       c.rowptrA, c.colA, va, c.rowptrB, c.colB, vb, c.prod, c.bins, c.rowptrC, c.colC, vc, r.passes);
+  TSAMD_LAUNCH_CHECK();
+  if (c.n_medium > 0) {
+    hipLaunchKernelGGL((spspmm_numeric_pairs_kernel<T, 256, kMediumCap>), dim3((unsigned int)c.n_medium), dim3(256), 0,
+                       c.stream, c.rowptrA, c.colA, va, c.rowptrB, c.colB, vb, c.prod, c.bins, c.rowptrC, c.colC, vc,
+                       r.passes);
     TSAMD_LAUNCH_CHECK();
   }
   return TSAMD_OK;
+}
+
+// exact counts of `rows` small (THREADS = 64: all M, the kernel skips the others) or medium rows in an LDS hash set
+template <int THREADS, int LOG_T>
+int launch_symbolic_rows(const SpspmmCall &c, const Route &r, int64_t rows) {
+  auto launch = [&](auto narrow) {
+    hipLaunchKernelGGL((spspmm_symbolic_kernel<THREADS, LOG_T, decltype(narrow)::value>), dim3((unsigned int)rows),
+                       dim3(THREADS), 0, c.stream, c.rowptrA, c.colA, c.rowptrB, c.colB, c.prod, c.bins, c.nnzC);
+  };
+  if (r.narrow_hash) launch(std::true_type{});
+  else launch(std::false_type{});
+  TSAMD_LAUNCH_CHECK();
+  return TSAMD_OK;
+}
+
+// fp32 / fp64 of a call spspmm_status() let through: f(T{}), once per entry point
+template <typename F>
+int dispatch_value(const SpspmmCall &c, F &&f) {
+  return dispatch_float(c.dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if constexpr (Traits<T>::kNarrow) return TSAMD_ERR_UNSUPPORTED;  // (no kernel is built for them)
+    else {
+      // Route::esize (value_size of the dtype code) sizes the scratch and the LDS of kernels compiled for T
+      static_assert(sizeof(T) == sizeof(typename Traits<T>::acc_t), "the host sizes accumulators by the value size");
+      if (value_size(c.dtype) != sizeof(T)) return TSAMD_ERR_UNSUPPORTED;
+      return f(t);
+    }
+  });
+}
+
+int spspmm_symbolic(const SpspmmCall &c) {
+  int st = spspmm_status(c, kSymbolic);
+  if (st != kSpProceed) return st;
+  const Route r = spspmm_route(c.dtype, c.N);
+  TSAMD_HIP_TRY(hipMemsetAsync(c.nnzC, 0, sizeof(int64_t) * (size_t)c.M, c.stream));
+  st = launch_symbolic_rows<64, 10>(c, r, c.M);
+  if (st == TSAMD_OK && c.n_medium > 0) st = launch_symbolic_rows<256, kMediumLogT>(c, r, c.n_medium);
+  if (st != TSAMD_OK || c.n_large == 0) return st;
+  return dispatch_value(c, [&](auto t) { return symbolic_large<decltype(t)>(c, r); });
+}
+
+int spspmm_numeric(const SpspmmCall &c) {
+  const int status = spspmm_status(c, kNumeric);
+  if (status != kSpProceed) return status;
+  const Route r = spspmm_route(c.dtype, c.N);
+  return dispatch_value(c, [&](auto t) {
+    using T = decltype(t);
+    const int st = numeric_rows<T>(c, r);
+    if (st != TSAMD_OK || c.n_large == 0) return st;
+    return numeric_large<T>(c, r);
+  });
 }
 
 }  // namespace
 }  // namespace tsamd
 
 using namespace tsamd;
-
-extern "C" size_t tsamd_exclusive_scan_workspace_bytes(int64_t n) { return scan_workspace_bytes(n); }
-
-extern "C" int tsamd_exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, int64_t *total,
-                                        void *workspace, size_t workspace_bytes, void *stream) {
-  if (n < 0 || (n > 0 && (!in || !out))) return TSAMD_ERR_INVALID;
-  if (n > kScanTile && (!workspace || workspace_bytes < scan_workspace_bytes(n)))
-    return TSAMD_ERR_WORKSPACE;
-  return exclusive_scan_i64(in, out, n, total, workspace, reinterpret_cast<hipStream_t>(stream));
-}
 
 extern "C" int tsamd_spspmm_plan(const int64_t *rowptrA, const int64_t *colA,
                                  const int64_t *rowptrB, const int64_t *colB64, int64_t nnzB, int64_t M,
@@ -1961,14 +2047,14 @@ extern "C" int tsamd_spspmm_plan(const int64_t *rowptrA, const int64_t *colA,
 
 extern "C" size_t tsamd_spspmm_workspace_bytes(int dtype, int64_t n_large, int64_t P_large, int64_t N) {
   if (n_large <= 0) return 0;
-  return carve_large(nullptr, n_large, P_large, N, dtype == TSAMD_F64 ? 8 : 4, nullptr);
+  return carve_large(nullptr, spspmm_route(dtype, N), n_large, P_large, nullptr);
 }
 
 extern "C" int tsamd_spspmm_route(int dtype, int64_t N, int64_t out[8]) {
   if (!out) return TSAMD_ERR_INVALID;
   if (dtype != TSAMD_F32 && dtype != TSAMD_F64) return TSAMD_ERR_UNSUPPORTED;
   if (N < 0 || N >= ((int64_t)1 << 32) - 1) return TSAMD_ERR_UNSUPPORTED;
-  const Route r = spspmm_route(dtype == TSAMD_F64 ? 8 : 4, N);
+  const Route r = spspmm_route(dtype, N);
   out[0] = r.lg_range;
   out[1] = r.nr;
   out[2] = r.sub;
@@ -1986,42 +2072,10 @@ extern "C" int tsamd_spspmm_symbolic(int dtype, const int64_t *rowptrA, const in
                                      const int64_t *prod, const int64_t *bins,
                                      int64_t n_medium, int64_t n_large, int64_t P_large,
                                      int64_t *nnzC, void *workspace, size_t workspace_bytes,
-                                     void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (M < 0 || N < 0 || N >= ((int64_t)1 << 32) - 1 || M >= ((int64_t)1 << 31)) return TSAMD_ERR_UNSUPPORTED;
-  if (M == 0) return TSAMD_OK;
-  // colA / colB may be NULL for operands without entries (every row then has zero products)
-  if (!nnzC || !rowptrA || !rowptrB || !prod || !bins) return TSAMD_ERR_INVALID;
-  if (n_medium < 0 || n_large < 0 || n_medium + n_large > M) return TSAMD_ERR_INVALID;
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F64) return TSAMD_ERR_UNSUPPORTED;
-  if (n_large > 0 && (!workspace || workspace_bytes < tsamd_spspmm_workspace_bytes(dtype, n_large, P_large, N)))
-    return TSAMD_ERR_WORKSPACE;
-  TSAMD_HIP_TRY(hipMemsetAsync(nnzC, 0, sizeof(int64_t) * (size_t)M, stream));
-  const bool narrow_cols = spspmm_route(dtype == TSAMD_F64 ? 8 : 4, N).narrow_hash;
-  if (narrow_cols)
-    hipLaunchKernelGGL((spspmm_symbolic_kernel<64, 10, true>), dim3((unsigned int)M), dim3(64), 0, stream, rowptrA,
-                       colA, rowptrB, colB, prod, bins, nnzC);
-  else
-    hipLaunchKernelGGL((spspmm_symbolic_kernel<64, 10, false>), dim3((unsigned int)M), dim3(64), 0, stream, rowptrA,
-                       colA, rowptrB, colB, prod, bins, nnzC);
-  TSAMD_LAUNCH_CHECK();
-  if (n_medium > 0) {
-    if (narrow_cols)
-      hipLaunchKernelGGL((spspmm_symbolic_kernel<256, kMediumLogT, true>), dim3((unsigned int)n_medium), dim3(256), 0,
-                         stream, rowptrA, colA, rowptrB, colB, prod, bins, nnzC);
-    else
-      hipLaunchKernelGGL((spspmm_symbolic_kernel<256, kMediumLogT, false>), dim3((unsigned int)n_medium), dim3(256), 0,
-                         stream, rowptrA, colA, rowptrB, colB, prod, bins, nnzC);
-    TSAMD_LAUNCH_CHECK();
-  }
-  if (n_large > 0) {
-    if (dtype == TSAMD_F64)
-      return symbolic_large<double>(rowptrA, colA, valA, rowptrB, colB, valB, bin_values != 0, bins + M, n_large,
-                                    P_large, N, nnzC, workspace, stream);
-    return symbolic_large<float>(rowptrA, colA, valA, rowptrB, colB, valB, bin_values != 0, bins + M, n_large,
-                                 P_large, N, nnzC, workspace, stream);
-  }
-  return TSAMD_OK;
+                                     void *stream) {
+  return spspmm_symbolic({dtype, rowptrA, colA, valA, rowptrB, colB, valB, M, N, prod, bins, n_medium, n_large, P_large,
+                          workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), nnzC, nullptr, nullptr,
+                          nullptr, bin_values != 0, false});
 }
 
 extern "C" int tsamd_spspmm_numeric(int dtype, const int64_t *rowptrA, const int64_t *colA,
@@ -2030,26 +2084,8 @@ extern "C" int tsamd_spspmm_numeric(int dtype, const int64_t *rowptrA, const int
                                     const int64_t *bins, int64_t n_medium, int64_t n_large,
                                     int64_t P_large, const int64_t *rowptrC, int64_t *colC,
                                     void *valC, int values_binned, void *workspace,
-                                    size_t workspace_bytes, void *stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (dtype != TSAMD_F32 && dtype != TSAMD_F64) return TSAMD_ERR_UNSUPPORTED;
-  if (M < 0 || N < 0 || N >= ((int64_t)1 << 32) - 1 || M >= ((int64_t)1 << 31)) return TSAMD_ERR_UNSUPPORTED;
-  if (M == 0) return TSAMD_OK;
-  if (!rowptrA || !rowptrB || !prod || !bins || !rowptrC) return TSAMD_ERR_INVALID;
-  if (n_medium < 0 || n_large < 0 || n_medium + n_large > M) return TSAMD_ERR_INVALID;
-  if (n_large > 0 && (!workspace || workspace_bytes < tsamd_spspmm_workspace_bytes(dtype, n_large, P_large, N)))
-    return TSAMD_ERR_WORKSPACE;
-  int st;
-  if (dtype == TSAMD_F32)
-    st = numeric_rows<float>(rowptrA, colA, valA, rowptrB, colB, valB, prod, bins, M, N, n_medium, rowptrC,
-                             colC, valC, stream);
-  else
-    st = numeric_rows<double>(rowptrA, colA, valA, rowptrB, colB, valB, prod, bins, M, N, n_medium, rowptrC,
-                              colC, valC, stream);
-  if (st != TSAMD_OK || n_large == 0) return st;
-  if (dtype == TSAMD_F32)
-    return numeric_large<float>(rowptrA, colA, valA, rowptrB, colB, valB, bins + M, n_large, P_large, N,
-                                rowptrC, colC, valC, values_binned != 0, workspace, stream);
-  return numeric_large<double>(rowptrA, colA, valA, rowptrB, colB, valB, bins + M, n_large, P_large, N,
-                               rowptrC, colC, valC, values_binned != 0, workspace, stream);
+                                    size_t workspace_bytes, void *stream) {
+  return spspmm_numeric({dtype, rowptrA, colA, valA, rowptrB, colB, valB, M, N, prod, bins, n_medium, n_large, P_large,
+                         workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), nullptr, rowptrC, colC, valC,
+                         false, values_binned != 0});
 }
