@@ -601,6 +601,46 @@ int tsamd_spmm_heads(int dtype, const int64_t *ptr, const int64_t *ind, const in
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Fused multi-aggregation (csrc/spmm_multi.hip): several reductions of the products y_e = value[e] * x[col[e], :] of
+ * every row in one gather of x.  mask is a non-empty set of tsamd_multi bits; out[m, r, f] is at
+ * out + m * stride_m + r * stride_r + f (strides in elements), slot r = the rank of the reduction's bit in mask.
+ * x [N, F] contiguous, value [E] or NULL (all ones), argmin / argmax [M, F] int64 or NULL (written only when MIN / MAX
+ * is in the mask; the entry id of the first winner, E for none).  sum, mean, min, max as tsamd_spmm computes them (a
+ * row without entries gives 0; min / max compare the product rounded to the element type with strict compares from
+ * the largest / lowest finite value, so a NaN product never wins); var is the population variance of the products --
+ * shifted sums per piece, pieces merged by M2 = M2a + M2b + delta^2 na nb / (na + nb), never E[y^2] - E[y]^2 -- and
+ * std its root, both 0 for a row without entries.  fp32 accumulation (fp64 for float64), one rounding on the store.
+ * Entry-balanced like tsamd_spmm_heads, whose lane map and chunk length it shares; no atomics, no host sync, three
+ * launches (fill of the rows without entries, tile, fix-up), deterministic.
+ * Status, in this order: a negative size or stride, or a mask that is 0 or has other bits, TSAMD_ERR_INVALID; a
+ * non-floating dtype, or M / F >= 2^31, N / E >= 2^32 or F > 65535 * 64, TSAMD_ERR_UNSUPPORTED; M * F == 0 TSAMD_OK;
+ * a null out TSAMD_ERR_INVALID; E == 0 TSAMD_OK with out zero-filled; a null rowptr / col / x or N == 0
+ * TSAMD_ERR_INVALID; a workspace that is missing, smaller than tsamd_spmm_multi_workspace_bytes() or off a 256-byte
+ * boundary TSAMD_ERR_WORKSPACE.
+ *   tsamd_spmm_multi_route (host arithmetic only): out[0] route: 0 packets (F * itemsize a multiple of 16, the
+ *   strides whole packets, x and out on a 16-byte boundary), 1 generic; out[1] elements per lane; out[2] lanes per
+ *   row; out[3] groups (chunks) side by side in a wave; out[4] entries per chunk = 8 * out[2] (a function of dtype
+ *   and F alone); out[5] entries per workgroup tile (2048); out[6] the compiled set: 1 moments, 2 extrema, 3 both;
+ *   out[7] column blocks.
+ *   workspace = align256(8 * acc * F * nchunks) [moments] + align256(4 * acc * F * nchunks) + align256(16 * F *
+ *   nchunks) [extrema] + 2 * align256(8 * nchunks), nchunks = ceil(E / out[4]), acc = 8 for float64, else 4.
+ * ------------------------------------------------------------------------ */
+typedef enum {
+  TSAMD_MULTI_SUM = 1,
+  TSAMD_MULTI_MEAN = 2,
+  TSAMD_MULTI_MIN = 4,
+  TSAMD_MULTI_MAX = 8,
+  TSAMD_MULTI_VAR = 16,
+  TSAMD_MULTI_STD = 32
+} tsamd_multi;
+int tsamd_spmm_multi_route(int dtype, int mask, int64_t F, const void *x, const void *out, int64_t stride_m,
+                           int64_t stride_r, int64_t out_route[8]);
+size_t tsamd_spmm_multi_workspace_bytes(int dtype, int mask, int64_t M, int64_t F, int64_t E);
+int tsamd_spmm_multi(int dtype, int mask, const int64_t *rowptr, const int64_t *col, const void *value, const void *x,
+                     void *out, int64_t stride_m, int64_t stride_r, int64_t *argmin, int64_t *argmax, int64_t M,
+                     int64_t N, int64_t F, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Fused attention over a pattern (csrc/attention.hip): scores, softmax over the row and aggregation in one pass.
  * (rowptr, col) is the CSR order of the E entries; q [nseg, H, D], k and v [nsrc, H, D], out [nseg, H, D],
  * lse [nseg, H] in the accumulator type (float, double for float64).  bias is NULL or holds one element of the

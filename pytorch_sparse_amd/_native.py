@@ -33,6 +33,7 @@ SYMBOLS = [
     'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
     'tsamd_segment_softmax_route', 'tsamd_segment_softmax_workspace_bytes', 'tsamd_segment_softmax', 'tsamd_segment_softmax_bw',
     'tsamd_sddmm_heads_route', 'tsamd_sddmm_heads', 'tsamd_spmm_heads_route', 'tsamd_spmm_heads_workspace_bytes', 'tsamd_spmm_heads',
+    'tsamd_spmm_multi_route', 'tsamd_spmm_multi_workspace_bytes', 'tsamd_spmm_multi',
     'tsamd_attention_heads_route', 'tsamd_attention_heads_workspace_bytes', 'tsamd_attention_heads', 'tsamd_attention_heads_bw',
     'tsamd_gat_attention_heads', 'tsamd_gat_attention_heads_bw',
     'tsamd_attention_heads_dropout', 'tsamd_attention_heads_dropout_bw', 'tsamd_gat_attention_heads_dropout',
@@ -110,6 +111,9 @@ def lib():
         L.tsamd_spmm_heads_workspace_bytes.argtypes = [ctypes.c_int, i64, i64, i64, i64]
         L.tsamd_spmm_heads_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_spmm_heads.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
+        L.tsamd_spmm_multi_route.argtypes = [ctypes.c_int, ctypes.c_int, i64, vp, vp, i64, i64, i64p]
+        L.tsamd_spmm_multi_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, i64, i64, i64]
+        L.tsamd_spmm_multi_workspace_bytes.restype = ctypes.c_size_t
         L.tsamd_attention_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, vp, vp, i64p]
         L.tsamd_attention_heads_workspace_bytes.argtypes = [ctypes.c_int, i64, i64, i64]
         L.tsamd_attention_heads_workspace_bytes.restype = ctypes.c_size_t

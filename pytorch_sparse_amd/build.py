@@ -24,8 +24,11 @@ OBJDIR = os.path.join(ROOT, 'build', 'obj')
 ARCH = 'gfx950'
 
 HIP_SOURCES = ['api.hip', 'spmm.hip', 'spmm_min.hip', 'spmm_max.hip', 'spmm_partial.hip', 'spmm_bw.hip', 'spmm_ref_order.hip', 'spmm_coo.hip', 'convert.hip', 'scan.hip', 'sort.hip',
-               'coalesce.hip', 'spspmm.hip', 'spspmm_bw.hip', 'select.hip', 'sample.hip', 'hgt_sample.hip', 'segreduce.hip', 'softmax.hip', 'sddmm.hip', 'spmm_heads.hip', 'attention.hip', 'partition.hip', 'rcm.hip']
-OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_spspmm.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp']
+               'coalesce.hip', 'spspmm.hip', 'spspmm_bw.hip', 'select.hip', 'sample.hip', 'hgt_sample.hip', 'segreduce.hip', 'softmax.hip', 'sddmm.hip', 'spmm_heads.hip', 'spmm_multi.hip', 'attention.hip', 'partition.hip', 'rcm.hip']
+OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_spspmm.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp', 'ops_spmm_multi.cpp']
+# per-source flags.  spmm_multi.hip: no packed fp32 arithmetic -- every add and fma of the moment sums is a scalar
+# instruction in the order the source states, in all three instantiations
+HIP_EXTRA_FLAGS = {'spmm_multi.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _hipcc():
@@ -79,7 +82,7 @@ def build_kernels(verbose=True, force=False):
         objs.append(o)
         deps = [s] + headers
         if force or _newer(o, deps):
-            jobs.append([hipcc] + flags + ['-c', s, '-o', o])
+            jobs.append([hipcc] + flags + HIP_EXTRA_FLAGS.get(src, []) + ['-c', s, '-o', o])
     if jobs:
         if verbose:
             print('[build] hipcc: %d translation unit(s) for %s' % (len(jobs), ARCH), flush=True)
