@@ -17,6 +17,12 @@
  *     device buffer of at least that size (256-byte aligned);
  *   - the return value is a tsamd_status; TSAMD_ERR_HIP means a HIP runtime
  *     call failed (tsamd_last_hip_error() returns the hipError_t).
+ *
+ * The Python binding (pytorch_sparse_amd/_native.py) reads its ctypes
+ * declarations from the prototypes below, so each stays in the plain form
+ * `ret tsamd_name(type name, ...);` with int, int64_t, uint64_t, uint32_t,
+ * size_t, double, float and pointers (or `type name[n]`) as parameter types:
+ * no macros, typedef'd scalars or function pointers in a prototype.
  */
 #ifndef TSAMD_H_
 #define TSAMD_H_

@@ -6,63 +6,64 @@ it: a missing library, a CPU tensor or a non-zero status raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TSAMD_LIB') or os.path.join(_HERE, 'lib', 'libtsamd.so')
 
-# Every symbol include/tsamd.h declares (tests check that all of them resolve).
-SYMBOLS = [
-    'tsamd_hip_version', 'tsamd_build_flags', 'tsamd_last_hip_error', 'tsamd_status_string',
-    'tsamd_spmm_workspace_bytes', 'tsamd_spmm_hot_rows_layout', 'tsamd_spmm_hot_blocks_layout', 'tsamd_spmm_hot_block_min', 'tsamd_spmm_route', 'tsamd_spmm', 'tsamd_spmm_reference_order', 'tsamd_spmm_column_order', 'tsamd_spmm_order_layout', 'tsamd_spmm_permuted', 'tsamd_spmm_profiled',
-    'tsamd_spmm_partial_workspace_bytes', 'tsamd_spmm_partial',
-    'tsamd_spmm_operand_cache_bytes', 'tsamd_spmm_cached_workspace_bytes', 'tsamd_spmm_cached',
-    'tsamd_spmm_hints_bytes', 'tsamd_spmm_hints_layout', 'tsamd_spmm_hinted',
-    'tsamd_spmm_minmax_arg32', 'tsamd_spmm_minmax_bw_csc_arg32',
-    'tsamd_spmm_minmax_records_in_forward', 'tsamd_spmm_minmax_records_bytes', 'tsamd_spmm_minmax_records_workspace_bytes', 'tsamd_spmm_minmax_records',
-    'tsamd_spmm_minmax_winrec', 'tsamd_spmm_minmax_bw_csc_records_workspace_bytes', 'tsamd_spmm_minmax_bw_csc_records',
-    'tsamd_gather_rows', 'tsamd_relabel_ids', 'tsamd_spmm_relabelled_workspace_bytes', 'tsamd_spmm_relabelled',
-    'tsamd_spmm_coo_small_supported', 'tsamd_spmm_coo_small',
-    'tsamd_spmm_value_bw',
-    'tsamd_spmm_minmax_bw_workspace_bytes', 'tsamd_spmm_minmax_bw',
-    'tsamd_spmm_minmax_bw_csc_workspace_bytes', 'tsamd_spmm_minmax_bw_csc', 'tsamd_spmm_minmax_bw_route',
-    'tsamd_ind2ptr', 'tsamd_ptr2ind',
-    'tsamd_coo_order', 'tsamd_coo_check', 'tsamd_sort_rank_mode', 'tsamd_sort_route', 'tsamd_sort_header', 'tsamd_sort_coalesce_workspace_bytes', 'tsamd_sort_coalesce', 'tsamd_sort_coalesce_reduce', 'tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo', 'tsamd_sort_coo_auto', 'tsamd_sort_coo_probed', 'tsamd_sort_coo_values',
-    'tsamd_coalesce_workspace_bytes', 'tsamd_coalesce_index', 'tsamd_segment_reduce',
-    'tsamd_segment_reduce_balanced_workspace_bytes', 'tsamd_segment_reduce_balanced',
-    'tsamd_segment_softmax_route', 'tsamd_segment_softmax_workspace_bytes', 'tsamd_segment_softmax', 'tsamd_segment_softmax_bw',
-    'tsamd_sddmm_heads_route', 'tsamd_sddmm_heads', 'tsamd_spmm_heads_route', 'tsamd_spmm_heads_workspace_bytes', 'tsamd_spmm_heads',
-    'tsamd_spmm_multi_route', 'tsamd_spmm_multi_workspace_bytes', 'tsamd_spmm_multi',
-    'tsamd_attention_heads_route', 'tsamd_attention_heads_workspace_bytes', 'tsamd_attention_heads', 'tsamd_attention_heads_bw',
-    'tsamd_gat_attention_heads', 'tsamd_gat_attention_heads_bw',
-    'tsamd_attention_heads_dropout', 'tsamd_attention_heads_dropout_bw', 'tsamd_gat_attention_heads_dropout',
-    'tsamd_gat_attention_heads_dropout_bw', 'tsamd_attention_dropout_mask',
-    'tsamd_exclusive_scan_workspace_bytes', 'tsamd_exclusive_scan_i64',
-    'tsamd_spspmm_route', 'tsamd_spspmm_plan', 'tsamd_spspmm_workspace_bytes', 'tsamd_spspmm_symbolic', 'tsamd_spspmm_numeric',
-    'tsamd_spspmm_bw_route', 'tsamd_spspmm_bw_plan_workspace_bytes', 'tsamd_spspmm_bw_workspace_bytes', 'tsamd_spspmm_bw_plan', 'tsamd_spspmm_value_bw',
-    'tsamd_index_route', 'tsamd_select_workspace_bytes', 'tsamd_select_plan', 'tsamd_select_fill',
-    'tsamd_filter_workspace_bytes', 'tsamd_filter_plan', 'tsamd_filter_apply',
-    'tsamd_filter_tiles_workspace_bytes', 'tsamd_filter_count', 'tsamd_filter_write',
-    'tsamd_scatter_rows',
-    'tsamd_num_diag', 'tsamd_non_diag_mask', 'tsamd_insert_diag', 'tsamd_set_diag_apply',
-    'tsamd_random_walk', 'tsamd_sample_workspace_bytes', 'tsamd_sample_plan', 'tsamd_sample_draw',
-    'tsamd_relabel_workspace_bytes', 'tsamd_relabel_plan', 'tsamd_relabel_apply', 'tsamd_relabel_seed',
-    'tsamd_relabel_extend', 'tsamd_temporal_mark', 'tsamd_temporal_redraw_workspace_bytes', 'tsamd_temporal_redraw',
-    'tsamd_temporal_relabel_workspace_bytes', 'tsamd_temporal_relabel', 'tsamd_temporal_emit', 'tsamd_subset_assoc',
-    'tsamd_ego_seeds', 'tsamd_ego_plan_workspace_bytes', 'tsamd_ego_plan', 'tsamd_ego_draw', 'tsamd_ego_roots',
-    'tsamd_ego_induced_workspace_bytes', 'tsamd_ego_induced_count', 'tsamd_ego_induced_write',
-    'tsamd_hgt_seen', 'tsamd_hgt_budget_add', 'tsamd_hgt_select_workspace_bytes', 'tsamd_hgt_select', 'tsamd_hgt_keys',
-    'tsamd_hgt_commit', 'tsamd_hgt_check_ids',
-    'tsamd_partition_edges', 'tsamd_partition_vertex_weights', 'tsamd_partition_match_workspace_bytes',
-    'tsamd_partition_match', 'tsamd_partition_bfs_init', 'tsamd_partition_bfs_seed', 'tsamd_partition_bfs_step',
-    'tsamd_partition_assign_workspace_bytes', 'tsamd_partition_assign', 'tsamd_partition_part_weights',
-    'tsamd_partition_conn_workspace_bytes', 'tsamd_partition_conn', 'tsamd_partition_recount',
-    'tsamd_partition_commit_workspace_bytes', 'tsamd_partition_commit', 'tsamd_partition_apply', 'tsamd_partition_cut',
-    'tsamd_partition_keep_better', 'tsamd_partition_balance',
-    'tsamd_rcm_limits', 'tsamd_rcm_degree', 'tsamd_rcm_relabel', 'tsamd_rcm_begin', 'tsamd_rcm_small',
-    'tsamd_rcm_level_workspace_bytes', 'tsamd_rcm_level_plan', 'tsamd_rcm_level_run', 'tsamd_rcm_finish',
-]
+# the header the signatures are read from: $TSAMD_HEADER, else the copy an installed package carries, else the tree's
+_SHIPPED = os.path.join(_HERE, 'include', 'tsamd.h')
+HEADER_PATH = os.environ.get('TSAMD_HEADER') or (
+    _SHIPPED if os.path.exists(_SHIPPED) else os.path.join(os.path.dirname(_HERE), 'include', 'tsamd.h'))
+
+_SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'uint32_t': ctypes.c_uint32,
+            'size_t': ctypes.c_size_t, 'double': ctypes.c_double, 'float': ctypes.c_float}
+_PROTOTYPE = re.compile(r'([\w\s*]+?)\b(tsamd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;')
+
+
+def _ctype(decl, name, param):
+    """The ctypes type of one parameter declaration (with or without its name) or of a return type."""
+    words = [w for w in decl.replace('*', ' * ').split() if w != 'const']
+    if param:
+        if '*' in words or decl.rstrip().endswith(']'):
+            return ctypes.c_void_p  # takes ints, None, c_void_p, ctypes arrays and pointers, byref()
+        words = words[:-1] or words  # drop the parameter's name
+    elif words in (['void'], ['char', '*']):
+        return None if words == ['void'] else ctypes.c_char_p
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise TypeError('include/tsamd.h: %s: no ctypes mapping for `%s`' % (name, ' '.join(decl.split())))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """{name: (restype, [argtypes])} for every ``ret tsamd_name(params);`` of the header's text.  A type outside the
+    table above and a prototype this does not read (one that is not in that plain form) both raise."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*|^[ \t]*#[^\n]*', ' ', text, flags=re.M)
+    table = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        params = [] if params.strip() == 'void' else params.split(',')
+        table[name] = (_ctype(ret, name, False), [_ctype(p, name, True) for p in params])
+    unread = set(re.findall(r'\b(tsamd_[a-z0-9_]+)\s*\(', text)) - set(table)
+    if unread:
+        raise TypeError('include/tsamd.h: prototype(s) not in the plain form the binding reads: %s' % sorted(unread))
+    return table
+
+
+def load_signatures():
+    """The signature table of the header at HEADER_PATH; a missing header is as fatal as a missing library."""
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(
+            'pytorch_sparse_amd: %s is missing. The ctypes binding takes every signature from this header '
+            '(TSAMD_HEADER names another place). There is no CPU fallback.' % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+SIGNATURES = load_signatures()
+SYMBOLS = sorted(SIGNATURES)  # every symbol include/tsamd.h declares (tests check that all of them resolve)
 
 DTYPES = {
     torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3,
@@ -77,8 +78,16 @@ class TsamdError(RuntimeError):
     pass
 
 
+def declare(L, names=SYMBOLS):
+    """Give these functions of a loaded library the restype and argtypes the header states."""
+    for name in names:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    return L
+
+
 def lib():
-    """Load libtsamd.so once; fail loudly when it has not been built."""
+    """Load libtsamd.so once, every function declared as in the header; fail loudly when it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -86,54 +95,7 @@ def lib():
                 'pytorch_sparse_amd: %s is missing. Build it with '
                 '`python pytorch_sparse_amd/build.py` (needs hipcc, targets gfx950). '
                 'There is no CPU fallback.' % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        L.tsamd_hip_version.restype = ctypes.c_int64
-        L.tsamd_status_string.restype = ctypes.c_char_p
-        L.tsamd_spmm_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spspmm_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spspmm_bw_plan_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spspmm_bw_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_exclusive_scan_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_partial_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_hints_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_minmax_bw_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_minmax_bw_csc_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_minmax_records_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_minmax_records_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_segment_softmax_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_sort_coo_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_sort_coalesce_workspace_bytes.restype = ctypes.c_size_t
-        i64, vp, i64p = ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)
-        L.tsamd_sddmm_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, i64p]
-        L.tsamd_sddmm_heads.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, i64, i64, i64, i64, i64, vp]
-        L.tsamd_spmm_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, i64p]
-        L.tsamd_spmm_heads_workspace_bytes.argtypes = [ctypes.c_int, i64, i64, i64, i64]
-        L.tsamd_spmm_heads_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_spmm_heads.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
-        L.tsamd_spmm_multi_route.argtypes = [ctypes.c_int, ctypes.c_int, i64, vp, vp, i64, i64, i64p]
-        L.tsamd_spmm_multi_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, i64, i64, i64]
-        L.tsamd_spmm_multi_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_attention_heads_route.argtypes = [ctypes.c_int, i64, i64, vp, vp, vp, vp, i64p]
-        L.tsamd_attention_heads_workspace_bytes.argtypes = [ctypes.c_int, i64, i64, i64]
-        L.tsamd_attention_heads_workspace_bytes.restype = ctypes.c_size_t
-        # the fused calls: dot-product and additive (GAT) scores share their signatures
-        fused_fw = [ctypes.c_int, vp, vp, vp, i64, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
-        fused_bw = [ctypes.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, i64, i64, i64, i64, i64, vp]
-        L.tsamd_attention_heads.argtypes = L.tsamd_gat_attention_heads.argtypes = fused_fw
-        L.tsamd_attention_heads_bw.argtypes = L.tsamd_gat_attention_heads_bw.argtypes = fused_bw
-        # with dropout on the probabilities: (double rate, uint64 seed) after the scalar
-        drop = [ctypes.c_double, ctypes.c_uint64]
-        L.tsamd_attention_heads_dropout.argtypes = L.tsamd_gat_attention_heads_dropout.argtypes = \
-            fused_fw[:9] + drop + fused_fw[9:]
-        L.tsamd_attention_heads_dropout_bw.argtypes = L.tsamd_gat_attention_heads_dropout_bw.argtypes = \
-            fused_bw[:13] + drop + fused_bw[13:]
-        L.tsamd_attention_dropout_mask.argtypes = [ctypes.c_uint64, ctypes.c_double, i64, i64, i64, vp]
-        L.tsamd_select_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_filter_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_filter_tiles_workspace_bytes.restype = ctypes.c_size_t
-        L.tsamd_num_diag.restype = ctypes.c_int64
-        _lib = L
+        _lib = declare(ctypes.CDLL(LIB_PATH))
     return _lib
 
 
@@ -150,7 +112,19 @@ def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _addr(p):
+    """A tensor or a plain address, as an address."""
+    return int(p.data_ptr() if hasattr(p, 'data_ptr') else p)
+
+
+def _dims(M, col, mat):
+    """(B, M, N, K, E) of a product with ``mat`` [..., N, K]; an empty matrix counts as one batch."""
+    N, K = mat.size(-2), mat.size(-1)
+    return (mat.numel() // (N * K) if N * K > 0 else 1), M, N, K, col.numel()
+
+
 def _i64(x):
+    """For raw calls in tests; the wrappers below pass plain ints (a c_int64 satisfies an int64_t parameter)."""
     return ctypes.c_int64(int(x))
 
 
@@ -188,9 +162,7 @@ def spmm(rowptr, col, value, mat, reduce, out=None, profile=None):
     if mat.dim() < 2:
         raise TsamdError('Input mismatch: mat.dim() >= 2 required')
     mat = mat.contiguous()
-    M, E = rowptr.numel() - 1, col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    B = mat.numel() // max(N * K, 1) if N * K > 0 else 1
+    B, M, N, K, E = _dims(rowptr.numel() - 1, col, mat)
     sizes = list(mat.shape)
     sizes[-2] = M
     if out is None:
@@ -199,12 +171,11 @@ def spmm(rowptr, col, value, mat, reduce, out=None, profile=None):
     if red >= 2:
         arg = torch.empty(sizes, dtype=torch.int64, device=mat.device)
     L = lib()
-    nb = L.tsamd_spmm_workspace_bytes(dt, red, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E))
+    nb = L.tsamd_spmm_workspace_bytes(dt, red, B, M, N, K, E)
     ws = workspace(nb, mat.device)
     with torch.cuda.device(mat.device):
         args = (dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(arg),
-                _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws), ctypes.c_size_t(ws.numel()),
-                stream_ptr(mat.device))
+                B, M, N, K, E, _ptr(ws), ws.numel(), stream_ptr(mat.device))
         if profile is None:
             st = L.tsamd_spmm(*args)
         else:
@@ -226,11 +197,9 @@ def spmm_route(dtype, reduce, B, M, N, K, E, mat=0, out=0, arg_out=0, arg32=Fals
     """C-ABI ``tsamd_spmm_route`` (host arithmetic, no device): what the forward decides for these operands, as a dict of
     SPMM_ROUTE_FIELDS (``family`` as one of SPMM_FAMILIES).  mat / out / arg_out / workspace: tensors or plain addresses
     (they count for their alignment and the offsets only; 0 = aligned / no workspace).  A refusal raises TsamdError."""
-    def addr(p):
-        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
     words = (ctypes.c_int64 * 24)()
-    st = lib().tsamd_spmm_route(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), addr(mat),
-                                addr(out), addr(arg_out), ctypes.c_int(1 if arg32 else 0), addr(workspace), words)
+    st = lib().tsamd_spmm_route(dtype_code(dtype), REDUCES[reduce], B, M, N, K, E, _addr(mat), _addr(out), _addr(arg_out),
+                                1 if arg32 else 0, _addr(workspace), words)
     check(st, 'tsamd_spmm_route')
     r = dict(zip(SPMM_ROUTE_FIELDS, (int(x) for x in words)))
     r['family'] = SPMM_FAMILIES[r['family']]
@@ -243,11 +212,9 @@ SPMM_ORDER_FIELDS = ('hdr_off', 'order_off', 'P', 'keys_off', 'shift', 'min_sing
 def spmm_order_layout(dtype, reduce, B, M, N, K, E, mat, out, workspace):
     """C-ABI ``tsamd_spmm_order_layout`` (host arithmetic): None when the call keeps slot = partition, else a dict of
     SPMM_ORDER_FIELDS plus ``mode`` (1 auto, 2 forced).  mat / out / workspace: tensors or plain addresses."""
-    def addr(p):
-        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
     words = (ctypes.c_int64 * 8)()
-    mode = lib().tsamd_spmm_order_layout(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E),
-                                         addr(mat), addr(out), addr(workspace), words)
+    mode = lib().tsamd_spmm_order_layout(dtype_code(dtype), REDUCES[reduce], B, M, N, K, E, _addr(mat), _addr(out),
+                                         _addr(workspace), words)
     if mode == 0:
         return None
     r = dict(zip(SPMM_ORDER_FIELDS, (int(x) for x in words)))
@@ -260,14 +227,14 @@ SPMM_HINTS_FIELDS = ('flags_off', 'hdr_off', 'totals_off', 'words_off', 'lists_o
 
 def spmm_hints_bytes(dtype, reduce, B, M, N, K, E):
     """C-ABI ``tsamd_spmm_hints_bytes``: the size of a pattern's hints buffer, 0 when the call is out of scope."""
-    return int(lib().tsamd_spmm_hints_bytes(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)))
+    return int(lib().tsamd_spmm_hints_bytes(dtype_code(dtype), REDUCES[reduce], B, M, N, K, E))
 
 
 def spmm_hints_layout(dtype, reduce, B, M, N, K, E):
     """C-ABI ``tsamd_spmm_hints_layout`` (host arithmetic): None when the call is out of scope, else a dict of
     SPMM_HINTS_FIELDS."""
     words = (ctypes.c_int64 * 8)()
-    if lib().tsamd_spmm_hints_layout(dtype_code(dtype), REDUCES[reduce], _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), words) == 0:
+    if lib().tsamd_spmm_hints_layout(dtype_code(dtype), REDUCES[reduce], B, M, N, K, E, words) == 0:
         return None
     return dict(zip(SPMM_HINTS_FIELDS, (int(x) for x in words)))
 
@@ -281,11 +248,10 @@ def spmm_hinted(rowptr, col, value, mat, reduce, hints, state, ws=None):
     out = torch.empty((M, K), dtype=mat.dtype, device=mat.device)
     L = lib()
     if ws is None:
-        ws = workspace(L.tsamd_spmm_workspace_bytes(dt, red, _i64(1), _i64(M), _i64(N), _i64(K), _i64(E)), mat.device)
+        ws = workspace(L.tsamd_spmm_workspace_bytes(dt, red, 1, M, N, K, E), mat.device)
     with torch.cuda.device(mat.device):
-        st = L.tsamd_spmm_hinted(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(None), _i64(1),
-                                 _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws), ctypes.c_size_t(ws.numel()), _ptr(hints),
-                                 ctypes.c_int(int(state)), stream_ptr(mat.device))
+        st = L.tsamd_spmm_hinted(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), None, 1, M, N, K, E,
+                                 _ptr(ws), ws.numel(), _ptr(hints), int(state), stream_ptr(mat.device))
     check(st, 'tsamd_spmm_hinted')
     return out
 
@@ -303,19 +269,16 @@ def spmm_partial(rowptr, col, value, mat, reduce, out, arg_out=None, arg_map=Non
         raise TsamdError('tsamd_spmm_partial works in place: mat / out / arg_out must be contiguous')
     if out.dtype != mat.dtype or (red >= 2 and (arg_out is None or arg_out.dtype != torch.int64)):
         raise TsamdError('Input mismatch: out / arg_out')
-    M, E = rowptr.numel() - 1, col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    B = mat.numel() // max(N * K, 1) if N * K > 0 else 1
+    B, M, N, K, E = _dims(rowptr.numel() - 1, col, mat)
     if out.numel() != B * M * K or (arg_out is not None and arg_out.numel() != out.numel()):
         raise TsamdError('Input mismatch: out must be [B, M, K]')
     L = lib()
-    nb = L.tsamd_spmm_partial_workspace_bytes(dt, red, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E))
+    nb = L.tsamd_spmm_partial_workspace_bytes(dt, red, B, M, N, K, E)
     ws = workspace(nb, mat.device)
     with torch.cuda.device(mat.device):
         st = L.tsamd_spmm_partial(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(arg_out),
-                                  _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(arg_map), _i64(arg_none),
-                                  ctypes.c_int(1 if accumulate else 0), _ptr(deg_rowptr), _ptr(ws),
-                                  ctypes.c_size_t(ws.numel()), stream_ptr(mat.device))
+                                  B, M, N, K, E, _ptr(arg_map), int(arg_none), 1 if accumulate else 0, _ptr(deg_rowptr),
+                                  _ptr(ws), ws.numel(), stream_ptr(mat.device))
     check(st, 'tsamd_spmm_partial')
     return out, arg_out
 
@@ -328,14 +291,11 @@ def spmm_value_bw(row, rowptr, col, mat, grad, reduce):
     mat, grad = mat.contiguous(), grad.contiguous()
     if grad.dtype != mat.dtype:
         raise TsamdError('expected scalar type %s but found %s' % (mat.dtype, grad.dtype))
-    M, E = rowptr.numel() - 1, col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(rowptr.numel() - 1, col, mat)
     out = torch.empty(E, dtype=mat.dtype, device=mat.device)
     with torch.cuda.device(mat.device):
-        st = lib().tsamd_spmm_value_bw(dt, red, _ptr(row), _ptr(rowptr), _ptr(col), _ptr(mat),
-                                       _ptr(grad), _ptr(out), _i64(B), _i64(M), _i64(N), _i64(K),
-                                       _i64(E), stream_ptr(mat.device))
+        st = lib().tsamd_spmm_value_bw(dt, red, _ptr(row), _ptr(rowptr), _ptr(col), _ptr(mat), _ptr(grad), _ptr(out),
+                                       B, M, N, K, E, stream_ptr(mat.device))
     check(st, 'tsamd_spmm_value_bw')
     return out
 
@@ -367,19 +327,17 @@ def spspmm_value_bw(side, segptr, segind, listptr, list_ind, list_val, rowptrC, 
         grad = torch.empty(nseg, dtype=gC.dtype, device=dev)
     elif grad.dtype != gC.dtype or grad.numel() != nseg or not grad.is_contiguous() or grad.device != dev:
         raise TsamdError('tsamd_spspmm_value_bw: grad must be a contiguous [nseg] tensor of the type of gC')
-    ws0 = workspace(L.tsamd_spspmm_bw_plan_workspace_bytes(_i64(nseg)), dev)
+    ws0 = workspace(L.tsamd_spspmm_bw_plan_workspace_bytes(nseg), dev)
     with torch.cuda.device(dev):
-        st = L.tsamd_spspmm_bw_plan(dt, ctypes.c_int(side), _ptr(segptr), _i64(nrows), _ptr(segind), _i64(nseg),
-                                    _ptr(listptr), _ptr(ptr), _ptr(stats), _ptr(ws0), ctypes.c_size_t(ws0.numel()),
-                                    stream_ptr(dev))
+        st = L.tsamd_spspmm_bw_plan(dt, side, _ptr(segptr), nrows, _ptr(segind), nseg, _ptr(listptr), _ptr(ptr),
+                                    _ptr(stats), _ptr(ws0), ws0.numel(), stream_ptr(dev))
         check(st, 'tsamd_spspmm_bw_plan')
         nbytes, P = (int(x) for x in stats.cpu())
-        assert nbytes == L.tsamd_spspmm_bw_workspace_bytes(dt, _i64(P))
+        assert nbytes == L.tsamd_spspmm_bw_workspace_bytes(dt, P)
         ws = workspace(nbytes, dev)
-        st = L.tsamd_spspmm_value_bw(dt, ctypes.c_int(side), _ptr(ptr), _i64(P), _ptr(segptr), _i64(nrows),
-                                     _ptr(segind), _i64(nseg), _ptr(listptr), _ptr(list_ind), _ptr(list_val),
-                                     _ptr(rowptrC), _ptr(colC), _ptr(gC), _ptr(grad), _ptr(ws),
-                                     ctypes.c_size_t(ws.numel()), stream_ptr(dev))
+        st = L.tsamd_spspmm_value_bw(dt, side, _ptr(ptr), P, _ptr(segptr), nrows, _ptr(segind), nseg, _ptr(listptr),
+                                     _ptr(list_ind), _ptr(list_val), _ptr(rowptrC), _ptr(colC), _ptr(gC), _ptr(grad),
+                                     _ptr(ws), ws.numel(), stream_ptr(dev))
     check(st, 'tsamd_spspmm_value_bw')
     return grad, P
 
@@ -415,13 +373,10 @@ def spmm_minmax_bw_route(winners, dtype, B, M, N, K, E, want_value=False, want_m
     mat / grad_out / grad_mat: tensors or plain addresses (their alignment counts; 0 = aligned).  ``status`` is the
     entry's answer as an int (0 = OK; the other fields are then filled), ``value`` / ``sddmm`` / ``mat`` / ``packed`` are
     names, ``family`` one of SPMM_FAMILIES."""
-    def addr(p):
-        return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, 'data_ptr') else p))
     words = (ctypes.c_int64 * 32)()
     dt = dtype if isinstance(dtype, int) else dtype_code(dtype)
-    st = lib().tsamd_spmm_minmax_bw_route(MINMAX_BW_WINNERS.index(winners), dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E),
-                                          ctypes.c_int(1 if want_value else 0), ctypes.c_int(1 if want_mat else 0),
-                                          addr(mat), addr(grad_out), addr(grad_mat), words)
+    st = lib().tsamd_spmm_minmax_bw_route(MINMAX_BW_WINNERS.index(winners), dt, B, M, N, K, E, 1 if want_value else 0,
+                                          1 if want_mat else 0, _addr(mat), _addr(grad_out), _addr(grad_mat), words)
     check(st, 'tsamd_spmm_minmax_bw_route')
     r = dict(zip(MINMAX_BW_ROUTE_FIELDS, (int(x) for x in words)))
     r['value'] = MINMAX_BW_VALUE[r['value']]
@@ -438,21 +393,17 @@ def spmm_minmax_bw(rowptr, col, value, mat, grad_out, arg_out, want_value=True, 
     require_gpu(rowptr, col, value, mat, grad_out, arg_out)
     dt = dtype_code(mat.dtype)
     mat, grad_out, arg_out = mat.contiguous(), grad_out.contiguous(), arg_out.contiguous()
-    E = col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    M = grad_out.size(-2)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(grad_out.size(-2), col, mat)
     gv = _out_buffer(gv, want_value, E, mat)
     gm = _out_buffer(gm, want_mat, mat.numel(), mat, like=True)
     L = lib()
-    nb = L.tsamd_spmm_minmax_bw_workspace_bytes(dt, _i64(B), _i64(N), _i64(K), _i64(E))
+    nb = L.tsamd_spmm_minmax_bw_workspace_bytes(dt, B, N, K, E)
     if gm is not None and gm.data_ptr() % 4 != 0:  # a misaligned f16 / bf16 grad_mat takes the fp32 shadow at any count
         nb = max(nb, 4 * B * N * K + 256)
     ws = workspace(nb, mat.device)
     with torch.cuda.device(mat.device):
         st = L.tsamd_spmm_minmax_bw(dt, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(grad_out),
-                                    _ptr(arg_out), _ptr(gv), _ptr(gm), _i64(B), _i64(M), _i64(N),
-                                    _i64(K), _i64(E), _ptr(ws), ctypes.c_size_t(ws.numel()),
+                                    _ptr(arg_out), _ptr(gv), _ptr(gm), B, M, N, K, E, _ptr(ws), ws.numel(),
                                     stream_ptr(mat.device))
     check(st, 'tsamd_spmm_minmax_bw')
     return gv, gm
@@ -462,21 +413,17 @@ def spmm_minmax_arg32(rowptr, col, value, mat, reduce):
     """C-ABI ``tsamd_spmm_minmax_arg32`` (stateless): min / max with the winners as int32 ids -> (out, arg32)."""
     require_gpu(rowptr, col, value, mat)
     mat = mat.contiguous()
-    M, E = rowptr.numel() - 1, col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(rowptr.numel() - 1, col, mat)
     red = REDUCES[reduce]
     dt = dtype_code(mat.dtype)
     out = torch.empty(list(mat.shape[:-2]) + [M, K], dtype=mat.dtype, device=mat.device)
     arg = torch.empty(out.shape, dtype=torch.int32, device=mat.device)
     L = lib()
-    nbytes = L.tsamd_spmm_workspace_bytes(dt, red, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E))
+    nbytes = L.tsamd_spmm_workspace_bytes(dt, red, B, M, N, K, E)
     ws = workspace(nbytes, mat.device)
     with torch.cuda.device(mat.device):
         st = L.tsamd_spmm_minmax_arg32(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(arg),
-                                       _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws),
-                                       ctypes.c_size_t(ws.numel()), None, ctypes.c_size_t(0), 0,
-                                       stream_ptr(mat.device))
+                                       B, M, N, K, E, _ptr(ws), ws.numel(), None, 0, 0, stream_ptr(mat.device))
     check(st, 'tsamd_spmm_minmax_arg32')
     return out, arg
 
@@ -488,21 +435,16 @@ def spmm_minmax_bw_csc(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2c
     require_gpu(rowptr, col, value, mat, grad_out, arg_out, colptr, csr2csc, row)
     dt = dtype_code(mat.dtype)
     mat, grad_out, arg_out = mat.contiguous(), grad_out.contiguous(), arg_out.contiguous()
-    E = col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    M = grad_out.size(-2)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(grad_out.size(-2), col, mat)
     gv = _out_buffer(gv, want_value, E, mat)
     gm = _out_buffer(gm, want_mat, mat.numel(), mat, like=True)
     L = lib()
-    nb = L.tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E))
+    nb = L.tsamd_spmm_minmax_bw_csc_workspace_bytes(dt, B, M, N, K, E)
     ws = workspace(nb, mat.device)
     fn = L.tsamd_spmm_minmax_bw_csc_arg32 if arg_out.dtype == torch.int32 else L.tsamd_spmm_minmax_bw_csc
     with torch.cuda.device(mat.device):
-        st = fn(dt, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(grad_out),
-                _ptr(arg_out), _ptr(colptr), _ptr(csr2csc), _ptr(row), _ptr(gv), _ptr(gm),
-                _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws),
-                ctypes.c_size_t(ws.numel()), stream_ptr(mat.device))
+        st = fn(dt, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(grad_out), _ptr(arg_out), _ptr(colptr),
+                _ptr(csr2csc), _ptr(row), _ptr(gv), _ptr(gm), B, M, N, K, E, _ptr(ws), ws.numel(), stream_ptr(mat.device))
     check(st, 'tsamd_spmm_minmax_bw_csc')
     return gv, gm
 
@@ -512,9 +454,7 @@ def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False, out=No
     -> (out, records as int32 words).  zero: the buffer starts as zeros (padding words of a record are never written)."""
     require_gpu(rowptr, col, value, mat, row)
     mat = mat.contiguous()
-    M, E = rowptr.numel() - 1, col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(rowptr.numel() - 1, col, mat)
     red = REDUCES[reduce]
     dt = dtype_code(mat.dtype)
     if out is None:
@@ -522,17 +462,15 @@ def spmm_minmax_records(rowptr, col, value, mat, reduce, row, zero=False, out=No
     else:
         _given(out, B * M * K, mat.dtype, 'out')
     L = lib()
-    nrec = L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4
+    nrec = L.tsamd_spmm_minmax_records_bytes(B, K, E) // 4
     if rec is None:
         rec = (torch.zeros if zero else torch.empty)(nrec, dtype=torch.int32, device=mat.device)
     else:
         _given(rec, nrec, torch.int32, 'records')
-    ws = workspace(L.tsamd_spmm_minmax_records_workspace_bytes(dt, red, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)),
-                   mat.device)
+    ws = workspace(L.tsamd_spmm_minmax_records_workspace_bytes(dt, red, B, M, N, K, E), mat.device)
     with torch.cuda.device(mat.device):
         st = L.tsamd_spmm_minmax_records(dt, red, _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), _ptr(out), _ptr(row),
-                                         _ptr(rec), _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws),
-                                         ctypes.c_size_t(ws.numel()), stream_ptr(mat.device))
+                                         _ptr(rec), B, M, N, K, E, _ptr(ws), ws.numel(), stream_ptr(mat.device))
     check(st, 'tsamd_spmm_minmax_records')
     return out, rec
 
@@ -544,15 +482,15 @@ def spmm_minmax_winrec(row, value, arg32, K, rec=None, dtype=None):
     E, M = row.numel(), arg32.size(-2)
     B = arg32.numel() // (M * K) if M * K > 0 else 1
     L = lib()
-    nrec = L.tsamd_spmm_minmax_records_bytes(_i64(B), _i64(K), _i64(E)) // 4
+    nrec = L.tsamd_spmm_minmax_records_bytes(B, K, E) // 4
     if rec is None:
         rec = torch.zeros(nrec, dtype=torch.int32, device=row.device)
     else:
         _given(rec, nrec, torch.int32, 'records')
     dt = dtype_code(value.dtype) if value is not None else (dtype_code(dtype) if dtype is not None else 0)
     with torch.cuda.device(row.device):
-        st = L.tsamd_spmm_minmax_winrec(dt, _ptr(row), _ptr(value), _ptr(arg32), _ptr(rec), _i64(B), _i64(M), _i64(K),
-                                        _i64(E), stream_ptr(row.device))
+        st = L.tsamd_spmm_minmax_winrec(dt, _ptr(row), _ptr(value), _ptr(arg32), _ptr(rec), B, M, K, E,
+                                        stream_ptr(row.device))
     check(st, 'tsamd_spmm_minmax_winrec')
     return rec
 
@@ -563,20 +501,16 @@ def spmm_minmax_bw_csc_records(rowptr, col, has_value, mat, grad_out, records, c
     require_gpu(rowptr, col, mat, grad_out, records, colptr, csr2csc, row)
     dt = dtype_code(mat.dtype)
     mat, grad_out = mat.contiguous(), grad_out.contiguous()
-    E = col.numel()
-    N, K = mat.size(-2), mat.size(-1)
-    M = grad_out.size(-2)
-    B = mat.numel() // (N * K) if N * K > 0 else 1
+    B, M, N, K, E = _dims(grad_out.size(-2), col, mat)
     gv = _out_buffer(gv, want_value, E, mat)
     gm = _out_buffer(gm, True, mat.numel(), mat, like=True)
     L = lib()
-    ws = workspace(L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes(dt, _i64(B), _i64(M), _i64(N), _i64(K), _i64(E)),
-                   mat.device)
+    ws = workspace(L.tsamd_spmm_minmax_bw_csc_records_workspace_bytes(dt, B, M, N, K, E), mat.device)
     with torch.cuda.device(mat.device):
-        st = L.tsamd_spmm_minmax_bw_csc_records(dt, _ptr(rowptr), _ptr(col), ctypes.c_int(1 if has_value else 0), _ptr(mat),
+        st = L.tsamd_spmm_minmax_bw_csc_records(dt, _ptr(rowptr), _ptr(col), 1 if has_value else 0, _ptr(mat),
                                                 _ptr(grad_out), _ptr(records), _ptr(colptr), _ptr(csr2csc), _ptr(row),
-                                                _ptr(gv), _ptr(gm), _i64(B), _i64(M), _i64(N), _i64(K), _i64(E), _ptr(ws),
-                                                ctypes.c_size_t(ws.numel()), stream_ptr(mat.device))
+                                                _ptr(gv), _ptr(gm), B, M, N, K, E, _ptr(ws), ws.numel(),
+                                                stream_ptr(mat.device))
     check(st, 'tsamd_spmm_minmax_bw_csc_records')
     return gv, gm
 
@@ -585,8 +519,7 @@ def ind2ptr(ind, M):
     require_gpu(ind)
     out = torch.empty(M + 1, dtype=torch.int64, device=ind.device)
     with torch.cuda.device(ind.device):
-        st = lib().tsamd_ind2ptr(_ptr(ind), _i64(M), _i64(ind.numel()), _ptr(out),
-                                 stream_ptr(ind.device))
+        st = lib().tsamd_ind2ptr(_ptr(ind), M, ind.numel(), _ptr(out), stream_ptr(ind.device))
     check(st, 'tsamd_ind2ptr')
     return out
 
@@ -595,7 +528,6 @@ def ptr2ind(ptr, E):
     require_gpu(ptr)
     out = torch.empty(E, dtype=torch.int64, device=ptr.device)
     with torch.cuda.device(ptr.device):
-        st = lib().tsamd_ptr2ind(_ptr(ptr), _i64(ptr.numel() - 1), _i64(E), _ptr(out),
-                                 stream_ptr(ptr.device))
+        st = lib().tsamd_ptr2ind(_ptr(ptr), ptr.numel() - 1, E, _ptr(out), stream_ptr(ptr.device))
     check(st, 'tsamd_ptr2ind')
     return out

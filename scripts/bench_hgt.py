@@ -105,7 +105,6 @@ def hgt_row(inputs, k, hops):
 
 def select_row(C, k, M=1 << 20):
     L = nat.lib()
-    L.tsamd_hgt_select_workspace_bytes.restype = ctypes.c_size_t
     g = torch.Generator(device=dev).manual_seed(C)
     cand = torch.randperm(M, generator=g, device=dev)[:C].contiguous()
     budget = torch.randint(1, 1 << 34, (C, ), generator=g, device=dev)

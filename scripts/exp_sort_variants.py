@@ -25,6 +25,7 @@ if '--build' in sys.argv:
     sys.exit(max(p.wait() for p in procs))
 
 import torch  # noqa: E402
+from pytorch_sparse_amd import _native as nat  # noqa: E402
 from pytorch_sparse_amd import synth  # noqa: E402
 dev = torch.device('cuda:0')
 m = n = int(os.environ.get('MN', 500000))
@@ -32,8 +33,8 @@ E = int(os.environ.get('E', 7500000))
 row, col = synth.uniform_edges(m, n, E, seed=0, device=dev)
 i64 = ctypes.c_int64
 for so in sorted(glob.glob(os.path.join(AB, 'sort_*.so'))):
-    L = ctypes.CDLL(so, mode=os.RTLD_LAZY)  # (tsamd_gather_rows of the one-launch path lives in another TU)
-    L.tsamd_sort_coo_workspace_bytes.restype = ctypes.c_size_t
+    # (RTLD_LAZY: tsamd_gather_rows of the one-launch path lives in another TU)
+    L = nat.declare(ctypes.CDLL(so, mode=os.RTLD_LAZY), ['tsamd_sort_coo_workspace_bytes', 'tsamd_sort_coo'])
     ws = torch.empty(L.tsamd_sort_coo_workspace_bytes(i64(E)), dtype=torch.uint8, device=dev)
     ro, co, po = torch.empty_like(row), torch.empty_like(col), torch.empty_like(row)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

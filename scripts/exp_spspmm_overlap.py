@@ -12,8 +12,6 @@ from pytorch_sparse_amd import _native as nat
 
 dev = torch.device('cuda:0')
 L = nat.lib()
-L.tsamd_spspmm_workspace_bytes.restype = ctypes.c_size_t
-L.tsamd_exclusive_scan_workspace_bytes.restype = ctypes.c_size_t
 A, At = bc.spspmm_inputs(dev, sys.argv[1] if len(sys.argv) > 1 else 'c4')
 rpA, cA, vA = A.storage.rowptr(), A.storage.col(), A.storage.value()
 rpB, cB, vB = At.storage.rowptr(), At.storage.col(), At.storage.value()

@@ -1,5 +1,6 @@
 """pip / setuptools entry: builds the two native libraries in-tree (hipcc for gfx950, g++ for the torch
-operator glue -- pytorch_sparse_amd/build.py) and installs the package with them as package data.
+operator glue -- pytorch_sparse_amd/build.py) and installs the package with them as package data, and with a copy of
+include/tsamd.h (pytorch_sparse_amd/include/), which the ctypes binding reads its signatures from.
 
     pip install --no-build-isolation -e .        # or: python setup.py build_ext --inplace
 
@@ -38,6 +39,10 @@ class BuildPy(build_py):
     def run(self):
         _build_native()
         super().run()
+        # the ctypes binding reads its signatures from the header: an installed package carries a copy
+        dest = os.path.join(self.build_lib, 'pytorch_sparse_amd', 'include')
+        self.mkpath(dest)
+        self.copy_file(os.path.join(ROOT, 'include', 'tsamd.h'), os.path.join(dest, 'tsamd.h'))
 
 
 setup(

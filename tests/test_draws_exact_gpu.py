@@ -37,9 +37,6 @@ I = lambda x: ctypes.c_int64(int(x))  # noqa: E731
 @pytest.fixture(scope='module')
 def nat():
     from pytorch_sparse_amd import _native
-    L = _native.lib()
-    for name in ('tsamd_sample_workspace_bytes', 'tsamd_ego_plan_workspace_bytes', 'tsamd_temporal_redraw_workspace_bytes'):
-        getattr(L, name).restype = ctypes.c_size_t
     return _native
 
 

@@ -117,7 +117,6 @@ def test_whole_budget_hops_against_the_restatement(seed):
 def test_budget_words_through_the_cabi():
     from pytorch_sparse_amd import _native as nat
     L = nat.lib()
-    L.tsamd_sample_workspace_bytes.restype = ctypes.c_size_t
     rng = np.random.default_rng(5)
     Ms, Md = 700, 400
     deg = rng.integers(0, MAX_NEIGHBORS + 1, Md)
@@ -163,7 +162,6 @@ def test_select_does_not_depend_on_the_order_of_the_candidate_list():
     order must be a function of (seed, hop, type tag) and the words alone; dead entries (seen) never win."""
     from pytorch_sparse_amd import _native as nat
     L = nat.lib()
-    L.tsamd_hgt_select_workspace_bytes.restype = ctypes.c_size_t
     g = torch.Generator().manual_seed(3)
     M, C, k = 5000, 1200, 100
     cand = torch.randperm(M, generator=g)[:C]

@@ -45,8 +45,6 @@ class Stages:
 
     def __init__(self, dev):
         self.dev, self.L = dev, nat.lib()
-        for name in ('conn', 'commit'):
-            getattr(self.L, 'tsamd_partition_%s_workspace_bytes' % name).restype = ctypes.c_size_t
 
     def empty(self, n):
         return torch.empty(n, dtype=torch.long, device=self.dev)

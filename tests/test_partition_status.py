@@ -13,11 +13,7 @@ OK, INVALID, UNSUPPORTED, WORKSPACE = 0, 1, 2, 4
 TWO31 = 1 << 31
 
 
-def L():
-    lib = nat.lib()
-    for name in ('match', 'assign', 'conn', 'commit'):
-        getattr(lib, 'tsamd_partition_%s_workspace_bytes' % name).restype = sz
-    return lib
+L = nat.lib
 
 
 def edges(row=fake, col=fake, E=5, n=4, n_key=4, row_out=fake, col_out=fake, w_out=fake, info=fake):

@@ -397,7 +397,6 @@ def test_relabel_seed_extend_cabi_matches_a_sequential_map():
     import ctypes
     from pytorch_sparse_amd import _native as nat
     L = nat.lib()
-    L.tsamd_relabel_workspace_bytes.restype = ctypes.c_size_t
     g = torch.Generator().manual_seed(7)
     M = 5000
     seeds = torch.randperm(M, generator=g)[:300]

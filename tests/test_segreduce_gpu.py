@@ -41,7 +41,6 @@ def _expect(case, kind, dtype, reduce, value):
 def _balanced(value, perm, ptr, nseg, E, reduce, dtype_code=None):
     """tsamd_segment_reduce_balanced through ctypes: no size gate in front of it."""
     L = nat.lib()
-    L.tsamd_segment_reduce_balanced_workspace_bytes.restype = ctypes.c_size_t
     D = value.numel() // value.size(0)
     dt = nat.DTYPES[value.dtype] if dtype_code is None else dtype_code
     nb = L.tsamd_segment_reduce_balanced_workspace_bytes(dt, nat._i64(E), nat._i64(D))

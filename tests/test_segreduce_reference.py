@@ -266,7 +266,6 @@ def test_balanced_entry_status_codes_before_any_device_call():
     i64, vp, sz = ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
     fake = vp(0x1000)  # never dereferenced
     fn = L.tsamd_segment_reduce_balanced
-    fn.restype = ctypes.c_int
 
     def call(dtype=0, reduce=0, nseg=3, E=4, D=1, out=fake, ptr=fake):
         return fn(dtype, reduce, fake, None, ptr, i64(nseg), i64(E), i64(D), out, fake, sz(1 << 20), None)
@@ -281,7 +280,6 @@ def test_balanced_entry_status_codes_before_any_device_call():
     # a negative size wins over everything after it, an unknown reduce over an unknown dtype
     assert call(nseg=-1, reduce=9, dtype=42) == INVALID and call(reduce=9, dtype=42, D=70000) == UNSUPPORTED
     ws = L.tsamd_segment_reduce_balanced_workspace_bytes
-    ws.restype = ctypes.c_size_t
     assert ws(0, i64(513), i64(1)) == 2 * 256 + 2 * 256  # two chunks: 8 B of fp32 and 16 B of ids, each padded to 256
     assert ws(1, i64(200_000), i64(3)) >= 2 * 8 * 3 * 391 + 2 * 8 * 391
     assert ws(0, i64(0), i64(0)) == ws(0, i64(1), i64(1))
