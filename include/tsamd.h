@@ -647,6 +647,45 @@ int tsamd_spmm_multi(int dtype, int mask, const int64_t *rowptr, const int64_t *
                      int64_t N, int64_t F, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Relational SpMM, the dense half (csrc/rel_gemm.hip): grouped products on the matrix instructions of gfx950.  The P
+ * items t = 0 .. P - 1 are ordered by group; group g (a relation) is the items [relptr[g], relptr[g + 1]), relptr
+ * [R + 1] int64 ascending from 0 to P.  float32 (v_mfma_f32_32x32x2_f32) and bfloat16 (v_mfma_f32_32x32x16_bf16), fp32
+ * accumulation; every width K, N, F, Fo in 1 .. 512 (narrow and odd widths are zero-padded in LDS).  Deterministic, no
+ * atomics, no host sync.
+ *
+ *   tsamd_rel_gemm   out[dst_idx[t], :] = dst_scale[dst_idx[t]] * (src[src_idx[t], :] @ W[g])        t in group g
+ *     src [n_src, K] dtype, out [n_dst, N] float, src_idx / dst_idx [P] int64 (src_idx may repeat rows; the dst_idx
+ *     of the call must be distinct, every row is written once, rows no item names are left alone; an id outside
+ *     [0, n_src) reads zeros, one outside [0, n_dst) stores nothing), dst_scale [n_dst] float or NULL (ones).
+ *     transposed = 0: weight is [R, K, N]; transposed = 1: weight is [R, N, K] and the product is with W[g]^T.
+ *   tsamd_rel_wgrad  grad_weight[g, :, :] = sum over t in group g of  h[h_idx[t], :]^T (outer) go[go_idx[t], :]
+ *     h [n_h, F], go [n_go, Fo] and grad_weight [R, F, Fo] in dtype; a group's items are cut into chunks of CK items,
+ *     CK a function of P alone, and the fp32 blocks of the chunks are added in ascending order, so the result does not
+ *     depend on the launch; a group without items gives zeros.
+ *   tsamd_rel_gemm_route (host arithmetic only) for the relational product of P pairs, R relations, x [*, F] and
+ *     weight [R, F, Fo]: out[0] TM items per tile, out[1] TN output columns per tile (64 up to Fo = 64, else 128),
+ *     out[2] elements of K per LDS slice, out[3] the tile bound ceil(P / TM) + R (gridDim.x), out[4..6] the matrix
+ *     instruction's M, N and K step, out[7] CK, out[8] the chunk bound ceil(P / CK) + R, out[9] items per LDS slice
+ *     of rel_wgrad, out[10] / out[11] rows and columns of its [F, Fo] block, out[12] / out[13] the two workspace
+ *     sizes of this shape (K = F, N = Fo); out[14..15] are 0.
+ * Status, in this order: a negative size (or out == NULL in the route) TSAMD_ERR_INVALID; a dtype other than float32
+ * / bfloat16, a width of 0 or above 512, or P, R >= 2^31 TSAMD_ERR_UNSUPPORTED; nothing to do (tsamd_rel_gemm: P == 0
+ * or R == 0; tsamd_rel_wgrad: R == 0) TSAMD_OK; a null array TSAMD_ERR_INVALID; a workspace that is missing, smaller
+ * than the matching *_workspace_bytes() or off a 256-byte boundary TSAMD_ERR_WORKSPACE.  The two *_workspace_bytes
+ * return 0 for shapes the calls refuse.
+ * ------------------------------------------------------------------------ */
+int tsamd_rel_gemm_route(int dtype, int64_t P, int64_t R, int64_t F, int64_t Fo, int64_t out[16]);
+size_t tsamd_rel_gemm_workspace_bytes(int dtype, int64_t P, int64_t R, int64_t K, int64_t N);
+int tsamd_rel_gemm(int dtype, int transposed, const void *src, int64_t n_src, const int64_t *src_idx,
+                   const int64_t *dst_idx, const int64_t *relptr, const void *weight, const float *dst_scale,
+                   float *out, int64_t n_dst, int64_t P, int64_t R, int64_t K, int64_t N, void *workspace,
+                   size_t workspace_bytes, void *stream);
+size_t tsamd_rel_wgrad_workspace_bytes(int dtype, int64_t P, int64_t R, int64_t F, int64_t Fo);
+int tsamd_rel_wgrad(int dtype, const void *h, int64_t n_h, const int64_t *h_idx, const void *go, int64_t n_go,
+                    const int64_t *go_idx, const int64_t *relptr, void *grad_weight, int64_t P, int64_t R, int64_t F,
+                    int64_t Fo, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Fused attention over a pattern (csrc/attention.hip): scores, softmax over the row and aggregation in one pass.
  * (rowptr, col) is the CSR order of the E entries; q [nseg, H, D], k and v [nsrc, H, D], out [nseg, H, D],
  * lse [nseg, H] in the accumulator type (float, double for float64).  bias is NULL or holds one element of the
