@@ -686,6 +686,37 @@ int tsamd_rel_wgrad(int dtype, const void *h, int64_t n_h, const int64_t *h_idx,
                     int64_t Fo, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The same two products for block-diagonal weights (csrc/rel_blocks.hip): W[g] = diag(Q[g, 0] .. Q[g, B - 1]) with
+ * Q[g, b] of [ci, co], stored compact as [R, B, ci, co]; F = B ci and Fo = B co in 1 .. 512.  Items, groups, indices,
+ * dtypes, accumulation and determinism are those of tsamd_rel_gemm / tsamd_rel_wgrad above.
+ *
+ *   tsamd_rel_gemm_blocks   out[dst_idx[t], b co + n] = dst_scale[.] * sum_k src[src_idx[t], b ci + k] Q[g, b][k, n]
+ *     src [n_src, B ci], out [n_dst, B co] float.  transposed = 1: weight is [R, B, co, ci] and every block is read
+ *     as its transpose, Q[g, b][k, n] = weight[g, b, n, k] (what the gradient of the source needs, ci and co
+ *     exchanged by the caller).  A tile of output columns contracts only the range of K its diagonal blocks cover.
+ *   tsamd_rel_wgrad_blocks  grad_weight[g, b] = sum over t in group g of  h[h_idx[t], b ci ..]^T (outer) go[go_idx[t],
+ *     b co ..]:  h [n_h, B ci], go [n_go, B co], grad_weight [R, B, ci, co] in dtype; only the tiles of [F, Fo] on the
+ *     diagonal are computed and the fp32 chunk blocks are compact ([chunk, B, ci, co]).
+ *   tsamd_rel_blocks_route (host arithmetic only): out[0] TM, out[1] TN, out[2] elements of K per LDS slice, out[3]
+ *     the tile bound, out[4..6] the matrix instruction's M, N and K step, out[7] CK, out[8] the chunk bound, out[9]
+ *     the longest K window of a column tile padded to the packet, out[10] gridDim.y of the weight gradient (column
+ *     tiles x the longest range of row tiles on the diagonal), out[11] its columns per tile, out[12] / out[13] the
+ *     workspace sizes of tsamd_rel_gemm_blocks and tsamd_rel_wgrad_blocks; out[14..15] are 0.
+ * Status as above, B, ci and co in the place of the widths: negative TSAMD_ERR_INVALID; 0, or B ci or B co above 512,
+ * TSAMD_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------ */
+int tsamd_rel_blocks_route(int dtype, int64_t P, int64_t R, int64_t B, int64_t ci, int64_t co, int64_t out[16]);
+size_t tsamd_rel_gemm_blocks_workspace_bytes(int dtype, int64_t P, int64_t R, int64_t B, int64_t ci, int64_t co);
+int tsamd_rel_gemm_blocks(int dtype, int transposed, const void *src, int64_t n_src, const int64_t *src_idx,
+                          const int64_t *dst_idx, const int64_t *relptr, const void *weight, const float *dst_scale,
+                          float *out, int64_t n_dst, int64_t P, int64_t R, int64_t B, int64_t ci, int64_t co,
+                          void *workspace, size_t workspace_bytes, void *stream);
+size_t tsamd_rel_wgrad_blocks_workspace_bytes(int dtype, int64_t P, int64_t R, int64_t B, int64_t ci, int64_t co);
+int tsamd_rel_wgrad_blocks(int dtype, const void *h, int64_t n_h, const int64_t *h_idx, const void *go, int64_t n_go,
+                           const int64_t *go_idx, const int64_t *relptr, void *grad_weight, int64_t P, int64_t R,
+                           int64_t B, int64_t ci, int64_t co, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Fused attention over a pattern (csrc/attention.hip): scores, softmax over the row and aggregation in one pass.
  * (rowptr, col) is the CSR order of the E entries; q [nseg, H, D], k and v [nsrc, H, D], out [nseg, H, D],
  * lse [nseg, H] in the accumulator type (float, double for float64).  bias is NULL or holds one element of the

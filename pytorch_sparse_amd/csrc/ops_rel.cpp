@@ -19,6 +19,9 @@
 //   gH[q[t], :] = grad[prow[q[t]], :] @ weight[g]^T  (tsamd_rel_gemm, transposed; scaled by 1 / count for 'mean')
 //   grad_x = the transposed sum-SpMM of gH: tsamd_spmm_permuted over (colptr, pair id of the entry, value, csr2csc)
 //   grad_weight[g] = sum_t H[q[t], :]^T (outer) grad[prow[q[t]], :]   (tsamd_rel_wgrad)
+// A 4-D weight [R, B, ci, co] is block-diagonal, weight[g] = diag of its B blocks (csrc/rel_blocks.hip): plan, A and C
+// are shared, step B and the two backward products go to tsamd_rel_gemm_blocks / tsamd_rel_wgrad_blocks; B = 1 is the
+// dense call on the squeezed weight.
 #include "ops_common.h"
 
 namespace tsamd_ops {
@@ -40,12 +43,20 @@ void check_rel_args(const Tensor &rowptr, const Tensor &col, const OptTensor &va
   TORCH_CHECK_VALUE(x.dim() == 2, "spmm_rel: x must be [N, F], got ", x.dim(), " dimension(s); a batched x is not supported");
   TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
                     "spmm_rel: float32 or bfloat16 expected, got ", x.scalar_type());
-  TORCH_CHECK_VALUE(weight.dim() == 3 && weight.size(1) == x.size(1), "spmm_rel: weight must be [R, F, Fo] with F = ",
-                    x.size(1), ", got ", weight.sizes());
+  if (weight.dim() == 4) {  // block-diagonal: [R, B, ci, co]
+    TORCH_CHECK_VALUE(weight.size(1) >= 1 && weight.size(2) >= 1 && weight.size(3) >= 1 &&
+                          weight.size(1) * weight.size(2) == x.size(1),
+                      "spmm_rel: a block-diagonal weight must be [R, B, ci, co] with B ci = ", x.size(1), ", got ",
+                      weight.sizes());
+  } else {
+    TORCH_CHECK_VALUE(weight.dim() == 3 && weight.size(1) == x.size(1), "spmm_rel: weight must be [R, F, Fo] with F = ",
+                      x.size(1), ", got ", weight.sizes());
+  }
   TORCH_CHECK_VALUE(weight.scalar_type() == x.scalar_type(), "spmm_rel: weight and x differ in dtype: ",
                     weight.scalar_type(), " and ", x.scalar_type());
-  TORCH_CHECK_VALUE(x.size(1) >= 1 && x.size(1) <= 512 && weight.size(2) >= 1 && weight.size(2) <= 512,
-                    "spmm_rel: F and Fo must lie in 1 .. 512, got ", x.size(1), " and ", weight.size(2));
+  const int64_t Fo = weight.dim() == 4 ? weight.size(1) * weight.size(3) : weight.size(2);
+  TORCH_CHECK_VALUE(x.size(1) >= 1 && x.size(1) <= 512 && Fo >= 1 && Fo <= 512,
+                    "spmm_rel: F and Fo must lie in 1 .. 512, got ", x.size(1), " and ", Fo);
   TORCH_CHECK_VALUE(weight.size(0) >= 1, "spmm_rel: weight holds no relation");
   TORCH_CHECK_VALUE(rel.scalar_type() == at::kLong && rel.dim() == 1 && rel.numel() == col.numel(),
                     "spmm_rel: rel must be an int64 tensor with one relation per entry ([", col.numel(), "]), got ",
@@ -70,12 +81,23 @@ Tensor ind2ptr(const Tensor &ind, int64_t n) {
   return ptr;
 }
 
-// one tsamd_rel_gemm: out [n_dst, N] fp32, rows no item names are not written
+// one tsamd_rel_gemm (weight [R, *, *]) or tsamd_rel_gemm_blocks (weight [R, B, *, *]; K and N are B times its
+// block sizes): out [n_dst, N] fp32, rows no item names are not written
 Tensor rel_gemm(bool transposed, const Tensor &src, const Tensor &src_idx, const Tensor &dst_idx, const Tensor &relptr,
                 const Tensor &weight, const Tensor &scale, int64_t n_dst, int64_t K, int64_t N) {
   const int64_t P = dst_idx.numel(), R = relptr.numel() - 1;
   const int dt = dtype_code(src);
   Tensor out = torch::empty({n_dst, N}, src.options().dtype(at::kFloat).requires_grad(false));
+  if (weight.dim() == 4) {
+    const int64_t B = weight.size(1);
+    Tensor ws = workspace(tsamd_rel_gemm_blocks_workspace_bytes(dt, P, R, B, K / B, N / B), src);
+    check_status(tsamd_rel_gemm_blocks(dt, transposed ? 1 : 0, src.data_ptr(), src.size(0), lp(src_idx), lp(dst_idx),
+                                       lp(relptr), weight.data_ptr(), scale.defined() ? scale.data_ptr<float>() : nullptr,
+                                       out.data_ptr<float>(), n_dst, P, R, B, K / B, N / B, ws.data_ptr(),
+                                       (size_t)ws.numel(), current_stream(src)),
+                 "tsamd_rel_gemm_blocks");
+    return out;
+  }
   Tensor ws = workspace(tsamd_rel_gemm_workspace_bytes(dt, P, R, K, N), src);
   check_status(tsamd_rel_gemm(dt, transposed ? 1 : 0, src.data_ptr(), src.size(0), lp(src_idx), lp(dst_idx), lp(relptr),
                               weight.data_ptr(), scale.defined() ? scale.data_ptr<float>() : nullptr,
@@ -98,10 +120,12 @@ class SpmmRelFunction : public torch::autograd::Function<SpmmRelFunction> {
     Tensor x = x_.detach().contiguous(), weight = weight_.detach().contiguous();
     Tensor value = has_value ? value_.detach().contiguous() : Tensor();
     const int64_t M = rowptr.numel() - 1, N = x.size(0), F = x.size(1), E = col.numel();
-    const int64_t R = weight.size(0), Fo = weight.size(2);
+    const int64_t B = weight.dim() == 4 ? weight.size(1) : 0;  // 0: a dense [R, F, Fo] weight
+    const int64_t R = weight.size(0), Fo = B ? B * weight.size(3) : weight.size(2);
     const int dt = dtype_code(x);
     void *stream = current_stream(x);
     const auto ids = col.options().requires_grad(false);
+    ctx->saved_data["B"] = B;
     ctx->saved_data["has_value"] = has_value;
     ctx->saved_data["mean"] = mean;
     ctx->saved_data["P"] = (int64_t)0;
@@ -179,7 +203,8 @@ class SpmmRelFunction : public torch::autograd::Function<SpmmRelFunction> {
     if ((!want_x && !want_w) || !grad_outs[0].defined()) return none;
     TORCH_CHECK(!at::GradMode::is_enabled(), "spmm_rel: second-order gradients are not supported");
     Tensor weight = s[4].detach().contiguous();
-    const int64_t R = weight.size(0), F = weight.size(1), Fo = weight.size(2);
+    const int64_t B = ctx->saved_data["B"].toInt(), R = weight.size(0);
+    const int64_t F = B ? B * weight.size(2) : weight.size(1), Fo = B ? B * weight.size(3) : weight.size(2);
     if (P == 0) {
       if (want_x) none[7] = torch::zeros({N, F}, weight.options());
       if (want_w) none[8] = torch::zeros_like(weight);
@@ -213,10 +238,18 @@ class SpmmRelFunction : public torch::autograd::Function<SpmmRelFunction> {
     }
     if (want_w) {
       Tensor gw = torch::empty_like(weight, weight.options().requires_grad(false));
-      Tensor ws = workspace(tsamd_rel_wgrad_workspace_bytes(dt, P, R, F, Fo), weight);
-      check_status(tsamd_rel_wgrad(dt, H.data_ptr(), P, lp(q), g.data_ptr(), M, lp(prow_q), lp(relptr), gw.data_ptr(), P, R,
-                                   F, Fo, ws.data_ptr(), (size_t)ws.numel(), stream),
-                   "tsamd_rel_wgrad");
+      if (B) {
+        Tensor ws = workspace(tsamd_rel_wgrad_blocks_workspace_bytes(dt, P, R, B, F / B, Fo / B), weight);
+        check_status(tsamd_rel_wgrad_blocks(dt, H.data_ptr(), P, lp(q), g.data_ptr(), M, lp(prow_q), lp(relptr),
+                                            gw.data_ptr(), P, R, B, F / B, Fo / B, ws.data_ptr(), (size_t)ws.numel(),
+                                            stream),
+                     "tsamd_rel_wgrad_blocks");
+      } else {
+        Tensor ws = workspace(tsamd_rel_wgrad_workspace_bytes(dt, P, R, F, Fo), weight);
+        check_status(tsamd_rel_wgrad(dt, H.data_ptr(), P, lp(q), g.data_ptr(), M, lp(prow_q), lp(relptr), gw.data_ptr(), P,
+                                     R, F, Fo, ws.data_ptr(), (size_t)ws.numel(), stream),
+                     "tsamd_rel_wgrad");
+      }
       none[8] = gw;
     }
     return none;
@@ -226,6 +259,7 @@ class SpmmRelFunction : public torch::autograd::Function<SpmmRelFunction> {
 Tensor spmm_rel(Tensor rowptr, Tensor col, OptTensor value, Tensor row, Tensor rel, OptTensor colptr, OptTensor csr2csc,
                 Tensor x, Tensor weight, std::string reduce) {
   check_rel_args(rowptr, col, value, row, rel, x, weight, reduce);
+  if (weight.dim() == 4 && weight.size(1) == 1) weight = weight.squeeze(1);  // one block is the dense product
   return SpmmRelFunction::apply(rowptr, col, value.value_or(col), row, rel, colptr, csr2csc, x, weight, value.has_value(),
                                 reduce == "mean");
 }

@@ -18,7 +18,11 @@ def matmul_rel(src: SparseTensor, x: Tensor, weight: Tensor, rel: Tensor, reduce
     ``[nnz]`` tensor in the order of ``src.storage.col()`` with values in ``[0, R)`` -> ``[M, Fo]`` in the dtype of
     ``x``.  ``reduce='mean'`` is R-GCN's default: the sum over the relations of the mean over the entries of every
     (row, relation) pair.  fp32 accumulation; deterministic.  Differentiable (once) with respect to ``x`` and
-    ``weight``; a batched ``x`` and values that require a gradient are refused.  Scriptable."""
+    ``weight``; a batched ``x`` and values that require a gradient are refused.  Scriptable.
+
+    A 4-D ``weight [R, B, ci, co]`` (``B * ci = F``, ``Fo = B * co``) is R-GCN's block-diagonal decomposition,
+    ``weight[r] = diag(weight[r, 0] .. weight[r, B - 1])``: ``out[i, b co + n] = sum_e value[e] sum_k x[col[e], b ci + k]
+    weight[rel[e], b, k, n]``, contracted block by block (csrc/rel_blocks.hip); its gradient is ``[R, B, ci, co]``."""
     if reduce == 'add':
         reduce = 'sum'
     if reduce != 'sum' and reduce != 'mean':
@@ -29,15 +33,24 @@ def matmul_rel(src: SparseTensor, x: Tensor, weight: Tensor, rel: Tensor, reduce
         raise ValueError('matmul_rel: float32 or bfloat16 expected (float16 and float64 are not supported)')
     if x.size(0) != src.sparse_size(1):
         raise ValueError('x has %d rows, the sparse pattern has %d columns' % (x.size(0), src.sparse_size(1)))
-    if weight.dim() != 3:
-        raise ValueError('matmul_rel: weight must be [R, F, Fo], got %d dimensions' % weight.dim())
-    if weight.size(0) < 1 or weight.size(1) != x.size(1):
-        raise ValueError('matmul_rel: weight must be [R, F, Fo] with R >= 1 and F = %d, got [%d, %d, %d]' %
-                         (x.size(1), weight.size(0), weight.size(1), weight.size(2)))
+    if weight.dim() == 4:
+        if (weight.size(0) < 1 or weight.size(1) < 1 or weight.size(2) < 1 or weight.size(3) < 1
+                or weight.size(1) * weight.size(2) != x.size(1)):
+            raise ValueError('matmul_rel: a block-diagonal weight must be [R, B, ci, co] with R >= 1 and B * ci = %d, '
+                             'got [%d, %d, %d, %d]' % (x.size(1), weight.size(0), weight.size(1), weight.size(2),
+                                                       weight.size(3)))
+        Fo = weight.size(1) * weight.size(3)
+    else:
+        if weight.dim() != 3:
+            raise ValueError('matmul_rel: weight must be [R, F, Fo], got %d dimensions' % weight.dim())
+        if weight.size(0) < 1 or weight.size(1) != x.size(1):
+            raise ValueError('matmul_rel: weight must be [R, F, Fo] with R >= 1 and F = %d, got [%d, %d, %d]' %
+                             (x.size(1), weight.size(0), weight.size(1), weight.size(2)))
+        Fo = weight.size(2)
     if weight.dtype != x.dtype:
         raise ValueError('matmul_rel: weight and x differ in dtype')
-    if x.size(1) < 1 or x.size(1) > 512 or weight.size(2) < 1 or weight.size(2) > 512:
-        raise ValueError('matmul_rel: F and Fo must lie in 1 .. 512, got %d and %d' % (x.size(1), weight.size(2)))
+    if x.size(1) < 1 or x.size(1) > 512 or Fo < 1 or Fo > 512:
+        raise ValueError('matmul_rel: F and Fo must lie in 1 .. 512, got %d and %d' % (x.size(1), Fo))
     if rel.dtype != torch.int64 or rel.dim() != 1 or rel.numel() != src.nnz():
         raise ValueError('matmul_rel: rel must be an int64 tensor with one relation per entry ([%d]), got %d element(s) '
                          'in %d dimension(s)' % (src.nnz(), rel.numel(), rel.dim()))
