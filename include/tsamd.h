@@ -647,6 +647,39 @@ int tsamd_spmm_multi(int dtype, int mask, const int64_t *rowptr, const int64_t *
                      int64_t N, int64_t F, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * SpMM over quantised features (csrc/spmm_q8.hip): xq [N, F] holds OCP fp8 codes (e4m3fn, torch.float8_e4m3fn: one
+ * byte per element, 0x7f / 0xff NaN, no infinity), rows F bytes apart at ANY address, scale [N] float or NULL (ones),
+ * value [E] float or NULL (ones):
+ *   out[m, :] = reduce over e in [rowptr[m], rowptr[m+1]) of value[e] * scale[col[e]] * decode(xq[col[e], :])
+ * reduce TSAMD_SUM or TSAMD_MEAN (divided by the row's entries), out [M, F] contiguous in out_dtype TSAMD_F32 or
+ * TSAMD_BF16 (round-to-nearest-even), float32 accumulation, a row without entries gives 0, F in 0 .. 1024.
+ * Entry-balanced (a workgroup owns 2048 entries); no atomics, no host sync, three launches (fill of the rows without
+ * entries, tile, fix-up), deterministic.  No byte outside xq[0 .. N * F) is read.
+ * Status, in this order: a negative size TSAMD_ERR_INVALID; a reduce other than sum / mean, an out_dtype other than
+ * float32 / bfloat16, F > 1024, M >= 2^31 or N / E >= 2^32 TSAMD_ERR_UNSUPPORTED; M * F == 0 TSAMD_OK, nothing is
+ * touched; a null out TSAMD_ERR_INVALID; E == 0 TSAMD_OK with out zero-filled; a null rowptr / col / xq or N == 0
+ * TSAMD_ERR_INVALID; a workspace that is missing, smaller than tsamd_spmm_q8_workspace_bytes() (0 for what the call
+ * refuses) or off a 256-byte boundary TSAMD_ERR_WORKSPACE.
+ *   tsamd_spmm_q8_route (host arithmetic only; xq and out count for their alignment, NULL = aligned): route[0] bytes
+ *   per packet = codes per lane, the largest of 16 / 8 / 4 / 1 that divides F and the address of xq; route[1] lanes
+ *   per row (from F alone); route[2] groups (chunks) side by side in a wave; route[3] entries per chunk = 8 * route[1];
+ *   route[4] entries per workgroup tile (2048); route[5] column blocks; route[6] 1 when out is stored in 16-byte
+ *   packets; route[7] gathers in flight per lane; route[8] chunks = ceil(E / route[3]); route[9] bytes of the head
+ *   records (the tail records are as many) = align256(4 * F * route[8]); route[10] bytes of the head row ids (the tail
+ *   row ids are as many); route[11] the workspace = 2 * route[9] + 2 * route[10]; route[12..15] are 0.
+ *   tsamd_quantize_rows: x [N, F] in dtype float32, bfloat16 or float16 -> scale[n] = absmax(x[n, :]) / 448 (1 for a
+ *   row of zeros) and xq[n, f] = fp8(clamp(float(x[n, f]) / scale[n], -448, 448)): an IEEE float32 divide and
+ *   round-to-nearest-even.  Non-finite input is not supported.  A negative size TSAMD_ERR_INVALID, another dtype or a
+ *   size >= 2^31 TSAMD_ERR_UNSUPPORTED, N == 0 TSAMD_OK, a null array TSAMD_ERR_INVALID.
+ * ------------------------------------------------------------------------ */
+int tsamd_spmm_q8_route(int out_dtype, int64_t F, int64_t E, const void *xq, const void *out, int64_t route[16]);
+size_t tsamd_spmm_q8_workspace_bytes(int out_dtype, int64_t M, int64_t F, int64_t E);
+int tsamd_spmm_q8(int out_dtype, int reduce, const int64_t *rowptr, const int64_t *col, const float *value,
+                  const void *xq, const float *scale, void *out, int64_t M, int64_t N, int64_t F, int64_t E,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_quantize_rows(int dtype, const void *x, void *xq, float *scale, int64_t N, int64_t F, void *stream);
+
+/* ------------------------------------------------------------------------
  * Relational SpMM, the dense half (csrc/rel_gemm.hip): grouped products on the matrix instructions of gfx950.  The P
  * items t = 0 .. P - 1 are ordered by group; group g (a relation) is the items [relptr[g], relptr[g + 1]), relptr
  * [R + 1] int64 ascending from 0 to P.  float32 (v_mfma_f32_32x32x2_f32) and bfloat16 (v_mfma_f32_32x32x16_bf16), fp32
