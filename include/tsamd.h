@@ -917,6 +917,80 @@ int tsamd_gat_attention_heads_dropout_bw(int dtype, const int64_t *row, const in
                                          void *stream);
 int tsamd_attention_dropout_mask(uint64_t seed, double rate, int64_t e0, int64_t n, int64_t H, uint8_t *keep);
 
+/* ------------------------------------------------------------------------
+ * Fused GATv2 attention over a pattern (csrc/gatv2.hip): the score is a dot product of att with the activated SUM of
+ * the two feature rows, and the gathered row is also the value -- one gather per entry.  (rowptr, col) is the CSR
+ * order of the E entries; x_dst [nseg, H, D], x_src [nsrc, H, D], att [H, D], out [nseg, H, D] share one dtype,
+ * float32 or bfloat16; lse [nseg, H], out_acc [nseg, H, D], p and ds [E, H] are float.  fp32 accumulators, one rounding on the store.
+ * All arrays are contiguous.  No bias, no dropout.
+ *
+ *   tsamd_gatv2_attention     for the entries i of row r and head h:
+ *                               z(i, h, d)   = x_dst[r, h, d] + x_src[col[i], h, d]    (one fp32 add: the sign of z
+ *                                                                                       is the sign of the exact sum)
+ *                               s(i, h)      = sum_d att[h, d] * (z > 0 ? z : negative_slope * z)
+ *                               out[r, h, :] = sum_i softmax_i(s(., h)) * x_src[col[i], h, :]
+ *                               lse[r, h]    = log sum_i exp(s(i, h)).
+ *                             Rows without entries are zeros with lse = -inf; non-finite scores as in
+ *                             tsamd_attention_heads.  Three launches (fill, tile, fix-up), deterministic, no atomics,
+ *                             no host sync, nothing of size E written.  out_acc is NULL or receives out before its
+ *                             rounding to the dtype, for the rows that have entries (the others are not written): what
+ *                             the backward of a bfloat16 call needs.
+ *   tsamd_gatv2_attention_bw  per entry i of row r and head h, from the forward's lse and unrounded out: p = e(s(i, h)
+ *                             - lse[r, h]), ds = p * (<grad_out[r, h], x_src[col[i], h]> - <grad_out[r, h],
+ *                             out_acc[r, h]>), both [E, H] float in storage order.  out_acc is the forward's out for
+ *                             float32 and its out_acc for bfloat16: the rounding of out to bfloat16 would outweigh a
+ *                             gradient whose terms cancel.  lse[r, h] not finite: p = ds = NaN; s = -inf: p = ds = 0.
+ *                             row [E] holds the row ids or is NULL (then they are searched in rowptr; not both NULL).
+ *                             One launch, no workspace.
+ *   tsamd_gatv2_grad          over a segmented order (ptr [nseg + 1], ind [E], perm [E] or NULL: the entry's place in
+ *                             ds and p), u [nseg, H, D] indexed by segment, w [nsrc, H, D] gathered by ind:
+ *                               out[s, h, :] = sum_i ds[perm(i), h] * att[h, :] * (u[s, h, :] + w[ind[i], h, :] > 0 ?
+ *                                              1 : negative_slope)
+ *                             (the derivative at z == 0 is negative_slope).  (rowptr, col, NULL; x_dst, x_src) gives
+ *                             grad_x_dst, (colptr, row ids in column order, csr2csc; x_src, x_dst) the score part of
+ *                             grad_x_src.  flags: 1 (VALUE) also adds p[perm(i), h] * g[ind[i], h, :], g [nsrc, H, D]
+ *                             -- with g = grad_out the second call gives the whole grad_x_src; 2 (ATT) also writes
+ *                             grad_att[h, d] = sum_i ds[i, h] * leaky_relu(z(i, h, d)) ([H, D] of the dtype; partial
+ *                             rows per chunk, added in chunk order).  1 | 2 together is TSAMD_ERR_UNSUPPORTED, a bit
+ *                             above 2 TSAMD_ERR_INVALID; p, g and grad_att may be NULL where their flag is not set.  Segments without entries are
+ *                             zeros.  Fill, tile, fix-up (and the fold of grad_att): no atomics, deterministic.
+ *
+ * Status, in this order: a negative size TSAMD_ERR_INVALID; a dtype other than float32 / bfloat16, D above
+ * 64 * (16 / itemsize) (no feature-block split), nseg (2^31 and above) / nsrc / H / H * D above 2^31 - 1, more than
+ * 65535 column blocks, an out above 2^39 elements or an E whose byte offsets leave int64 TSAMD_ERR_UNSUPPORTED; then
+ *   forward, grad: nseg * H * D == 0 TSAMD_OK, nothing is written (grad with flag 2 still zero-fills grad_att); a null
+ *             out / lse / grad_att TSAMD_ERR_INVALID; E == 0 TSAMD_OK after the fill; a null operand or nsrc == 0
+ *             TSAMD_ERR_INVALID; a missing or short workspace TSAMD_ERR_WORKSPACE;
+ *   backward: E == 0 or H == 0 TSAMD_OK without a launch; D == 0, a null array (row and rowptr both), nseg == 0 or
+ *             nsrc == 0 TSAMD_ERR_INVALID.
+ * Every one of these is decided on the host before the first device call.
+ *
+ * tsamd_gatv2_route is host arithmetic only, through the function the driver plans with; only the alignment of the
+ * pointers is looked at (NULL counts as aligned).  out[0] route: 0 packets (D * itemsize a multiple of 16 and x_dst,
+ * x_src, out on a 16-byte boundary), 1 generic (element loads, any 1 <= D <= 64 * (16 / itemsize)); out[1] elements
+ * per load; out[2] lanes per head (a lane covers 16 / itemsize adjacent features on both routes); out[3] heads side
+ * by side; out[4] column blocks = ceil(H / out[3]); out[5] entries per chunk = 8 * out[2] * out[3]; out[6] the
+ * workspace in bytes = tsamd_gatv2_workspace_bytes(dtype, H, D, E), which serves all three calls: with nchunks =
+ * ceil(E / out[5]) and W = H * D the larger of
+ *   2 * align256(4 * nchunks * W) + 2 * align256(8 * nchunks * H) + 2 * align256(8 * nchunks)     (forward)
+ *   3 * align256(4 * nchunks * W) + 2 * align256(8 * nchunks)                                     (grad)
+ * (0 bytes for a dtype or a size that is not supported).
+ * ------------------------------------------------------------------------ */
+int tsamd_gatv2_route(int dtype, int64_t H, int64_t D, int64_t E, const void *x_dst, const void *x_src,
+                      const void *out, int64_t out_route[7]);
+size_t tsamd_gatv2_workspace_bytes(int dtype, int64_t H, int64_t D, int64_t E);
+int tsamd_gatv2_attention(int dtype, const int64_t *rowptr, const int64_t *col, const void *x_dst, const void *x_src,
+                          const void *att, double negative_slope, void *out, float *out_acc, void *lse, int64_t nseg,
+                          int64_t nsrc, int64_t H, int64_t D, int64_t E, void *workspace, size_t workspace_bytes, void *stream);
+int tsamd_gatv2_attention_bw(int dtype, const int64_t *row, const int64_t *rowptr, const int64_t *col,
+                             const void *x_dst, const void *x_src, const void *att, const float *out_acc,
+                             const void *lse, const void *grad_out, double negative_slope, float *p_out,
+                             float *ds_out, int64_t nseg, int64_t nsrc, int64_t H, int64_t D, int64_t E, void *stream);
+int tsamd_gatv2_grad(int dtype, int flags, const int64_t *ptr, const int64_t *ind, const int64_t *perm, const void *u,
+                     const void *w, const void *att, double negative_slope, const float *ds, const float *p,
+                     const void *g, void *out, void *grad_att, int64_t nseg, int64_t nsrc, int64_t H, int64_t D,
+                     int64_t E, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * COO ordering / sorting / coalescing. Replace the Python + ATen +
  * torch_scatter compositions of SparseStorage (torch_sparse/storage.py):

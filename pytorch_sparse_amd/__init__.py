@@ -61,7 +61,7 @@ from .spspmm import spspmm  # noqa: E402
 from .reduce import sum, mean, min, max  # noqa: E402,A004
 from .softmax import softmax  # noqa: E402
 from .segment import segment_softmax  # noqa: E402
-from .attention import sddmm, matmul_heads, attention, gat_attention  # noqa: E402
+from .attention import sddmm, matmul_heads, attention, gat_attention, gatv2_attention  # noqa: E402
 from .multi import matmul_multi  # noqa: E402
 from .rel import matmul_rel  # noqa: E402
 from .q8 import matmul_q8, quantize_rows  # noqa: E402
@@ -79,7 +79,7 @@ from .convert import to_torch_sparse, from_torch_sparse, to_scipy, from_scipy, e
 
 __all__ = [
     'SparseStorage', 'SparseTensor', 't', 'transpose', 'matmul', 'coalesce', 'spmm', 'spspmm',
-    'sum', 'mean', 'min', 'max', 'softmax', 'segment_softmax', 'sddmm', 'matmul_heads', 'matmul_multi', 'matmul_rel', 'matmul_q8', 'quantize_rows', 'attention', 'gat_attention', 'mul', 'mul_', 'mul_nnz', 'mul_nnz_', 'add', 'add_', 'add_nnz',
+    'sum', 'mean', 'min', 'max', 'softmax', 'segment_softmax', 'sddmm', 'matmul_heads', 'matmul_multi', 'matmul_rel', 'matmul_q8', 'quantize_rows', 'attention', 'gat_attention', 'gatv2_attention', 'mul', 'mul_', 'mul_nnz', 'mul_nnz_', 'add', 'add_', 'add_nnz',
     'add_nnz_', 'narrow', '__narrow_diag__', 'select', 'index_select', 'index_select_nnz',
     'masked_select', 'masked_select_nnz', 'permute', 'cat', 'remove_diag', 'set_diag', 'fill_diag',
     'get_diag', 'sample', 'sample_adj', 'random_walk', 'saint_subgraph', 'reverse_cuthill_mckee', 'partition', 'to_torch_sparse', 'from_torch_sparse', 'to_scipy', 'from_scipy', 'eye', 'spadd',

@@ -31,6 +31,12 @@ Both fused calls take ``dropout`` on the probabilities (the DROP instantiations 
 Philox function of ``(seed, entry, head)`` recomputed in the backward, so training with attention dropout keeps the
 fused pass and its memory: ``out = sum softmax(score) * keep / (1 - dropout) * v``, and the backward kernel returns
 ``p * keep / (1 - dropout)`` and ``ds = p * (keep / (1 - dropout) * <grad_out, v> - <grad_out, out>)``.
+
+``gatv2_attention(adj, x_dst, x_src, att, negative_slope=0.2)`` is the fused pass for the GATv2 score ``<att,
+leaky_relu(x_dst[row] + x_src[col])>`` (``tsamd::gatv2_attention_heads``, csrc/gatv2.hip): the gathered row ``x_src[col]``
+is the score operand and the value, one gather per entry.  Its backward (``tsamd::gatv2_attention_heads_bw`` for ``p``
+and ``ds``, then ``tsamd::gatv2_grad`` over the rows and over the columns) recomputes ``z`` from the two rows, so the
+``[nnz, H, D]`` sum is never written in either direction.
 """
 from typing import Optional
 
@@ -391,6 +397,98 @@ def gat_attention(adj: SparseTensor, a_dst: Tensor, a_src: Tensor, v: Tensor, ne
     return out.squeeze(1) if flat else out
 
 
+class _Gatv2AttentionHeads(torch.autograd.Function):
+    """out = tsamd::gatv2_attention_heads; backward: (p, ds) = tsamd::gatv2_attention_heads_bw from lse and the
+    unrounded out (a bfloat16 forward keeps an fp32 copy for it), then tsamd::gatv2_grad once over the rows (grad_x_dst,
+    and grad_att with it) and once over the columns with the value term (grad_x_src).  Each walk runs only where its gradient is asked for; nothing of size nnz * D is formed."""
+
+    @staticmethod
+    def forward(ctx, x_dst: Tensor, x_src: Tensor, att: Tensor, row: Optional[Tensor], rowptr: Tensor, col: Tensor,
+                colptr: Optional[Tensor], row_csc: Optional[Tensor], csr2csc: Optional[Tensor], slope: float):
+        out, lse, out_acc = torch.ops.tsamd.gatv2_attention_heads(rowptr, col, x_dst.detach(), x_src.detach(), att.detach(),
+                                                                  slope, True)
+        ctx.slope, ctx.has_row, ctx.has_csc = slope, row is not None, colptr is not None
+        ctx.save_for_backward(*([x_dst, x_src, att, out_acc, lse, rowptr, col] + ([row] if ctx.has_row else []) +
+                                ([colptr, row_csc, csr2csc] if ctx.has_csc else [])))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        x_dst, x_src, att, out_acc, lse, rowptr, col = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        row = rest.pop(0) if ctx.has_row else None
+        g = grad_out.contiguous()  # expanded / transposed gradients arrive here
+        p, ds = torch.ops.tsamd.gatv2_attention_heads_bw(row, rowptr, col, x_dst, x_src, att, out_acc, lse, g, ctx.slope)
+        grad_dst = grad_src = grad_att = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            grad_dst, ga = torch.ops.tsamd.gatv2_grad(rowptr, col, None, x_dst, x_src, att, ctx.slope, ds, None, None,
+                                                      ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[2]:
+                grad_att = ga
+            if not ctx.needs_input_grad[0]:
+                grad_dst = None
+        if ctx.needs_input_grad[1]:
+            colptr, row_csc, csr2csc = rest
+            grad_src = torch.ops.tsamd.gatv2_grad(colptr, row_csc, csr2csc, x_src, x_dst, att, ctx.slope, ds, p, g,
+                                                  False)[0]
+        return grad_dst, grad_src, grad_att, None, None, None, None, None, None, None
+
+
+def gatv2_attention(adj: SparseTensor, x_dst: Tensor, x_src: Tensor, att: Tensor, negative_slope: float = 0.2) -> Tensor:
+    """GATv2 attention over the pattern of ``adj`` in one fused pass (``tsamd::gatv2_attention_heads``, csrc/gatv2.hip): for
+    row ``m`` and head ``h`` the score of a stored entry ``(m, n)`` is ``(att[h] * leaky_relu(x_dst[m, h] + x_src[n, h],
+    negative_slope)).sum()`` and ``out[m, h] = sum_n softmax_n(score) * x_src[n, h]``: the gathered row is the score
+    operand and the value, so the ``[nnz, H, D]`` sum a layer would build is never formed, forward or backward.  ``x_dst
+    [M, H, D]``, ``x_src [N, H, D]`` (the transformed node features), ``att [H, D]`` -> ``[M, H, D]``; 2-D ``x_dst`` /
+    ``x_src`` with a 1-D ``att`` mean one head.  The values of ``adj`` are not read.  Rows without entries are zeros.
+
+    float32 and bfloat16, ``D <= 64 * (16 / itemsize)`` (256 / 512).  Differentiable (once) w.r.t. ``x_dst``, ``x_src`` and
+    ``att``; the derivative of the activation at ``z == 0`` is ``negative_slope``, as torch has it.  The same tensor may
+    be passed for ``x_dst`` and ``x_src`` (shared weights): autograd adds its two gradients.  No bias, no dropout."""
+    for t, name in ((x_dst, 'x_dst'), (x_src, 'x_src'), (att, 'att')):
+        if not isinstance(t, Tensor):
+            raise TypeError('%s must be a Tensor' % name)
+    if not (x_dst.dim() == x_src.dim() == att.dim() + 1) or x_dst.dim() not in (2, 3):
+        raise ValueError('x_dst, x_src and att must be [rows, D], [columns, D] and [D] or [rows, H, D], [columns, H, D] '
+                         'and [H, D], got %d, %d and %d dimensions' % (x_dst.dim(), x_src.dim(), att.dim()))
+    _check_operand(x_dst, 'x_dst', adj.sparse_size(0), 'rows')
+    _check_operand(x_src, 'x_src', adj.sparse_size(1), 'columns')
+    if x_dst.dtype != x_src.dtype or x_dst.dtype != att.dtype:
+        raise ValueError('x_dst, x_src and att differ in dtype: %s, %s and %s' % (x_dst.dtype, x_src.dtype, att.dtype))
+    if x_dst.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('gatv2_attention supports float32 and bfloat16, got %s' % x_dst.dtype)
+    if x_src.shape[1:] != x_dst.shape[1:]:
+        raise ValueError('x_src must be %s per row like x_dst, got %s: the gathered row is also the value, a value width '
+                         'of its own is not supported' % (tuple(x_dst.shape[1:]), tuple(x_src.shape[1:])))
+    if att.shape != x_dst.shape[1:]:
+        raise ValueError('att must be %s, got %s' % (tuple(x_dst.shape[1:]), tuple(att.shape)))
+    flat = x_dst.dim() == 2
+    if flat:
+        x_dst, x_src, att = x_dst.unsqueeze(1), x_src.unsqueeze(1), att.unsqueeze(0)
+    D = x_dst.size(2)
+    if D == 0:
+        raise ValueError('gatv2_attention needs at least one feature per head')
+    limit = 64 * (16 // x_dst.element_size())
+    if D > limit:
+        raise ValueError('gatv2_attention supports at most %d features per head in %s, got %d'
+                         % (limit, x_dst.dtype, D))
+    negative_slope = float(negative_slope)
+    if negative_slope != negative_slope or negative_slope in (float('inf'), float('-inf')):
+        raise ValueError('negative_slope must be finite, got %r' % negative_slope)
+    st = adj.storage
+    rowptr, col = st.rowptr(), st.col()
+    if torch.is_grad_enabled() and (x_dst.requires_grad or x_src.requires_grad or att.requires_grad):
+        csc = _csc_side(st) if x_src.requires_grad else (None, None, None)
+        out = _Gatv2AttentionHeads.apply(x_dst, x_src, att, st._row, rowptr, col, csc[0], csc[1], csc[2],
+                                         negative_slope)
+    else:
+        out = torch.ops.tsamd.gatv2_attention_heads(rowptr, col, x_dst, x_src, att, negative_slope)[0]
+    return out.squeeze(1) if flat else out
+
+
+SparseTensor.gatv2_attention = (lambda self, x_dst, x_src, att, negative_slope=0.2:
+                                gatv2_attention(self, x_dst, x_src, att, negative_slope))
 SparseTensor.gat_attention = (lambda self, a_dst, a_src, v, negative_slope=0.2, bias=False, dropout=0.0, training=True,
                               seed=None: gat_attention(self, a_dst, a_src, v, negative_slope, bias, dropout, training, seed))
 SparseTensor.attention = (lambda self, q, k, v, scale=None, bias=False, dropout=0.0, training=True, seed=None:

@@ -24,8 +24,8 @@ OBJDIR = os.path.join(ROOT, 'build', 'obj')
 ARCH = 'gfx950'
 
 HIP_SOURCES = ['api.hip', 'spmm.hip', 'spmm_min.hip', 'spmm_max.hip', 'spmm_partial.hip', 'spmm_bw.hip', 'spmm_ref_order.hip', 'spmm_coo.hip', 'convert.hip', 'scan.hip', 'sort.hip',
-               'coalesce.hip', 'spspmm.hip', 'spspmm_bw.hip', 'select.hip', 'sample.hip', 'hgt_sample.hip', 'segreduce.hip', 'softmax.hip', 'sddmm.hip', 'spmm_heads.hip', 'spmm_multi.hip', 'attention.hip', 'partition.hip', 'rcm.hip', 'rel_gemm.hip', 'rel_blocks.hip', 'spmm_q8.hip']
-OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_spspmm.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp', 'ops_spmm_multi.cpp', 'ops_rel.cpp', 'ops_q8.cpp']
+               'coalesce.hip', 'spspmm.hip', 'spspmm_bw.hip', 'select.hip', 'sample.hip', 'hgt_sample.hip', 'segreduce.hip', 'softmax.hip', 'sddmm.hip', 'spmm_heads.hip', 'spmm_multi.hip', 'attention.hip', 'gatv2.hip', 'partition.hip', 'rcm.hip', 'rel_gemm.hip', 'rel_blocks.hip', 'spmm_q8.hip']
+OPS_SOURCES = ['ops_spmm.cpp', 'ops_spmm_state.cpp', 'ops_storage.cpp', 'ops_spspmm.cpp', 'ops_sample.cpp', 'ops_sample_hetero.cpp', 'ops_sample_hgt.cpp', 'ops_partition.cpp', 'ops_rcm.cpp', 'ops_attention.cpp', 'ops_gatv2.cpp', 'ops_spmm_multi.cpp', 'ops_rel.cpp', 'ops_q8.cpp']
 # per-source flags.  spmm_multi.hip: no packed fp32 arithmetic -- every add and fma of the moment sums is a scalar
 # instruction in the order the source states, in all three instantiations
 HIP_EXTRA_FLAGS = {'spmm_multi.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
